@@ -15,7 +15,10 @@ process, before anything touches the GPU); under an external launcher it checks 
 rank holds a full index replica and its own 50 M-read shard (weak scaling); the only collective is the
 final all-reduce of the statistics block over RCCL.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (wall clock of one timed
+step), the mapping statistics and the kernel times of the timed steps.  A plain run builds the index, warms up, times
+--steps steps of the headline leg and prints that line; `--dump-outputs DIR` writes the leg's records of its last step
+as .npy files first.  `--full` adds everything else the bench measures and checks:
   roofline     : algorithmic bytes of the implemented search per launch (128-byte line per dependent
                  gather; DESIGN.md section 6) / HIP-event duration of the mapping kernels, vs 8 TB/s;
                  measured HBM traffic (PMC, profiles/traffic.json) beside it
@@ -39,6 +42,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 HBM_PEAK = 8.0e12  # B/s, MI355X_MICROARCH.md "HBM3E peak BW"
+DUMP_SAMPLE = 1 << 19  # records --dump-outputs writes at most (14 float64 fields of pairs: 59 MB)
 
 
 def csrc_sha():
@@ -90,13 +94,13 @@ def parse_args(argv):
     ap.add_argument("--bucket", type=int, default=5000)
     ap.add_argument("--dir-bits", type=int, default=-1)
     ap.add_argument("--contigs", type=int, default=0, help="cut the genome into this many equal contigs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle legs (cpu_baseline, roofline)")
     ap.add_argument("--mode", choices=["se", "pe"], default="se", help="headline leg: se = configs[1], pe = configs[2]")
     ap.add_argument("--ag", action="store_true", help="single-end -A: A-rich reads on the _GA10/_GA11 indexes")
     ap.add_argument("--pbat", action="store_true", help="paired-end -P: mate 1 is the A-rich mate (mates exchanged for mapping)")
     ap.add_argument("--top-k", type=int, default=50)
     ap.add_argument("--frag-range", type=int, default=1000)
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_lines legs (configs[2], configs[4])")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_lines legs (configs[2], configs[4])")
     ap.add_argument("--extra-pairs", type=int, default=0, help="pairs of the extra paired-end legs (default: --reads, 150 bp: half)")
     ap.add_argument("--extra-steps", type=int, default=10)
     ap.add_argument("--extra-contigs", type=int, default=3000,
@@ -118,7 +122,20 @@ def parse_args(argv):
                     help="an option of the mapping library on every index the run opens (walt_index_set_option; A/B runs)")
     ap.add_argument("--pattern", type=int, choices=[3, 5, 7], default=3,
                     help="seed pattern (the reference's -D SEEDPATTERN3/5/7); 5 and 7 use libwalt_amd_sp5/_sp7.so")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: oracle exactness sample, cpu_baseline, roofline, "
+                         "the reference binary, the extra legs, calibration, the gather ceiling and the C ABI all-reduce "
+                         "cross-check (--no-cpu-baseline, --no-extra, --no-calibration trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline leg's records of its last step as DIR/<field>.npy "
+                         "(float64; a fixed, seeded sample of at most %d reads or pairs) and its mapping statistics" % DUMP_SAMPLE)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does what the headline figure needs and nothing else
+        args.no_cpu_baseline = args.no_extra = args.no_calibration = True
+    return args
 
 
 def apply_opts(idx, args):
@@ -148,6 +165,30 @@ def launch_ranks(args, argv):
 
 class Ctx:
     pass
+
+
+def dump_outputs(cx, d_out, n, pairs, mapping, out_dir):
+    """--dump-outputs: the records a caller of the timed path receives (walt_best_match per read, walt_pair_result per
+    pair), from its last step, one float64 array per field; above DUMP_SAMPLE records a fixed, seeded sample of them
+    (`index` holds the record numbers).  mapping.npy: the line's mapping statistics, over every record."""
+    import numpy as np
+    torch, walt_amd = cx.torch, cx.walt_amd
+    os.makedirs(out_dir, exist_ok=True)
+    rec_bytes = 64 if pairs else 16
+    ix = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(12345).integers(0, n, DUMP_SAMPLE))
+    rows = d_out.view(n, rec_bytes)[torch.from_numpy(ix).to(cx.dev)].cpu().numpy()
+    rec = rows.view(walt_amd.pair_result_dtype if pairs else walt_amd.best_match_dtype).reshape(-1)
+    cols = {"index": ix}
+    mates = (("m1_", rec["m1"]), ("m2_", rec["m2"])) if pairs else (("", rec),)
+    for pre, m in mates:
+        cols.update({pre + "genome_pos": m["genome_pos"], pre + "times": m["times"],
+                     pre + "strand": m["strand"].view(np.uint8), pre + "mismatch": m["mismatch"]})
+    if pairs:
+        cols.update({f: rec[f] for f in ("best_times", "frag_len", "best_i", "best_j", "pair_mm")})
+    cols["mapping"] = np.array(mapping)
+    for name, a in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log("outputs of the last step: %d of %d records (%d fields) in %s" % (ix.size, n, len(cols) - 2, out_dir))
 
 
 # ------------------------------------------------------------------------------------------------ single-end
@@ -1011,8 +1052,10 @@ def worker(args):
         st = wdist.allreduce_stats(vec)
         total, uniq, amb, unm, short = [int(v) for v in st.tolist()]
         c_abi = None
-        if world > 1 and not shared_gpu:  # the same sum through the C ABI (walt_stats_allreduce over RCCL)
+        if args.full and world > 1 and not shared_gpu:  # the same sum through the C ABI (walt_stats_allreduce over RCCL)
             c_abi = wdist.c_abi_cross_check(local, vec_local, [total, uniq, amb, unm, short])
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(cx, leg["d_out"], n, False, [total, uniq, amb, unm, short], args.dump_outputs)
         if os.environ.get("WALT_AMD_STAMPS"):
             buf = (ctypes.c_ulonglong * 16)()
             if walt_amd.lib().walt_profile_stamps(buf) == 0:
@@ -1214,8 +1257,10 @@ def worker(args):
                                 "frag_len_mean": float((hist * np.arange(hist.size)).sum() / max(1.0, hist.sum())),
                                 "unique_frac": v[1] / max(1, v[0])},
                     "lists_last_pass": leg["lists"]}
-            if headline and world > 1 and not shared_gpu:
+            if headline and args.full and world > 1 and not shared_gpu:
                 line["stats_allreduce_c_abi"] = wdist.c_abi_cross_check(local, vec_local, v)
+            if headline and rank == 0 and args.dump_outputs:
+                dump_outputs(cx, leg["d_out"], npairs, True, v, args.dump_outputs)
             if headline:
                 out = line if rank == 0 else None
             else:

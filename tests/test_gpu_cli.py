@@ -8,7 +8,7 @@ import subprocess
 import pytest
 
 import refio
-from test_oracle_golden import META
+from test_oracle_golden import META, run_se_case
 
 pytestmark = pytest.mark.gpu
 
@@ -134,16 +134,14 @@ def _awkward_copy(src, dst, seed):
         f.write(data)
 
 
-@pytest.mark.parametrize("mode,extra", [("se", ["-N", "10000000"]), ("se", ["-N", "37", "-sam"]), ("se", ["-N", "1000", "-A"]),
-                                         ("pe", ["-N", "10000000", "-sam"]), ("pe", ["-N", "53"])])
-@pytest.mark.parametrize("threads", ["1", "6"])
-def test_cli_awkward_fastq_matches_reference_binary(cli_index, scratch, mode, extra, threads):
-    """Both binaries on the same awkward FASTQ: exercises the threaded loader's batch boundaries
-    and the srand(0)-per-batch N replacement end to end."""
-    if not os.path.exists(refio.REF_WALT):
-        pytest.skip("oracle/_ref/walt not built")
+AWKWARD_CASES = [("se", ["-N", "10000000"]), ("se", ["-N", "37", "-sam"]), ("se", ["-N", "1000", "-A"]),
+                 ("pe", ["-N", "10000000", "-sam"]), ("pe", ["-N", "53"])]
+
+
+def awkward_run(binary, index, wd, mode, extra, threads):
+    """`binary` on the awkward copies of the golden reads of `mode`; returns (tag, {output file: bytes})."""
     tag = "%s_%s_%s" % (mode, "_".join(a.strip("-") for a in extra), threads)
-    wd = os.path.join(scratch, "awk_" + tag)
+    wd = os.path.join(wd, "awk_" + tag)
     os.makedirs(wd, exist_ok=True)
     if mode == "se":
         fq = os.path.join(wd, "reads.fastq")
@@ -154,19 +152,31 @@ def test_cli_awkward_fastq_matches_reference_binary(cli_index, scratch, mode, ex
         _awkward_copy(os.path.join(refio.GOLDEN, "pe_1.fastq"), f1, 4)
         _awkward_copy(os.path.join(refio.GOLDEN, "pe_2.fastq"), f2, 5)
         inputs = ["-1", f1, "-2", f2]
-    outs = {}
-    for who, binary in (("gpu", WALT_BIN), ("ref", refio.REF_WALT)):
-        od = os.path.join(wd, who)
-        os.makedirs(od, exist_ok=True)
-        for fn in os.listdir(od):
-            os.remove(os.path.join(od, fn))
-        subprocess.run([binary, "-i", cli_index, "-o", os.path.join(od, "out"), "-a", "-u", "-t", threads] + inputs + extra,
-                       check=True, stderr=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
-        outs[who] = {fn: open(os.path.join(od, fn), "rb").read() for fn in sorted(os.listdir(od))}
-    assert sorted(outs["gpu"]) == sorted(outs["ref"])
-    for fn in outs["ref"]:
-        assert outs["gpu"][fn] == outs["ref"][fn], "%s: %s differs" % (tag, fn)
-    assert len(outs["ref"]["out"]) > 1000
+    od = os.path.join(wd, "out")
+    os.makedirs(od, exist_ok=True)
+    for fn in os.listdir(od):
+        os.remove(os.path.join(od, fn))
+    subprocess.run([binary, "-i", index, "-o", os.path.join(od, "out"), "-a", "-u", "-t", threads] + inputs + extra,
+                   check=True, stderr=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
+    return tag, {fn: open(os.path.join(od, fn), "rb").read() for fn in sorted(os.listdir(od))}
+
+
+@pytest.mark.parametrize("mode,extra", AWKWARD_CASES)
+@pytest.mark.parametrize("threads", ["1", "6"])
+def test_cli_awkward_fastq_matches_reference_binary(cli_index, scratch, mode, extra, threads):
+    """The product binary on an awkward FASTQ writes the files the REAL reference binary wrote for it (their md5 and
+    size, recorded in tests/golden/refbin.json by tests/golden/make_golden_refbin.py): exercises the threaded
+    loader's batch boundaries and the srand(0)-per-batch N replacement end to end."""
+    import hashlib
+    import json
+    with open(os.path.join(refio.GOLDEN, "refbin.json")) as f:
+        gold = json.load(f)["awkward"]
+    tag, got = awkward_run(WALT_BIN, cli_index, scratch, mode, extra, threads)
+    want = gold[tag]
+    assert sorted(got) == sorted(want)
+    for fn, (md5, size) in want.items():
+        assert (hashlib.md5(got[fn]).hexdigest(), len(got[fn])) == (md5, size), "%s: %s differs" % (tag, fn)
+    assert want["out"][1] > 1000
 
 
 def _run_cli(wd, args):
@@ -259,14 +269,19 @@ def test_cli_makedb_on_gpu_writes_files_the_reference_binary_maps_from(scratch):
     for s in range(4):
         assert (a.genome[s] == b.genome[s]).all() and (a.counter[s] == b.counter[s]).all()
         assert sorted(a.index[s].tolist()) == sorted(b.index[s].tolist())
-    if not os.path.exists(refio.REF_WALT):
-        pytest.skip("oracle/_ref/walt not built")
-    outs = []
-    for who, binary in (("gpu", WALT_BIN), ("ref", refio.REF_WALT)):
-        o = os.path.join(scratch, "mk_%s.sam" % who)
-        if os.path.exists(o):
-            os.remove(o)
-        subprocess.run([binary, "-i", dev, "-r", os.path.join(refio.GOLDEN, "se_ct.fastq"), "-o", o, "-sam", "-a", "-u"],
-                       check=True, stderr=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
-        outs.append(open(o, "rb").read())
-    assert outs[0] == outs[1] and len(outs[0]) > 1000
+    # both binaries must produce the same SAM from the GPU-built files: the reference's is what the oracle port, pinned
+    # byte for byte to the real binary's files (test_oracle_golden.py), writes from them for golden case se_sam_au
+    # (se_ct.fastq -sam -a -u)
+    o = os.path.join(scratch, "mk_gpu.sam")
+    if os.path.exists(o):
+        os.remove(o)
+    subprocess.run([WALT_BIN, "-i", dev, "-r", os.path.join(refio.GOLDEN, "se_ct.fastq"), "-o", o, "-sam", "-a", "-u"],
+                   check=True, stderr=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
+    with open(o) as f:
+        got = f.read()
+
+    def mapper(seqs, ag, m, b_):
+        recs, work = refio.oracle_se(b, seqs, ag=ag, max_mm=m, b=b_)
+        return recs, int(work["too_short"])
+    want = run_se_case(b, "se_sam_au", mapper)["out.sam"]
+    assert got == want and len(got) > 1000

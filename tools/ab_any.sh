@@ -9,7 +9,7 @@ mkdir -p $OUT
 for SPEC in "$@"; do
   NAME=${SPEC%%|*}; REST=${SPEC#*|}; ENVS=${REST%%|*}; ARGS=${REST#*|}
   echo "== $NAME: env [$ENVS] args [$ARGS]"
-  ( export $ENVS; timeout -k 10 1100 python3 bench.py $ARGS > $OUT/$NAME.json 2> $OUT/$NAME.log ) || { echo "$NAME failed"; tail -n 8 $OUT/$NAME.log; exit 1; }
+  ( export $ENVS; timeout -k 10 1100 python3 bench.py --full $ARGS > $OUT/$NAME.json 2> $OUT/$NAME.log ) || { echo "$NAME failed"; tail -n 8 $OUT/$NAME.log; exit 1; }
   python3 - "$OUT/$NAME.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ mkdir -p $OUT
 for SPEC in "$@"; do
   NAME=${SPEC%%|*}; REST=${SPEC#*|}; ENVS=${REST%%|*}; ARGS=${REST#*|}
   echo "== $NAME: env [$ENVS] args [$ARGS]"
-  ( [ -n "$ENVS" ] && export $ENVS; timeout -k 10 900 python3 bench.py $ARGS > $OUT/$NAME.json 2> $OUT/$NAME.log ) || { echo "$NAME failed"; tail -n 5 $OUT/$NAME.log; exit 1; }
+  ( [ -n "$ENVS" ] && export $ENVS; timeout -k 10 900 python3 bench.py --full $ARGS > $OUT/$NAME.json 2> $OUT/$NAME.log ) || { echo "$NAME failed"; tail -n 5 $OUT/$NAME.log; exit 1; }
   python3 - "$OUT/$NAME.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -169,6 +169,40 @@ int walt_map_se_batch_device(walt_index* idx, const void* d_bases, const void* d
                              uint32_t b, void* d_out, void* d_stats, void* d_workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- single-end random PBAT: each read mapped under BOTH conversions -------
+ * For libraries whose reads come in either conversion (random-primed PBAT, most single-cell bisulfite protocols:
+ * some reads T-rich, some A-rich).  The reference has no such mode; its contract is defined here.  With
+ *   c = the record walt_map_se_batch(..., ag_wildcard = 0, ...) returns for a read (C->T, strands _CT00/_CT01),
+ *   g = the record the same call returns with ag_wildcard = 1 (G->A, strands _GA10/_GA11),
+ * both with the same max_mismatches and b, the record r and its conversion conv ('T' or 'A') follow from the first
+ * rule that applies:
+ *   1. c.times == 1 && g.times == 1 && c.genome_pos == g.genome_pos && c.strand == g.strand (the same alignment
+ *      under both conversions: a read with no informative C or G): r = c, conv = 'T';
+ *   2. g.times == 0, or c.times > 0 && c.mismatch < g.mismatch: r = c, conv = 'T' (both unmapped: c's initial
+ *      record (0, 0, '+', max_mismatches));
+ *   3. c.times == 0, or g.mismatch < c.mismatch: r = g, conv = 'A';
+ *   4. otherwise (both mapped with equal mismatches): r = c with r.times = c.times + g.times (>= 2: ambiguous),
+ *      conv = 'T'.
+ * Both conversions start from (0, 0, '+', max_mismatches); the G->A pass is not seeded with the C->T result.
+ * Statistics: too_short is what a single-conversion call reports (one count per strand pass: a read is short under
+ * both conversions); probes, candidates and big_regions are the sums over both conversions.
+ * The index must hold all four strands (WALT_STRANDS_ALL); otherwise the call fails with WALT_EINVAL and names the
+ * missing ones.  Every option of the index (walt_index_set_option) applies to both conversions, none changes r.
+ * Host form: as walt_map_se_batch (offsets relative to offsets[0]; WALT_EBASE for a read with a non-ACGT base,
+ * WALT_EINVAL as there); conv[n] receives 'T' / 'A' per read.  A second single-end call on the same index while
+ * this one runs is refused with WALT_EINVAL before it touches anything of the first.
+ * Device form: as walt_map_se_batch_device, plus d_conv (uint8_t[n]); d_out and d_workspace 16-byte aligned;
+ * d_workspace holds walt_se_rpbat_workspace_bytes(n, max_read_len) bytes (walt_se_workspace_bytes plus the G->A
+ * records), and a smaller workspace is refused with WALT_EINVAL. */
+size_t walt_se_rpbat_workspace_bytes(uint32_t n, uint32_t max_read_len);
+int walt_map_se_rpbat_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n,
+                            uint32_t max_mismatches, uint32_t b, walt_best_match* out, uint8_t* conv,
+                            walt_batch_stats* stats);
+int walt_map_se_rpbat_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                   uint32_t max_read_len, uint32_t max_mismatches, uint32_t b, void* d_out,
+                                   void* d_conv, void* d_stats, void* d_workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* The device-resident calls are asynchronous, so invalid input cannot come back as their status.
  * walt_batch_check waits for `stream` and reports what the last call on `d_workspace` found:
  * WALT_EBASE (a read holds a non-ACGT base: the reference's getBits exits, util.hpp:117-119; its

@@ -167,5 +167,74 @@ def run_soak(seconds, seed0=1, pattern=3, max_genomes=None):
         args.pattern, cases, reads_total, pairs_total, args.seed0, seed - 1)
 
 
+def run_soak_rpbat(seeds, pattern=3):
+    """Random PBAT (walt_map_se_rpbat_batch) on the genomes of `seeds`: each read drawn T-rich or A-rich at random, the
+    GPU's records and conversions compared with the rule of include/walt_amd.h applied to the oracle's C->T and G->A
+    runs.  Returns the summary line, raises SoakMismatch at the first difference (tests/test_gpu_rpbat_soak.py)."""
+    import refio
+    import walt_amd
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 260)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    reads_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 104729 + 1)  # a generator of its own: run_soak's draws for a seed stay as they are
+            tmp = tempfile.mkdtemp(prefix="walt_soak_rpbat_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, s in seqs:
+                        f.write(">%s\n%s\n" % (nm, s))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL)
+                try:
+                    g_opt = rng.choice([0, 0, 0, 1, 2])
+                    if g_opt:
+                        idx.set_option("grid", g_opt)
+                    lengths = [lo + 2, 40, 60, 100, 100, 131, min(150, hi), hi]
+                    m, b = rng.choice([0, 2, 6, 10]), rng.choice([2, 30, 5000])
+                    reads = [sample(rng, seqs, 1, rng.choice(["CT", "GA"]), lengths, refio)[0] for _ in range(1500)]
+                    c, _ = refio.oracle_se(db, reads, ag=False, max_mm=m, b=b)
+                    g, _ = refio.oracle_se(db, reads, ag=True, max_mm=m, b=b)
+                    got, conv, _ = idx.map_se_rpbat_batch(*walt_amd.pack_reads(reads), max_mismatches=m, b=b)
+                finally:
+                    idx.close()
+                want, want_conv = rpbat_rule(c, g)
+                for f in ("genome_pos", "times", "strand", "mismatch"):
+                    if not np.array_equal(got[f], want[f]):
+                        bad = int(np.nonzero(got[f] != want[f])[0][0])
+                        raise SoakMismatch("MISMATCH random PBAT seed %d field %s read %d (%s) m=%d b=%d" % (seed, f, bad, reads[bad], m, b))
+                if not np.array_equal(conv, want_conv):
+                    bad = int(np.nonzero(conv != want_conv)[0][0])
+                    raise SoakMismatch("MISMATCH random PBAT seed %d conv read %d (%s) m=%d b=%d" % (seed, bad, reads[bad], m, b))
+                reads_total += len(reads)
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    return "soak ok: random PBAT, pattern %d, %d genomes, %d reads identical to the rule on the oracle" % (
+        pattern, len(seeds), reads_total)
+
+
+def rpbat_rule(c, g):
+    """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
+    ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)
+    r1 = (ct == 1) & (gt == 1) & (c["genome_pos"] == g["genome_pos"]) & (c["strand"] == g["strand"])
+    r2 = ~r1 & ((gt == 0) | ((ct > 0) & (c["mismatch"] < g["mismatch"])))
+    r3 = ~r1 & ~r2 & ((ct == 0) | (g["mismatch"] < c["mismatch"]))
+    r4 = ~r1 & ~r2 & ~r3
+    rec = c.copy()
+    for f in ("genome_pos", "times", "strand", "mismatch"):
+        rec[f] = np.where(r3, g[f], c[f])
+    rec["times"][r4] = (ct + gt)[r4]
+    return rec, np.where(r3, ord("A"), ord("T")).astype(np.uint8)
+
+
 if __name__ == "__main__":
     main()

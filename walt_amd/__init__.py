@@ -174,6 +174,10 @@ def lib(pattern=None):
     L.walt_se_workspace_bytes.restype = c.c_size_t
     L.walt_map_se_batch_device.argtypes = [vp, vp, vp, u32, u32, ci, u32, u32, vp, vp, vp, c.c_size_t, vp]
     L.walt_batch_check.argtypes = [vp, vp]
+    L.walt_se_rpbat_workspace_bytes.argtypes = [u32, u32]
+    L.walt_se_rpbat_workspace_bytes.restype = c.c_size_t
+    L.walt_map_se_rpbat_batch.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.walt_map_se_rpbat_batch_device.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, c.c_size_t, vp]
     L.walt_map_pe_batch.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, ci, vp, vp, vp, vp, vp, vp]
     L.walt_pe_workspace_bytes.argtypes = [u32, u32, u32]
     L.walt_pe_workspace_bytes.restype = c.c_size_t
@@ -229,6 +233,11 @@ def pack_reads(seqs):
         offsets[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
     bases = np.frombuffer(b"".join(bs), dtype=np.uint8).copy() if bs else np.zeros(0, dtype=np.uint8)
     return bases, offsets
+
+
+def se_rpbat_workspace_bytes(n, max_read_len):
+    """Bytes of the workspace Index.map_se_rpbat_batch_device needs (walt_se_rpbat_workspace_bytes)."""
+    return lib().walt_se_rpbat_workspace_bytes(int(n), int(max_read_len))
 
 
 COMM_ID_BYTES = 128
@@ -441,6 +450,28 @@ class Index:
         self._ck(self._L.walt_map_se_batch_device(self._h, d_bases, d_offsets, int(n), int(max_read_len),
                                               int(bool(ag_wildcard)), int(max_mismatches), int(b), d_out, d_stats,
                                               d_workspace, int(workspace_bytes), stream))
+
+    # -- single-end random PBAT: every read under both conversions (include/walt_amd.h states the rules) ----------
+    def map_se_rpbat_batch(self, bases, offsets, max_mismatches=6, b=5000):
+        """Host-buffer form.  Returns (best_match[n], conv uint8[n] of ord('T') / ord('A'), stats); the index must
+        hold all four strands."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        out = np.zeros(n, dtype=best_match_dtype)
+        conv = np.zeros(n, dtype=np.uint8)
+        stats = np.zeros(1, dtype=batch_stats_dtype)
+        self._ck(self._L.walt_map_se_rpbat_batch(self._h, _ptr(bases), _ptr(offsets), n, int(max_mismatches), int(b),
+                                             _ptr(out), _ptr(conv), _ptr(stats)))
+        return out, conv, stats[0]
+
+    def map_se_rpbat_batch_device(self, d_bases, d_offsets, n, max_read_len, d_out, d_conv, d_stats, d_workspace,
+                                  workspace_bytes, stream=0, max_mismatches=6, b=5000):
+        """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); workspace_bytes = what
+        d_workspace holds (at least the module's se_rpbat_workspace_bytes(n, max_read_len))."""
+        self._ck(self._L.walt_map_se_rpbat_batch_device(self._h, d_bases, d_offsets, int(n), int(max_read_len),
+                                                    int(max_mismatches), int(b), d_out, d_conv, d_stats, d_workspace,
+                                                    int(workspace_bytes), stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
     def set_option(self, name, value):

@@ -48,6 +48,7 @@ static void check(int rc) { if (rc != WALT_OK) die(walt_last_error()); }
 struct Options {
   string index_file, se_csv, pe1_csv, pe2_csv, out_csv, adaptor;
   bool sam = false, ambiguous = false, unmapped = false, ag = false, verbose = false, pbat = false;
+  bool rpbat = false;  // -R: single-end random PBAT, every read under both conversions (walt_map_se_rpbat_batch)
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -83,6 +84,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "C", "clip")) o.adaptor = val();
     else if (is_opt(a, "A", "ag-wild")) o.ag = true;
     else if (is_opt(a, "P", "pbat")) o.pbat = true;  // README.md:64,100-104; no code in the reference snapshot
+    else if (is_opt(a, "R", "random-pbat")) o.rpbat = true;  // extension: reads of either conversion (abismal's -R)
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -103,6 +105,9 @@ static Options parse(int argc, const char** argv) {
   }
   if (o.index_file.empty() || o.out_csv.empty()) die("options -i and -o are required");
   if (o.devices.empty()) o.devices.push_back(0);
+  if (o.rpbat && o.ag) die("-R (random PBAT) maps every read under both conversions: it cannot be combined with -A");
+  if (o.rpbat && o.pbat) die("-R (random PBAT) cannot be combined with -P");
+  if (o.rpbat && (!o.pe1_csv.empty() || !o.pe2_csv.empty())) die("-R (random PBAT) is single-end only: it cannot be combined with -1 / -2");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -232,8 +237,9 @@ static void put_seq_qual(Sink& f, View seq, View score, bool flip) {
   if (flip) { f.revcomp(seq); f.ch('\t'); f.rev(score); } else { f.put(seq); f.ch('\t'); f.put(score); }
 }
 // OutputSingleSAM, mapping.cpp:382-419
+// tag: appended to the main and -a lines (-R: "\tCV:A:T" / "\tCV:A:A", the conversion of the record), or null
 static void out_single_sam(const walt_best_match& bm, View name, View seq, View score, const GenomeInfo& g,
-                           bool out_amb, bool out_unm, Sink& f) {
+                           bool out_amb, bool out_unm, Sink& f, const char* tag = nullptr) {
   uint32_t chr = chrom_id(g, bm.genome_pos);
   uint32_t start = bm.genome_pos - g.start[chr];
   if (bm.strand == '-') start = g.length[chr] - start - seq.len;
@@ -247,7 +253,9 @@ static void out_single_sam(const walt_best_match& bm, View name, View seq, View 
     f.put(name); f.ch('\t'); f.i32(flag); f.ch('\t'); f.put(g.name[chr]); f.ch('\t'); f.u32(start + 1);
     f.lit("\t255\t"); f.u32(seq.len); f.lit("M\t*\t0\t0\t");
     put_seq_qual(f, seq, score, flip);
-    f.lit("\tNM:i:"); f.u32(bm.mismatch); f.ch('\n');
+    f.lit("\tNM:i:"); f.u32(bm.mismatch);
+    if (tag) f.lit(tag);
+    f.ch('\n');
   }
 }
 
@@ -400,7 +408,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     rd.load(o.batch_size, o.adaptor, bt[0]);
   });
   DeviceSet dev;
-  dev.open(o, o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT);
+  dev.open(o, o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   OutFile fout;
@@ -412,6 +420,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.sam) { string h = sam_head(g); fout.write(h.data(), h.size()); }
   walt_best_match* res = nullptr;
   size_t res_cap = 0;
+  vector<uint8_t> conv;  // -R: the conversion of every record ('T' / 'A')
   vector<Sink> sinks((size_t)T * kSinks);
   vector<SeCounts> acc(T);
   // Only the ingest runs ahead.  Storing a batch's lines from a helper thread while the next batch is formatted was
@@ -442,9 +451,11 @@ static void process_se(const Options& o, const string& reads_file, const string&
     }
     t0 = now_s();
     vector<uint64_t> short_of(dev.size(), 0);
+    if (o.rpbat && conv.size() < n) conv.resize(n);
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
-      const int rc = walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
+      const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
+                             : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
       short_of[d] = bs.too_short;
       return rc;
     });
@@ -462,9 +473,12 @@ static void process_se(const Options& o, const string& reads_file, const string&
       s[kMain].grow((b.offsets[hi] - b.offsets[lo]) * 2 + (size_t)(hi - lo) * 96);
       for (uint32_t j = lo; j < hi; ++j) {
         c.update(res[j].times);
-        if (!o.sam) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, o.ag, side.out_amb, side.out_unm,
+        // -R: a record of the G->A conversion is written as a -A run writes it (MR), or tagged (SAM)
+        const bool ag = o.rpbat ? conv[j] == 'A' : o.ag;
+        if (!o.sam) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
                                        s[kMain], s[kAmb1], s[kUnm1]);
-        else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain]);
+        else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain],
+                            o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr);
       }
       acc[t] = c;
     }
@@ -797,7 +811,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

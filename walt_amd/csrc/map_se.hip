@@ -854,7 +854,9 @@ __device__ __forceinline__ void flush_counters(const MapCounters& ctr, uint32_t 
   block_flush_stats(shortv, ctr.probes, ctr.verified, ctr.big, shards);
 }
 
-// folds the shards into walt_batch_stats (accumulating) and clears them
+// folds the shards into walt_batch_stats (accumulating) and clears them; counters below FIRST are cleared but not
+// added (the random-PBAT call's second pass: its too_short, counter 0, is the first pass's again)
+template <uint32_t FIRST = 0>
 static __global__ void k_reduce_stats(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
   const uint32_t t = threadIdx.x;  // one thread per shard
   unsigned long long v[4];
@@ -865,7 +867,7 @@ static __global__ void k_reduce_stats(unsigned long long* __restrict__ shards, u
   __shared__ unsigned long long red[4][kStatShards];
   for (int i = 0; i < 4; ++i) red[i][t] = v[i];
   __syncthreads();
-  if (t < 4) {
+  if (t >= FIRST && t < 4) {
     unsigned long long sum = 0;
     for (uint32_t k = 0; k < kStatShards; ++k) sum += red[t][k];
     if (sum) atomicAdd(&stats[t], sum);
@@ -971,7 +973,7 @@ void launch_bin_deferred(uint32_t* d_ctl, const uint32_t* d_list, uint32_t* d_so
 }
 
 void launch_reduce_stats(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream) {
-  hipLaunchKernelGGL(k_reduce_stats, dim3(1), dim3(kStatShards), 0, stream, d_shards, d_stats);
+  hipLaunchKernelGGL(k_reduce_stats<0>, dim3(1), dim3(kStatShards), 0, stream, d_shards, d_stats);
 }
 
 // pass 1: every read of the batch, one per lane (HEAVY = false); the one-kernel heavy pass over the heavy list (HEAVY = true)
@@ -2030,64 +2032,63 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
   return WALT_OK;
 }
 
-int map_se_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, uint32_t max_read_len,
-                  int ag, uint32_t max_mm, uint32_t b, void* d_out, void* d_stats, void* d_workspace,
-                  size_t workspace_bytes, hipStream_t stream) {
-  if (!idx) return fail(WALT_EINVAL, "null index");
-  const unsigned need = ag ? WALT_STRANDS_GA : WALT_STRANDS_CT;
-  if ((idx->strand_mask & need) != need)
-    return fail(WALT_EINVAL, ag ? "index opened without the _GA10/_GA11 strands" : "index opened without the _CT00/_CT01 strands");
-  if (n == 0) return WALT_OK;
-  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
-  // One single-end call at a time per index: the call's side streams and events belong to the index (include/walt_amd.h)
-  std::unique_lock<std::mutex> busy(idx->se_busy, std::try_to_lock);
-  if (!busy.owns_lock()) return fail(WALT_EINVAL, "walt_map_se_batch: another single-end call is running on this index (an index is not re-entrant)");
 #if defined(WALT_DIAG)
-  {
-    const char* ab = getenv("WALT_AMD_ABLATE");
-    g_ablate = ab ? (uint32_t)atoi(ab) : 0u;
-    if (g_ablate & ~8u) fprintf(stderr, "[walt_amd] WALT_AMD_ABLATE=%u: DIAGNOSTIC RUN, mapping results are not valid\n", g_ablate);
-    if ((getenv("WALT_AMD_STAMPS") || g_ablate) && !g_stamps) {  // the diagnostic kernels always write their stamps
-      WALT_HIP(hipMalloc(reinterpret_cast<void**>(&g_stamps), 16 * sizeof(unsigned long long)));
-      WALT_HIP(hipMemset(g_stamps, 0, 16 * sizeof(unsigned long long)));
-    }
+static int se_diag_setup() {
+  const char* ab = getenv("WALT_AMD_ABLATE");
+  g_ablate = ab ? (uint32_t)atoi(ab) : 0u;
+  if (g_ablate & ~8u) fprintf(stderr, "[walt_amd] WALT_AMD_ABLATE=%u: DIAGNOSTIC RUN, mapping results are not valid\n", g_ablate);
+  if ((getenv("WALT_AMD_STAMPS") || g_ablate) && !g_stamps) {  // the diagnostic kernels always write their stamps
+    WALT_HIP(hipMalloc(reinterpret_cast<void**>(&g_stamps), 16 * sizeof(unsigned long long)));
+    WALT_HIP(hipMemset(g_stamps, 0, 16 * sizeof(unsigned long long)));
   }
+  return WALT_OK;
+}
 #endif
-  const int nw = nw_for_len(max_read_len);
+
+// the read-length checks of a single-end call; nw: the kernel instance the batch's longest read selects
+static int se_check_len(uint32_t max_read_len, int& nw) {
+  nw = nw_for_len(max_read_len);
   if (!nw) return fail(WALT_EINVAL, "read length above 1024 is not supported (reference line limit is 1000, util.hpp:43)");
   if (max_read_len > kMaxReadLen)
     return fail(WALT_EINVAL, "reads longer than " + std::to_string(kMaxReadLen) + " bases are outside the tables of seed pattern " +
                                  std::to_string(kPat) + " (seedpattern.hpp)");
-  if (workspace_bytes < walt_se_workspace_bytes(n, max_read_len))
-    return fail(WALT_EINVAL, "walt_map_se_batch_device: the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
-                                 std::to_string(walt_se_workspace_bytes(n, max_read_len)) + " (walt_se_workspace_bytes)");
-  WALT_HIP(hipSetDevice(idx->device));
-  const uint64_t stride = se_stride(n);
-  // workspace: [64 words: read errors, deferral control] [statistic shards] [deferred list] [sorted deferred
-  // list] [heavy list] [dense 2-bit reads] [state of the staged heavy pass] [what pass 1 hands over]
-  uint32_t* err = reinterpret_cast<uint32_t*>(d_workspace);
-  unsigned long long* shards = reinterpret_cast<unsigned long long*>(err + 64);
-  uint32_t* defer_count = err + 32;  // control block: [0] count, [8..15] bin counts, [16..23] bin cursors
-  uint32_t* defer_list = err + 64 + kStatShardBytes / 4;
-  uint32_t* codes2 = defer_list + 3 * stride;  // deferred list, its sorted copy, heavy list
-  // state of the staged heavy pass behind the dense reads, 16-byte aligned
-  uint32_t* heavy_area = reinterpret_cast<uint32_t*>(
-      align_up(reinterpret_cast<uint64_t>(codes2 + codes2_words((uint64_t)n * max_read_len)), 16));
-  uint4* carry_area = reinterpret_cast<uint4*>(align_up(reinterpret_cast<uint64_t>(heavy_area) + se_heavy_bytes(n, nw), 16));
-  WALT_HIP(hipMemsetAsync(err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
-  WALT_HIP(hipMemsetAsync(heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
-  const uint8_t* bases = reinterpret_cast<const uint8_t*>(d_bases);
-  const uint64_t* offsets = reinterpret_cast<const uint64_t*>(d_offsets);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
-  IndexView view = idx->view;  // this launch's copy: the limits lane_load_read enforces
-  view.batch_max_len = max_read_len;
-  view.batch_cap_bytes = (uint64_t)n * max_read_len;
-  launch_ascii_to_2bit(bases, offsets, n, codes2, view.batch_cap_bytes, err, stream);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
-  BestMatch* out = reinterpret_cast<BestMatch*>(d_out);
-  const uint32_t sb = ag ? 2u : 0u;
+  return WALT_OK;
+}
+
+// workspace of a single-end call: [64 words: read errors, deferral control] [statistic shards] [deferred list] [sorted
+// deferred list] [heavy list] [dense 2-bit reads] [state of the staged heavy pass] [what pass 1 hands over]
+struct SeWorkspace {
+  uint32_t* err;                // [0] non-ACGT words, [1] over-long reads, [2] dropped work items
+  unsigned long long* shards;   // statistic shards
+  uint32_t* defer_count;        // control block: [0] count, [8..15] bin counts, [16..23] bin cursors, [24] heavy count
+  uint32_t* defer_list;
+  uint32_t* codes2;             // deferred list, its sorted copy, heavy list, then the dense reads
+  uint32_t* heavy_area;         // state of the staged heavy pass behind the dense reads, 16-byte aligned
+  uint4* carry_area;
+  uint64_t stride;
+  uint64_t end;                 // first byte behind the layout (walt_se_workspace_bytes bytes from the start at most)
+};
+static SeWorkspace se_workspace(void* d_workspace, uint32_t n, uint32_t max_read_len, int nw) {
+  SeWorkspace w;
+  w.stride = se_stride(n);
+  w.err = reinterpret_cast<uint32_t*>(d_workspace);
+  w.shards = reinterpret_cast<unsigned long long*>(w.err + 64);
+  w.defer_count = w.err + 32;
+  w.defer_list = w.err + 64 + kStatShardBytes / 4;
+  w.codes2 = w.defer_list + 3 * w.stride;
+  w.heavy_area = reinterpret_cast<uint32_t*>(
+      align_up(reinterpret_cast<uint64_t>(w.codes2 + codes2_words((uint64_t)n * max_read_len)), 16));
+  w.carry_area = reinterpret_cast<uint4*>(align_up(reinterpret_cast<uint64_t>(w.heavy_area) + se_heavy_bytes(n, nw), 16));
+  w.end = reinterpret_cast<uint64_t>(w.carry_area) + se_carry_bytes(n);
+  return w;
+}
+
+// one conversion's mapping (both strand passes) of the packed reads in w.codes2 into out; sb: strand base (0: C->T
+// strands _CT00/_CT01, 2: G->A strands _GA10/_GA11)
+static int se_map_pass(walt_index* idx, const IndexView& view, const SeWorkspace& w, const uint64_t* offsets, uint32_t n,
+                       int nw, uint32_t sb, uint32_t max_mm, uint32_t b, BestMatch* out, hipStream_t stream) {
   int rc;
-#define WALT_SE_CASE(NWV) rc = launch_map_se<NWV>(idx, view, codes2, offsets, err, n, sb, max_mm, b, out, shards, defer_count, defer_list, stride, heavy_area, carry_area, stream)
+#define WALT_SE_CASE(NWV) rc = launch_map_se<NWV>(idx, view, w.codes2, offsets, w.err, n, sb, max_mm, b, out, w.shards, w.defer_count, w.defer_list, w.stride, w.heavy_area, w.carry_area, stream)
 #if defined(WALT_ONLY_NW)  // (development: one kernel instance, for quick resource checks -- tools/kernel_resources.sh)
   WALT_SE_CASE(WALT_ONLY_NW);
   (void)nw;
@@ -2106,13 +2107,177 @@ int map_se_device(walt_index* idx, const void* d_bases, const void* d_offsets, u
   }
 #endif
 #undef WALT_SE_CASE
+  return rc;
+}
+
+int map_se_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, uint32_t max_read_len,
+                  int ag, uint32_t max_mm, uint32_t b, void* d_out, void* d_stats, void* d_workspace,
+                  size_t workspace_bytes, hipStream_t stream) {
+  if (!idx) return fail(WALT_EINVAL, "null index");
+  const unsigned need = ag ? WALT_STRANDS_GA : WALT_STRANDS_CT;
+  if ((idx->strand_mask & need) != need)
+    return fail(WALT_EINVAL, ag ? "index opened without the _GA10/_GA11 strands" : "index opened without the _CT00/_CT01 strands");
+  if (n == 0) return WALT_OK;
+  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
+  // One single-end call at a time per index: the call's side streams and events belong to the index (include/walt_amd.h)
+  std::unique_lock<std::mutex> busy(idx->se_busy, std::try_to_lock);
+  if (!busy.owns_lock()) return fail(WALT_EINVAL, "walt_map_se_batch: another single-end call is running on this index (an index is not re-entrant)");
+#if defined(WALT_DIAG)
+  if (const int rc_diag = se_diag_setup()) return rc_diag;
+#endif
+  int nw;
+  if (const int rc_len = se_check_len(max_read_len, nw)) return rc_len;
+  if (workspace_bytes < walt_se_workspace_bytes(n, max_read_len))
+    return fail(WALT_EINVAL, "walt_map_se_batch_device: the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
+                                 std::to_string(walt_se_workspace_bytes(n, max_read_len)) + " (walt_se_workspace_bytes)");
+  WALT_HIP(hipSetDevice(idx->device));
+  const SeWorkspace w = se_workspace(d_workspace, n, max_read_len, nw);
+  WALT_HIP(hipMemsetAsync(w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
+  WALT_HIP(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  const uint8_t* bases = reinterpret_cast<const uint8_t*>(d_bases);
+  const uint64_t* offsets = reinterpret_cast<const uint64_t*>(d_offsets);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
+  IndexView view = idx->view;  // this launch's copy: the limits lane_load_read enforces
+  view.batch_max_len = max_read_len;
+  view.batch_cap_bytes = (uint64_t)n * max_read_len;
+  launch_ascii_to_2bit(bases, offsets, n, w.codes2, view.batch_cap_bytes, w.err, stream);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
+  BestMatch* out = reinterpret_cast<BestMatch*>(d_out);
+  const int rc = se_map_pass(idx, view, w, offsets, n, nw, ag ? 2u : 0u, max_mm, b, out, stream);
   if (rc) return rc;
-  launch_reduce_stats(shards, reinterpret_cast<unsigned long long*>(d_stats), stream);
+  launch_reduce_stats(w.shards, reinterpret_cast<unsigned long long*>(d_stats), stream);
   if (idx->profile) {
     WALT_HIP(hipEventRecord(idx->ev[2], stream));
     idx->ev_valid = true;
   }
   WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// random PBAT (walt_map_se_rpbat_batch): every read under both conversions, one record per read
+// ---------------------------------------------------------------------------
+// c = the C->T pass's record (in `out`), g = the G->A pass's (`ga`).  The first rule that applies decides the record
+// r written back to `out` and its conversion conv[r] (include/walt_amd.h):
+//   1. both unique at the same position and strand (a read without an informative C or G): c, 'T'
+//   2. g unmapped, or c mapped with fewer mismatches: c, 'T' (both unmapped: c's initial record)
+//   3. c unmapped, or g with fewer mismatches: g, 'A'
+//   4. both mapped with equal mismatches: c with times = c.times + g.times (ambiguous), 'T'
+// One read per lane, grid-stride; each record is one 16-byte load (out and ga are 16-byte aligned).
+static __global__ __launch_bounds__(kBlock) void k_se_rpbat_merge(uint4* __restrict__ out, const uint4* __restrict__ ga,
+                                                                   uint8_t* __restrict__ conv, uint32_t n) {
+  for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kBlock) {
+    const uint4 c = out[r];  // {genome_pos, times, strand, mismatch} (BestMatch)
+    const uint4 g = ga[r];
+    uint4 o = c;
+    uint8_t cv = 'T';
+    if (c.y == 1 && g.y == 1 && c.x == g.x && c.z == g.z) {
+      // rule 1
+    } else if (g.y == 0 || (c.y > 0 && c.w < g.w)) {
+      // rule 2
+    } else if (c.y == 0 || g.w < c.w) {
+      o = g;  // rule 3
+      cv = 'A';
+    } else {
+      o.y = c.y + g.y;  // rule 4
+    }
+    out[r] = o;
+    conv[r] = cv;
+  }
+}
+
+// what the call needs behind a single-conversion workspace: the G->A pass's record array
+static uint64_t se_rpbat_ga_offset(uint32_t n, uint32_t max_read_len) {
+  return align_up(walt_se_workspace_bytes(n, max_read_len), 16);
+}
+
+// locked: the caller (walt_map_se_rpbat_batch) already holds idx->se_busy
+int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, uint32_t max_read_len,
+                        uint32_t max_mm, uint32_t b, void* d_out, void* d_conv, void* d_stats, void* d_workspace,
+                        size_t workspace_bytes, hipStream_t stream, bool locked) {
+  if (!idx) return fail(WALT_EINVAL, "null index");
+  if ((idx->strand_mask & WALT_STRANDS_ALL) != WALT_STRANDS_ALL) {
+    std::string missing;
+    static const char* const names[4] = {"_CT00", "_CT01", "_GA10", "_GA11"};
+    for (int s = 0; s < 4; ++s)
+      if (!(idx->strand_mask & (1u << s))) missing += std::string(missing.empty() ? "" : ", ") + names[s];
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: the index was opened without the strands " + missing +
+                                 " (random PBAT maps under both conversions: open it with WALT_STRANDS_ALL)");
+  }
+  if (n == 0) return WALT_OK;
+  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
+  if (!d_out || !d_conv || !d_stats || !d_workspace || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_workspace) & 15))
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch_device: bad argument (null pointer, or d_out / d_workspace not 16-byte aligned)");
+  std::unique_lock<std::mutex> busy(idx->se_busy, std::defer_lock);
+  if (!locked && !busy.try_lock())
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: another single-end call is running on this index (an index is not re-entrant)");
+#if defined(WALT_DIAG)
+  if (const int rc_diag = se_diag_setup()) return rc_diag;
+#endif
+  int nw;
+  if (const int rc_len = se_check_len(max_read_len, nw)) return rc_len;
+  if (workspace_bytes < walt_se_rpbat_workspace_bytes(n, max_read_len))
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch_device: the workspace holds " + std::to_string(workspace_bytes) +
+                                 " bytes, the call needs " + std::to_string(walt_se_rpbat_workspace_bytes(n, max_read_len)) +
+                                 " (walt_se_rpbat_workspace_bytes)");
+  WALT_HIP(hipSetDevice(idx->device));
+  const SeWorkspace w = se_workspace(d_workspace, n, max_read_len, nw);
+  uint4* const ga = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(d_workspace) + se_rpbat_ga_offset(n, max_read_len));
+  WALT_HIP(hipMemsetAsync(w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
+  WALT_HIP(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  const uint64_t* offsets = reinterpret_cast<const uint64_t*>(d_offsets);
+  unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
+  IndexView view = idx->view;
+  view.batch_max_len = max_read_len;
+  view.batch_cap_bytes = (uint64_t)n * max_read_len;
+  // the reads are packed once; both passes map the same 2-bit codes (the conversion is only the strand base)
+  launch_ascii_to_2bit(reinterpret_cast<const uint8_t*>(d_bases), offsets, n, w.codes2, view.batch_cap_bytes, w.err, stream);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
+  // C->T pass into the caller's records
+  int rc = se_map_pass(idx, view, w, offsets, n, nw, 0u, max_mm, b, reinterpret_cast<BestMatch*>(d_out), stream);
+  if (rc) return rc;
+  // From here the index's side streams may still run the first pass's work on this workspace: an error return waits
+  // for them first.
+  auto unwind = [&]() {
+    if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
+    if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
+  };
+#define WALT_HIP_FORKED(expr)                                                                \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      unwind();                                                                              \
+      return walt::fail(WALT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+    }                                                                                        \
+  } while (0)
+  // Statistics: the shards are reduced once per pass.  The first pass adds all four counters (and clears the shards);
+  // the second adds probes / candidates / big_regions only, so too_short is counted once, as a single-conversion call
+  // counts it (a read is short under both conversions).
+  launch_reduce_stats(w.shards, stats, stream);
+  WALT_HIP_FORKED(hipGetLastError());
+  // The second pass starts from the state a fresh call starts from: the deferral control block (err[32..63]) and the
+  // staged pass's control words.  err[0..2] stay: they report what either pass met.
+  WALT_HIP_FORKED(hipMemsetAsync(w.err + 3, 0, 61 * sizeof(uint32_t), stream));
+  WALT_HIP_FORKED(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  // G->A pass into the workspace's record array; it starts from (0, 0, '+', max_mm) like the first, never from the
+  // first pass's result (a cap taken from it would stop the seed loop before equally good hits are found)
+  rc = se_map_pass(idx, view, w, offsets, n, nw, 2u, max_mm, b, reinterpret_cast<BestMatch*>(ga), stream);
+  if (rc) {
+    unwind();
+    return rc;
+  }
+  const unsigned gm = grid_for(n) < (unsigned)idx->n_cu * 4u ? grid_for(n) : (unsigned)idx->n_cu * 4u;
+  hipLaunchKernelGGL(k_se_rpbat_merge, dim3(gm), dim3(kBlock), 0, stream, reinterpret_cast<uint4*>(d_out), ga,
+                     reinterpret_cast<uint8_t*>(d_conv), n);
+  hipLaunchKernelGGL(k_reduce_stats<1>, dim3(1), dim3(kStatShards), 0, stream, w.shards, stats);
+  if (idx->profile) {
+    WALT_HIP_FORKED(hipEventRecord(idx->ev[2], stream));
+    idx->ev_valid = true;
+  }
+  WALT_HIP_FORKED(hipGetLastError());
+#undef WALT_HIP_FORKED
   return WALT_OK;
 }
 
@@ -2260,6 +2425,73 @@ int walt_map_se_batch(walt_index* idx, const char* bases, const uint64_t* offset
   if (!rc) rc = check_read_errors(d_ws, nullptr);
   if (!rc) {
     if ((e = hipMemcpy(out, d_out, (size_t)n * sizeof(walt_best_match), hipMemcpyDeviceToHost)) != hipSuccess)
+      rc = fail(WALT_EHIP, std::string("download failed: ") + hipGetErrorString(e));
+    walt_batch_stats st;
+    if (!rc && hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess && stats) *stats = st;
+  }
+  return rc;
+}
+
+size_t walt_se_rpbat_workspace_bytes(uint32_t n, uint32_t max_read_len) {
+  return se_rpbat_ga_offset(n, max_read_len) + (size_t)(n ? n : 1) * sizeof(walt_best_match);
+}
+
+int walt_map_se_rpbat_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                   uint32_t max_read_len, uint32_t max_mismatches, uint32_t b, void* d_out,
+                                   void* d_conv, void* d_stats, void* d_workspace, size_t workspace_bytes,
+                                   void* stream) {
+  return map_se_rpbat_device(idx, d_bases, d_offsets, n, max_read_len, max_mismatches, b, d_out, d_conv, d_stats,
+                             d_workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false);
+}
+
+int walt_map_se_rpbat_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n,
+                            uint32_t max_mismatches, uint32_t b, walt_best_match* out, uint8_t* conv,
+                            walt_batch_stats* stats) {
+  if (!idx || !offsets || (!bases && n && offsets[n] > 0) || (!out && n) || (!conv && n))
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: bad argument");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return WALT_OK;
+  // the index's single-end lock before its host-call buffers are touched: a second call is refused, it cannot
+  // reallocate them under this one
+  std::unique_lock<std::mutex> busy(idx->se_busy, std::try_to_lock);
+  if (!busy.owns_lock())
+    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: another single-end call is running on this index (an index is not re-entrant)");
+  WALT_HIP(hipSetDevice(idx->device));
+  uint32_t max_len = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
+    uint64_t l = offsets[i + 1] - offsets[i];
+    if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
+    if (l > max_len) max_len = (uint32_t)l;
+  }
+  const uint64_t nbytes = offsets[n] - offsets[0];
+  void *d_bases = nullptr, *d_off = nullptr, *d_out = nullptr, *d_conv = nullptr, *d_stats = nullptr, *d_ws = nullptr;
+  hipError_t e;
+  const uint64_t* off_src = offsets;  // relative to the first read of the batch (as walt_map_se_batch)
+  std::vector<uint64_t> rel;
+  if (offsets[0] != 0) {
+    rel.resize((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
+    off_src = rel.data();
+  }
+  const size_t ws_bytes = walt_se_rpbat_workspace_bytes(n, max_len);
+  if ((e = host_api_buffer(idx, 0, nbytes + 16, &d_bases)) != hipSuccess ||
+      (e = host_api_buffer(idx, 1, ((size_t)n + 1) * sizeof(uint64_t), &d_off)) != hipSuccess ||
+      (e = host_api_buffer(idx, 2, (size_t)n * sizeof(walt_best_match), &d_out)) != hipSuccess ||
+      (e = host_api_buffer(idx, 3, sizeof(walt_batch_stats), &d_stats)) != hipSuccess ||
+      (e = host_api_buffer(idx, 4, ws_bytes, &d_ws)) != hipSuccess ||
+      (e = host_api_buffer(idx, 5, n, &d_conv)) != hipSuccess)
+    return fail(WALT_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  if ((e = hipMemcpyAsync(d_bases, bases + offsets[0], nbytes, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_off, off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
+      (e = hipMemsetAsync(d_stats, 0, sizeof(walt_batch_stats), nullptr)) != hipSuccess)
+    return fail(WALT_EHIP, std::string("upload failed: ") + hipGetErrorString(e));
+  int rc = map_se_rpbat_device(idx, d_bases, d_off, n, max_len, max_mismatches, b, d_out, d_conv, d_stats, d_ws,
+                               ws_bytes, nullptr, true);
+  if (!rc) rc = check_read_errors(d_ws, nullptr);
+  if (!rc) {
+    if ((e = hipMemcpy(out, d_out, (size_t)n * sizeof(walt_best_match), hipMemcpyDeviceToHost)) != hipSuccess ||
+        (e = hipMemcpy(conv, d_conv, n, hipMemcpyDeviceToHost)) != hipSuccess)
       rc = fail(WALT_EHIP, std::string("download failed: ") + hipGetErrorString(e));
     walt_batch_stats st;
     if (!rc && hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess && stats) *stats = st;

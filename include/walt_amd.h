@@ -240,6 +240,52 @@ int walt_map_pe_batch_device(walt_index* idx, const void* d_bases1, const void* 
                              uint32_t top_k, int frag_range, void* d_out, void* d_stats /*[2]*/,
                              void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ---- paired-end random PBAT: each pair mapped in BOTH orientations --------
+ * For paired-end libraries in which the T-rich read of a pair may sit in either file (random-primed PBAT, most
+ * single-cell bisulfite protocols).  The reference has no such mode; its contract is defined here.  For one pair:
+ *   p = the record walt_map_pe_batch(bases1, bases2, ...) returns: orientation T (mate 1 C->T on _CT00/_CT01, mate 2
+ *       G->A on _GA10/_GA11);
+ *   q = the record the same call returns with the mates exchanged, walt_map_pe_batch(bases2, bases1, ...): orientation
+ *       A (what bin/walt -P maps), put back into user order: m1 and m2 exchanged, best_i and best_j exchanged
+ *       (frag_len and pair_mm do not depend on mate order);
+ * both with the same max_mismatches, b, top_k and frag_range.  P = p.best_times, Q = q.best_times; mp, mq = the
+ * smallest pair mismatch count of each orientation's pair search (the final min_mm of the pair merge, defined when
+ * best_times >= 1: pair_mm for a unique pair; not otherwise visible through this ABI).  The first rule that applies
+ * decides the record r and the conversions conv[2i], conv[2i+1] ('T' / 'A') of mate 1 and mate 2:
+ *   1. P == 1 && Q == 1 and both mates have the same position and strand in p and q (a pair with no informative C
+ *      or G): r = p, conv = (T, A);
+ *   2. P > 0 && (Q == 0 || mp < mq): r = p, conv = (T, A);
+ *   3. Q > 0 && (P == 0 || mq < mp): r = q in user order, conv = (A, T);
+ *   4. P > 0 && Q > 0 && mp == mq (ambiguous across the orientations): r.best_times = P + Q;
+ *   5. P == 0 && Q == 0 (no proper pair in either orientation): r.best_times = 0.
+ * Under rules 4 and 5 r.frag_len = 0, r.best_i = r.best_j = -1, r.pair_mm = 0, and each mate's record and conversion
+ * follow the single-end random-PBAT rules 1-4 above, unchanged, with c = the mate's record where it was mapped C->T
+ * and g = its record where it was mapped G->A: mate 1 c = p.m1, g = q.m1; mate 2 c = q.m2, g = p.m2.  pad_ is
+ * written as 0.
+ * Statistics (stats[2], per mate in user order): too_short is what walt_map_pe_batch reports for that mate (counted
+ * once); probes, candidates and big_regions are the sums over both orientations.
+ * The index must hold all four strands.  Every option of the index applies to both orientations, none changes r.
+ * Host form: as walt_map_pe_batch without the ranked lists; conv[2n].  It takes the index's paired-end lock before it
+ * touches anything: a second paired-end call on the same index while this one runs is refused with WALT_EINVAL.
+ * Device form: as walt_map_pe_batch_device, plus d_conv (uint8_t[2n], 2-byte aligned); d_out and d_workspace 16-byte
+ * aligned.
+ * Workspace: walt_pe_rpbat_workspace_bytes(n, L, k) = walt_pe_workspace_bytes(n, L, k) + s * R, with c the pairs of a
+ * pass (c = min(n, max(65536, min(2^23, floor(10 GiB / (24 k)))))), s the pipeline slots (2 when n > c, else 1) and
+ * R = 64 c rounded up to a multiple of 256: every slot holds orientation A's records of its pass.
+ * walt_pe_rpbat_workspace_bytes_best is what the call uses best on idx's device (as walt_pe_workspace_bytes_best);
+ * the call takes the geometry workspace_bytes has room for and refuses a smaller workspace with WALT_EINVAL. */
+size_t walt_pe_rpbat_workspace_bytes(uint32_t n, uint32_t max_read_len, uint32_t top_k);
+size_t walt_pe_rpbat_workspace_bytes_best(walt_index* idx, uint32_t n, uint32_t max_read_len, uint32_t top_k);
+int walt_map_pe_rpbat_batch(walt_index* idx, const char* bases1, const uint64_t* offsets1, const char* bases2,
+                            const uint64_t* offsets2, uint32_t n, uint32_t max_mismatches, uint32_t b,
+                            uint32_t top_k, int frag_range, walt_pair_result* out, uint8_t* conv,
+                            walt_batch_stats* stats /*[2]*/);
+int walt_map_pe_rpbat_batch_device(walt_index* idx, const void* d_bases1, const void* d_offsets1,
+                                   const void* d_bases2, const void* d_offsets2, uint32_t n,
+                                   uint32_t max_read_len, uint32_t max_mismatches, uint32_t b, uint32_t top_k,
+                                   int frag_range, void* d_out, void* d_conv, void* d_stats /*[2]*/,
+                                   void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

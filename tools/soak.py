@@ -222,6 +222,88 @@ def run_soak_rpbat(seeds, pattern=3):
         pattern, len(seeds), reads_total)
 
 
+def sample_pairs(rng, seqs, n, lengths, frag_range, refio):
+    """n bisulfite pairs of either orientation: a fragment of a random strand, mate 1 its C->T converted start, mate 2
+    the reverse complement of its converted end (T-rich mate first); the mates of about half of the pairs exchanged
+    (A-rich mate first), and a tenth of the pairs two unrelated reads."""
+    out1, out2 = [], []
+    while len(out1) < n:
+        l1, l2 = rng.choice(lengths), rng.choice(lengths)
+        _, g = seqs[rng.randrange(len(seqs))]
+        f_len = rng.randrange(max(l1, l2), max(l1, l2) + frag_range + 1)
+        if rng.random() < 0.1 or len(g) < f_len:
+            m1, m2 = sample(rng, seqs, 1, "CT", lengths, refio)[0], sample(rng, seqs, 1, "GA", lengths, refio)[0]
+        else:
+            p = rng.randrange(0, len(g) - f_len + 1)
+            f = g[p:p + f_len]
+            if rng.random() < 0.5:
+                f = refio.revcomp(f)
+            f = "".join("T" if (c == "C" and rng.random() < 0.9) else c for c in f)
+            rate = rng.choice([0.0, 0.01, 0.04])
+            m1, m2 = f[:l1], refio.revcomp(f[-l2:])
+            m1, m2 = ("".join(rng.choice("ACGT") if rng.random() < rate else c for c in m) for m in (m1, m2))
+        if rng.random() < 0.5:
+            m1, m2 = m2, m1
+        out1.append(m1)
+        out2.append(m2)
+    return out1, out2
+
+
+def run_soak_pe_rpbat(seeds, pattern=3):
+    """Paired-end random PBAT (walt_map_pe_rpbat_batch) on the genomes of `seeds`: pairs of either orientation, random
+    m, b, k and L; the GPU's records and conversions compared with the rule of include/walt_amd.h applied to the
+    oracle's two orientations (tests/test_pe_rpbat_cpu.py).  Returns the summary line, raises SoakMismatch at the first
+    difference (tests/test_gpu_pe_rpbat_soak.py)."""
+    import refio
+    import walt_amd
+    import test_pe_rpbat_cpu as rule_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 260)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    pairs_total = 0
+    rules = np.zeros(6, dtype=np.int64)
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 7727 + 3)  # a generator of its own: run_soak's draws for a seed stay as they are
+            tmp = tempfile.mkdtemp(prefix="walt_soak_pe_rpbat_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL)
+                m, b, k = rng.choice([0, 2, 6, 10]), rng.choice([2, 30, 5000]), rng.choice([2, 5, 50, 300])
+                L = rng.choice([200, 1000])
+                lengths = [lo + 2, 40, 60, 100, 100, 131, min(150, hi)]
+                s1, s2 = sample_pairs(rng, seqs, 500, lengths, L, refio)
+                try:
+                    if rng.random() < 0.3:
+                        idx.set_option("pe_chunk", 128)  # several passes: both pipeline slots
+                    got, conv, _ = idx.map_pe_rpbat_batch(*walt_amd.pack_reads(s1), *walt_amd.pack_reads(s2),
+                                                          max_mismatches=m, b=b, top_k=k, frag_range=L)
+                finally:
+                    idx.close()
+                rec, want_conv, rule, _ = rule_of.oracle_pe_rpbat(db, s1, s2, m=m, b=b, k=k, L=L)
+                try:
+                    rule_of.compare(got, conv, rec, want_conv)
+                except AssertionError as e:
+                    raise SoakMismatch("MISMATCH paired-end random PBAT seed %d m=%d b=%d k=%d L=%d: %s" % (seed, m, b, k, L, e))
+                rules += np.bincount(rule, minlength=6)
+                pairs_total += len(s1)
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    return ("soak ok: paired-end random PBAT, pattern %d, %d genomes, %d pairs identical to the rule on the oracle "
+            "(rules 1-5: %s)" % (pattern, len(seeds), pairs_total, list(rules[1:])))
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

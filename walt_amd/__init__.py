@@ -184,6 +184,13 @@ def lib(pattern=None):
     L.walt_pe_workspace_bytes_best.argtypes = [vp, u32, u32, u32]
     L.walt_pe_workspace_bytes_best.restype = c.c_size_t
     L.walt_map_pe_batch_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, ci, vp, vp, vp, c.c_size_t, vp]
+    L.walt_pe_rpbat_workspace_bytes.argtypes = [u32, u32, u32]
+    L.walt_pe_rpbat_workspace_bytes.restype = c.c_size_t
+    L.walt_pe_rpbat_workspace_bytes_best.argtypes = [vp, u32, u32, u32]
+    L.walt_pe_rpbat_workspace_bytes_best.restype = c.c_size_t
+    L.walt_map_pe_rpbat_batch.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, ci, vp, vp, vp]
+    L.walt_map_pe_rpbat_batch_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, ci, vp, vp, vp, vp,
+                                                 c.c_size_t, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -238,6 +245,11 @@ def pack_reads(seqs):
 def se_rpbat_workspace_bytes(n, max_read_len):
     """Bytes of the workspace Index.map_se_rpbat_batch_device needs (walt_se_rpbat_workspace_bytes)."""
     return lib().walt_se_rpbat_workspace_bytes(int(n), int(max_read_len))
+
+
+def pe_rpbat_workspace_bytes(n, max_read_len, top_k):
+    """Least bytes of the workspace Index.map_pe_rpbat_batch_device needs (walt_pe_rpbat_workspace_bytes)."""
+    return lib().walt_pe_rpbat_workspace_bytes(int(n), int(max_read_len), int(top_k))
 
 
 COMM_ID_BYTES = 128
@@ -521,3 +533,36 @@ class Index:
         if want_ranked:
             return out, stats, (r1, n1, r2, n2)
         return out, stats
+
+    # -- paired-end random PBAT: every pair in both orientations (include/walt_amd.h states the rules) -------------
+    def map_pe_rpbat_batch(self, bases1, offsets1, bases2, offsets2, max_mismatches=6, b=5000, top_k=50,
+                           frag_range=1000):
+        """Host-buffer form.  Returns (pair_result[n], conv uint8[n, 2] of ord('T') / ord('A') per mate, stats[2])."""
+        bases1 = np.ascontiguousarray(bases1, dtype=np.uint8)
+        bases2 = np.ascontiguousarray(bases2, dtype=np.uint8)
+        offsets1 = np.ascontiguousarray(offsets1, dtype=np.uint64)
+        offsets2 = np.ascontiguousarray(offsets2, dtype=np.uint64)
+        n = offsets1.size - 1
+        if offsets2.size - 1 != n:
+            raise ValueError("The number of reads in paired-end files should be the same.")
+        out = np.zeros(n, dtype=pair_result_dtype)
+        conv = np.zeros((n, 2), dtype=np.uint8)
+        stats = np.zeros(2, dtype=batch_stats_dtype)
+        self._ck(self._L.walt_map_pe_rpbat_batch(self._h, _ptr(bases1), _ptr(offsets1), _ptr(bases2), _ptr(offsets2),
+                                             n, int(max_mismatches), int(b), int(top_k), int(frag_range), _ptr(out),
+                                             _ptr(conv), _ptr(stats)))
+        return out, conv, stats
+
+    def map_pe_rpbat_batch_device(self, d_bases1, d_offsets1, d_bases2, d_offsets2, n, max_read_len, d_out, d_conv,
+                                  d_stats, d_workspace, workspace_bytes, stream=0, max_mismatches=6, b=5000, top_k=50,
+                                  frag_range=1000):
+        """Device-pointer form; d_conv holds 2n bytes, d_stats two walt_batch_stats; workspace_bytes = what d_workspace
+        holds (at least pe_rpbat_workspace_bytes(n, max_read_len, top_k))."""
+        self._ck(self._L.walt_map_pe_rpbat_batch_device(self._h, d_bases1, d_offsets1, d_bases2, d_offsets2, int(n),
+                                                    int(max_read_len), int(max_mismatches), int(b), int(top_k),
+                                                    int(frag_range), d_out, d_conv, d_stats, d_workspace,
+                                                    int(workspace_bytes), stream))
+
+    def pe_rpbat_workspace_bytes(self, n, max_read_len, top_k):
+        """What a random-PBAT paired-end call uses best on this index's device now (walt_pe_rpbat_workspace_bytes_best)."""
+        return self._L.walt_pe_rpbat_workspace_bytes_best(self._h, int(n), int(max_read_len), int(top_k))

@@ -1854,9 +1854,11 @@ WALT_HD void pair_finish(const Candidate* r1, int n1, const Candidate* r2, int n
     best4single(r2, n2, out.m2);
   }
 }
-WALT_HD void pair_merge(const Candidate* r1, int n1, const Candidate* r2, int n2, uint32_t len1, uint32_t len2,
-                        const uint32_t* start_index, uint32_t n_chrom, int frag_range, uint32_t max_mm,
-                        PairResult& out) {
+// returns the search's final min_mm: the smallest pair mismatch count when out.best_times >= 1 (the random-PBAT merge
+// compares the two orientations by it), else max_mm
+WALT_HD uint32_t pair_merge(const Candidate* r1, int n1, const Candidate* r2, int n2, uint32_t len1, uint32_t len2,
+                            const uint32_t* start_index, uint32_t n_chrom, int frag_range, uint32_t max_mm,
+                            PairResult& out) {
   int bi = -1, bj = -1;
   uint32_t min_mm = max_mm;
   uint64_t best_pos = 0;
@@ -1884,6 +1886,7 @@ WALT_HD void pair_merge(const Candidate* r1, int n1, const Candidate* r2, int n2
     }
   }
   pair_finish(r1, n1, r2, n2, len1, len2, start_index, n_chrom, max_mm, bi, bj, best_times, out);
+  return min_mm;
 }
 
 }  // namespace walt

@@ -49,6 +49,7 @@ struct Options {
   string index_file, se_csv, pe1_csv, pe2_csv, out_csv, adaptor;
   bool sam = false, ambiguous = false, unmapped = false, ag = false, verbose = false, pbat = false;
   bool rpbat = false;  // -R: single-end random PBAT, every read under both conversions (walt_map_se_rpbat_batch)
+  bool rpbat_pe = false;  // -RP: paired-end random PBAT, every pair in both orientations (walt_map_pe_rpbat_batch)
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -85,6 +86,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "A", "ag-wild")) o.ag = true;
     else if (is_opt(a, "P", "pbat")) o.pbat = true;  // README.md:64,100-104; no code in the reference snapshot
     else if (is_opt(a, "R", "random-pbat")) o.rpbat = true;  // extension: reads of either conversion (abismal's -R)
+    else if (is_opt(a, "RP", "random-pbat-pe")) o.rpbat_pe = true;  // extension: pairs of either orientation
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -105,9 +107,13 @@ static Options parse(int argc, const char** argv) {
   }
   if (o.index_file.empty() || o.out_csv.empty()) die("options -i and -o are required");
   if (o.devices.empty()) o.devices.push_back(0);
+  if (o.rpbat_pe && o.rpbat) die("-RP (paired-end random PBAT) cannot be combined with -R (single-end random PBAT)");
+  if (o.rpbat_pe && !o.se_csv.empty()) die("-RP (random PBAT) is paired-end only: it cannot be combined with -r (use -R)");
+  if (o.rpbat_pe && o.ag) die("-RP (random PBAT) maps every pair in both orientations: it cannot be combined with -A");
+  if (o.rpbat_pe && o.pbat) die("-RP (random PBAT) maps every pair in both orientations: it cannot be combined with -P");
   if (o.rpbat && o.ag) die("-R (random PBAT) maps every read under both conversions: it cannot be combined with -A");
   if (o.rpbat && o.pbat) die("-R (random PBAT) cannot be combined with -P");
-  if (o.rpbat && (!o.pe1_csv.empty() || !o.pe2_csv.empty())) die("-R (random PBAT) is single-end only: it cannot be combined with -1 / -2");
+  if (o.rpbat && (!o.pe1_csv.empty() || !o.pe2_csv.empty())) die("-R (random PBAT) is single-end only: it cannot be combined with -1 / -2 (use -RP)");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -584,18 +590,23 @@ static int sam_flag(bool paired_mapped, bool unmapped, bool next_unmapped, bool 
          (next_rev ? 0x20 : 0) + (first ? 0x40 : 0x80) + (secondary ? 0x100 : 0);
 }
 static void sam_mate_line(Sink& f, View name, int flag, bool mapped, const string& chrom, uint32_t pos, uint32_t read_len,
-                          const string& rnext, uint32_t pnext, int tlen, View seq, View score, bool flip, uint32_t mm) {
+                          const string& rnext, uint32_t pnext, int tlen, View seq, View score, bool flip, uint32_t mm,
+                          const char* tag) {
   f.put(name); f.ch('\t'); f.i32(flag); f.ch('\t');
   if (mapped) { f.put(chrom); f.ch('\t'); f.u32(pos); f.lit("\t255\t"); f.u32(read_len); f.lit("M\t"); }
   else { f.lit("*\t"); f.u32(pos); f.lit("\t255\t*\t"); }
   f.put(rnext); f.ch('\t'); f.u32(pnext); f.ch('\t'); f.i32(tlen); f.ch('\t');
   put_seq_qual(f, seq, score, flip);
-  f.lit("\tNM:i:"); f.u32(mm); f.ch('\n');
+  f.lit("\tNM:i:"); f.u32(mm);
+  if (tag) f.lit(tag);
+  f.ch('\n');
 }
 // OutputPairedSAM, paired.cpp:333-435
+// tag_1 / tag_2: appended to the mate's line (-RP: "\tCV:A:T" / "\tCV:A:A", the conversion of its record), or null
 static void out_paired_sam(const walt_best_match& b1, const walt_best_match& b2, const GenomeInfo& g, View name,
                            View seq1, View scr1, View seq2, View scr2, int len, int flag_1, int flag_2, bool out_amb,
-                           bool out_unm, bool second_first, Sink& fout) {
+                           bool out_unm, bool second_first, Sink& fout, const char* tag_1 = nullptr,
+                           const char* tag_2 = nullptr) {
   uint32_t c1 = chrom_id(g, b1.genome_pos), c2 = chrom_id(g, b2.genome_pos);
   uint32_t s1, s2, e1, e2;
   forward_pos(b1.genome_pos, b1.strand, c1, seq1.len, g, s1, e1);
@@ -612,15 +623,15 @@ static void out_paired_sam(const walt_best_match& b1, const walt_best_match& b2,
   }
   auto first = [&]() {
     if (b1.times == 0 && out_unm)
-      sam_mate_line(fout, name, flag_1, false, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1);
+      sam_mate_line(fout, name, flag_1, false, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1);
     else if (b1.times == 1 || (b1.times >= 2 && out_amb))
-      sam_mate_line(fout, name, flag_1, true, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1);
+      sam_mate_line(fout, name, flag_1, true, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1);
   };
   auto second = [&]() {
     if (b2.times == 0 && out_unm)
-      sam_mate_line(fout, name, flag_2, false, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2);
+      sam_mate_line(fout, name, flag_2, false, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2);
     else if (b2.times == 1 || (b2.times >= 2 && out_amb))
-      sam_mate_line(fout, name, flag_2, true, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2);
+      sam_mate_line(fout, name, flag_2, true, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2);
   };
   if (second_first) { second(); first(); } else { first(); second(); }
 }
@@ -637,8 +648,15 @@ struct PeAcc {
 // mate files exchanged (mate 2 against the C->T indexes, mate 1 against the G->A indexes), and the output is
 // then put back in the user's order: mate 1's record / line / _1 side files / mapstats block first, FLAG
 // 0x40 on mate 1 and 0x80 on mate 2, QNAME from the -1 file.
+// -RP (paired-end random PBAT): every pair is mapped in both orientations by walt_map_pe_rpbat_batch, which returns
+// one record per pair in user order and the conversion of each mate (include/walt_amd.h).  A unique pair that the
+// mate-exchanged orientation decided (rule 3, conversions (A, T)) gets the FRAG line a -P run writes; every other line
+// is written in user order, each mate's single-end line by the writer of its conversion, and SAM lines carry the
+// mate's conversion as CV:A:T / CV:A:A.  Since -P output is in user order too, rule-3 pairs are written as -P writes
+// them and the other rules as the plain run does.
 static void process_pe(const Options& o, const string& file1, const string& file2, const string& out_file, bool last_file) {
   const bool pbat = o.pbat;
+  const bool rp = o.rpbat_pe;
   const string& f1 = pbat ? file2 : file1;  // slot 0: the T-rich mate, mapped on _CT00/_CT01
   const string& f2 = pbat ? file1 : file2;  // slot 1: the A-rich mate, mapped on _GA10/_GA11
   const int name_slot = pbat ? 1 : 0;       // paired.cpp:694 prints the -1 file's name for both records
@@ -668,6 +686,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   Batch bts[2][2];  // [buffer][mate]: one pair of batches is mapped and written while the next is read
   walt_pair_result* pr = nullptr;
   size_t pr_cap = 0;
+  vector<uint8_t> conv;  // -RP: the conversion of each mate's record ('T' / 'A'), two per pair
   vector<Sink> sinks((size_t)T * kSinks);
   vector<PeAcc> acc(T);
   Prefetch pre, unlock_idle;  // (the idle buffers of the last batch: see process_se)
@@ -701,10 +720,14 @@ static void process_pe(const Options& o, const string& file1, const string& file
     t0 = now_s();
     // the best pair's two candidates come back inside walt_pair_result (m1/m2), so the ranked lists stay on the GPU
     vector<uint64_t> short1(dev.size(), 0), short2(dev.size(), 0);
+    if (rp && conv.size() < 2 * (size_t)n) conv.resize(2 * (size_t)n);
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs[2];
-      const int rc = walt_map_pe_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo, hi - lo,
-                                       o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
+      const int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
+                                                  hi - lo, o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo,
+                                                  conv.data() + 2 * (size_t)lo, bs)
+                        : walt_map_pe_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo, hi - lo,
+                                            o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
       short1[d] = bs[0].too_short;
       short2[d] = bs[1].too_short;
       return rc;
@@ -726,11 +749,15 @@ static void process_pe(const Options& o, const string& file1, const string& file
         walt_best_match bm1 = {0, 0, '+', {0, 0, 0}, o.max_mismatches}, bm2 = bm1;
         bool is_paired = false;
         int len = 0;
+        const bool ag1 = rp && conv[2 * (size_t)j] == 'A', ag2 = !rp || conv[2 * (size_t)j + 1] == 'A';
         if (p.best_times == 1) {
           a.unique_pairs++;
           walt_candidate r1 = {p.m1.genome_pos, p.m1.strand, {0, 0, 0}, p.m1.mismatch};
           walt_candidate r2 = {p.m2.genome_pos, p.m2.strand, {0, 0, 0}, p.m2.mismatch};
-          len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam, s[kMain]);
+          if (ag1)  // -RP rule 3: the fragment of the mate-exchanged orientation, written from the T-rich mate 2 as -P writes it
+            len = put_fragment(r2, r1, o.frag_range, g, name, q2, k2, q1, k1, o.sam, s[kMain]);
+          else
+            len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam, s[kMain]);
           a.frag_count[len]++;
           if (o.sam) { is_paired = true; bm1 = p.m1; bm2 = p.m2; }
         } else {
@@ -738,9 +765,9 @@ static void process_pe(const Options& o, const string& file1, const string& file
           bm1 = p.m1; bm2 = p.m2;
           a.st1.update(bm1.times);
           a.st2.update(bm2.times);
-          if (!o.sam && !pbat) {
-            out_single_results(bm1, name, q1, k1, g, false, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
-            out_single_results(bm2, name, q2, k2, g, true, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
+          if (!o.sam && !pbat) {  // (-RP: each mate by the writer of its conversion)
+            out_single_results(bm1, name, q1, k1, g, ag1, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
+            out_single_results(bm2, name, q2, k2, g, ag2, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
           } else if (!o.sam) {  // the user's mate 1 sits in slot 1
             out_single_results(bm2, name, q2, k2, g, true, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
             out_single_results(bm1, name, q1, k1, g, false, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
@@ -749,7 +776,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
         if (o.sam) {
           int fl1 = sam_flag(is_paired, bm1.times == 0, bm2.times == 0, bm1.strand == '-', bm2.strand == '-', !pbat, bm1.times >= 2);
           int fl2 = sam_flag(is_paired, bm2.times == 0, bm1.times == 0, bm2.strand == '-', bm1.strand == '-', pbat, bm2.times >= 2);
-          out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain]);
+          out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain],
+                         rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr);
         }
       }
       acc[t] = std::move(a);
@@ -811,7 +839,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

@@ -1001,6 +1001,8 @@ void launch_bin_deferred(uint32_t* d_ctl /*32 zeroed words: [0] = count*/, const
                          hipStream_t stream, const uint32_t* d_first = nullptr /*device word: first entry of the share (nullptr: 0)*/);
 
 void launch_reduce_stats(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream);
+// as launch_reduce_stats, but too_short (counter 0) is cleared without being added (a second mapping of the same reads)
+void launch_reduce_stats_no_short(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream);
 
 int check_read_errors(const void* d_workspace, hipStream_t stream);
 

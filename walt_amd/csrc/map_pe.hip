@@ -1108,6 +1108,9 @@ __global__ __launch_bounds__(kBlock) void k_pe_push(const uint32_t* __restrict__
 // thousands of iterations (repeat families fill both lists to top_k).
 constexpr uint32_t kLightCombos = 16;  // (64 until the heavy kernel worked the candidates out once per pair: 202 -> 199 ms)
 
+// MIN_MM (the random-PBAT call): a record with best_times >= 1 also carries the search's final min_mm -- the smallest
+// pair mismatch count -- in pad_[0], which k_pe_rpbat_merge reads and clears.  MIN_MM = false is the plain call.
+template <bool MIN_MM>
 __global__ void k_pe_merge(IndexView iv, const Candidate* __restrict__ ranked1, const uint32_t* __restrict__ n1,
                            const Candidate* __restrict__ ranked2, const uint32_t* __restrict__ n2,
                            const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2, uint32_t n,
@@ -1166,8 +1169,10 @@ __global__ void k_pe_merge(IndexView iv, const Candidate* __restrict__ ranked1, 
         }
       }
       pair_finish(r1, (int)a, r2, (int)b, len1, len2, starts, iv.n_chrom, max_mm, bi, bj, best_times, pr);
+      if constexpr (MIN_MM) pr.pad_[0] = best_times ? min_mm : 0u;
     } else {
-      pair_merge(r1, (int)a, r2, (int)b, len1, len2, starts, iv.n_chrom, frag_range, max_mm, pr);
+      const uint32_t min_mm = pair_merge(r1, (int)a, r2, (int)b, len1, len2, starts, iv.n_chrom, frag_range, max_mm, pr);
+      if constexpr (MIN_MM) pr.pad_[0] = pr.best_times ? min_mm : 0u;
     }
     out[r] = pr;
   }
@@ -1199,6 +1204,8 @@ __global__ void k_pe_merge(IndexView iv, const Candidate* __restrict__ ranked1, 
 // key count; if m* == min the lanes with mm == min and a key different from best_key count.
 // The reference's ordered `break` (486-487) only skips combinations with mm > min, which never
 // change the fold, so evaluating them (and rejecting on mm > min) is equivalent.
+// MIN_MM: as k_pe_merge.
+template <bool MIN_MM>
 __global__ __launch_bounds__(kBlock) void k_pe_merge_heavy(IndexView iv, const Candidate* __restrict__ ranked1,
                                                             const uint32_t* __restrict__ n1,
                                                             const Candidate* __restrict__ ranked2,
@@ -1330,6 +1337,7 @@ __global__ __launch_bounds__(kBlock) void k_pe_merge_heavy(IndexView iv, const C
         pr.m2.genome_pos = o_pos; pr.m2.times = o_times; pr.m2.strand = (char)o_strand; pr.m2.mismatch = o_mm;
         pr.best_times = best_times; pr.frag_len = 0; pr.best_i = -1; pr.best_j = -1; pr.pair_mm = 0;
         pr.pad_[0] = pr.pad_[1] = pr.pad_[2] = 0;
+        if constexpr (MIN_MM) pr.pad_[0] = best_times ? min_mm : 0u;
         if (best_times == 1) {
           const uint4 A = ca[bi], B = cb[bj];
           pr.best_i = bi; pr.best_j = bj;
@@ -1341,6 +1349,64 @@ __global__ __launch_bounds__(kBlock) void k_pe_merge_heavy(IndexView iv, const C
         out[r] = pr;
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// random PBAT (walt_map_pe_rpbat_batch): every pair in both orientations, one record per pair
+// ---------------------------------------------------------------------------
+// single-end random-PBAT rules 1-4 (include/walt_amd.h) on one mate's two records {genome_pos, times, strand,
+// mismatch}: c from its C->T mapping, g from its G->A mapping; true when g wins ('A')
+__device__ __forceinline__ bool se_rpbat_pick(const uint4 c, const uint4 g, uint4& r) {
+  r = c;
+  if (c.y == 1 && g.y == 1 && c.x == g.x && (c.z & 0xFFu) == (g.z & 0xFFu)) return false;  // rule 1
+  if (g.y == 0 || (c.y > 0 && c.w < g.w)) return false;                                 // rule 2
+  if (c.y == 0 || g.w < c.w) {                                                           // rule 3
+    r = g;
+    return true;
+  }
+  r.y = c.y + g.y;  // rule 4
+  return false;
+}
+
+// p = orientation T's record (in `out`, the caller's array), q = the mate-exchanged orientation's (`qa`, its mate 1 is
+// the user's mate 2); pad_[0] of both holds the pair search's min_mm when best_times >= 1 (k_pe_merge<true>).  The
+// first rule that applies (include/walt_amd.h) decides the record written back to `out`, in user order, with pad_ = 0,
+// and the two conversion bytes of the pair:
+//   1. both unique with the same mates (a pair without an informative C or G): p, (T, A)
+//   2. p paired, and q not or with more mismatches: p, (T, A)
+//   3. q paired, and p not or with more mismatches: q with its mates exchanged, (A, T)
+//   4. both paired with equal mismatches: best_times = P + Q, no pair; 5. neither paired: best_times = 0, no pair;
+//      under 4 and 5 each mate's record and conversion follow the single-end rule (mate 1: p.m1 / q.m1, mate 2:
+//      q.m2 / p.m2).
+// One pair per lane, grid-stride; a record is four 16-byte loads / stores (out and qa are 16-byte aligned).
+static __global__ __launch_bounds__(kBlock) void k_pe_rpbat_merge(uint4* __restrict__ out, const uint4* __restrict__ qa,
+                                                                   uint16_t* __restrict__ conv, uint32_t n) {
+  for (uint64_t r = (uint64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (uint64_t)gridDim.x * kBlock) {
+    // {m1}, {m2}, {best_times, frag_len, best_i, best_j}, {pair_mm, min_mm, 0, 0}
+    const uint4 p0 = out[4 * r], p1 = out[4 * r + 1], p2 = out[4 * r + 2], p3 = out[4 * r + 3];
+    const uint4 q0 = qa[4 * r], q1 = qa[4 * r + 1], q2 = qa[4 * r + 2], q3 = qa[4 * r + 3];
+    const uint32_t P = p2.x, Q = q2.x, mp = p3.y, mq = q3.y;
+    uint4 o0 = p0, o1 = p1, o2 = p2, o3 = make_uint4(p3.x, 0u, 0u, 0u);
+    bool a1 = false, a2 = true;  // conversion 'A' of mate 1 / mate 2
+    const bool same = P == 1 && Q == 1 && p0.x == q1.x && (p0.z & 0xFFu) == (q1.z & 0xFFu) && p1.x == q0.x &&
+                      (p1.z & 0xFFu) == (q0.z & 0xFFu);
+    if (same || (P > 0 && (Q == 0 || mp < mq))) {
+      // rules 1 and 2
+    } else if (Q > 0 && (P == 0 || mq < mp)) {
+      o0 = q1; o1 = q0;  // rule 3: user order
+      o2 = make_uint4(Q, q2.y, q2.w, q2.z);
+      o3 = make_uint4(q3.x, 0u, 0u, 0u);
+      a1 = true; a2 = false;
+    } else {
+      // rules 4 and 5
+      o2 = make_uint4(P + Q, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu);
+      o3 = make_uint4(0u, 0u, 0u, 0u);
+      a1 = se_rpbat_pick(p0, q1, o0);  // mate 1: C->T in p, G->A in q
+      a2 = se_rpbat_pick(q0, p1, o1);  // mate 2: C->T in q, G->A in p
+    }
+    out[4 * r] = o0; out[4 * r + 1] = o1; out[4 * r + 2] = o2; out[4 * r + 3] = o3;
+    conv[r] = (uint16_t)((a1 ? 'A' : 'T') | ((a2 ? 'A' : 'T') << 8));
   }
 }
 
@@ -1373,6 +1439,7 @@ struct PeWorkspace {
   uint4* items[2];
   uint4* bigs[2];
   uint32_t ccap, pool_chunks, rounds;
+  PairResult* arec;  // random PBAT: the mate-exchanged orientation's records of the pass (nullptr otherwise)
 };
 // staged reads per round, pass and mate: a sixteenth of the pass (complex reads and filter hits are a fifth of the
 // reads of an hg19-like genome: four rounds; the state of a staged read is 2.2 KB and the paired-end index leaves
@@ -1405,7 +1472,8 @@ static PeGeometry pe_geometry(uint32_t n, uint32_t top_k, const walt_options& op
   return g;
 }
 
-static PeWorkspace carve_pe(void* base, const PeGeometry& geo, int nw, uint32_t top_k, uint32_t max_read_len) {
+// rp (random PBAT): the slot also holds the mate-exchanged orientation's records of its pass, behind everything else
+static PeWorkspace carve_pe(void* base, const PeGeometry& geo, int nw, uint32_t top_k, uint32_t max_read_len, bool rp = false) {
   PeWorkspace w;
   const uint32_t chunk = geo.chunk;
   uint8_t* p = reinterpret_cast<uint8_t*>(base);
@@ -1440,6 +1508,7 @@ static PeWorkspace carve_pe(void* base, const PeGeometry& geo, int nw, uint32_t 
     w.items[m] = reinterpret_cast<uint4*>(take((uint64_t)2 * w.ccap * quads * 16));  // the queue is emptied after every seed: two probes per read
     w.bigs[m] = reinterpret_cast<uint4*>(take((uint64_t)(w.ccap / 8 + 64) * quads * 16));  // its largest-first array
   }
+  w.arec = rp ? reinterpret_cast<PairResult*>(take((uint64_t)chunk * sizeof(PairResult))) : nullptr;
   w.total_bytes = off;
   return w;
 }
@@ -1598,12 +1667,19 @@ static int pe_streams(walt_index* idx) {
   return WALT_OK;
 }
 
-// one pass (n <= pass capacity of the workspace) in pipeline slot `slot`; `stream` carries mate 1 and the merge
+// What a pass of pe_chunk is part of: the plain call, or one of the random-PBAT call's two orientations.  Both of the
+// latter emit min_mm (k_pe_merge<true>); the mate-exchanged one maps the 2-bit codes the first packed (packing is
+// conversion-free: the conversion is only the strand base), its mate m being the first orientation's mate 1 - m.
+enum PeRun { kPePlain = 0, kPeRpT = 1, kPeRpA = 2 };
+
+// one pass (n <= pass capacity of the workspace) in pipeline slot `slot`; `stream` carries mate 1 and the merge.
+// stats_of[m]: the walt_batch_stats (4 counters) that mate m's counters are added to; count_short: whether too_short
+// is among them (false: a second mapping of the same reads, whose short reads were counted already)
 static int pe_chunk(walt_index* idx, const uint8_t* d_bases1, const uint64_t* d_off1, const uint8_t* d_bases2,
                     const uint64_t* d_off2, uint32_t n, int nw, uint32_t max_read_len, uint32_t max_mm, uint32_t b,
                     uint32_t top_k,
-                    int frag_range, PairResult* d_out, unsigned long long* d_stats, const PeWorkspace& w,
-                    uint32_t* pack_err, int slot, hipStream_t stream) {
+                    int frag_range, PairResult* d_out, unsigned long long* const stats_of[2], bool count_short,
+                    const PeWorkspace& w, uint32_t* pack_err, int slot, hipStream_t stream, PeRun run = kPePlain) {
   const uint8_t* bases[2] = {d_bases1, d_bases2};
   const uint64_t* offs[2] = {d_off1, d_off2};
   // err words of the slot's workspace: [64 + 32 m ..] deferral control block of mate m, [128] heavy-pair count
@@ -1626,22 +1702,24 @@ static int pe_chunk(walt_index* idx, const uint8_t* d_bases1, const uint64_t* d_
     IndexView view = idx->view;  // this launch's copy: the limits lane_load_read enforces (the pass's share of the workspace)
     view.batch_max_len = max_read_len;
     view.batch_cap_bytes = (uint64_t)w.cap_reads * max_read_len;
-    launch_ascii_to_2bit(bases[m], offs[m], n, w.codes2[m], view.batch_cap_bytes, pack_err, stream);
+    uint32_t* const codes2 = run == kPeRpA ? w.codes2[1 - m] : w.codes2[m];
+    if (run != kPeRpA) launch_ascii_to_2bit(bases[m], offs[m], n, codes2, view.batch_cap_bytes, pack_err, stream);
     int rc;
     switch (nw) {
-      case 7: rc = launch_pe_topk<7>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 8: rc = launch_pe_topk<8>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      case 7: rc = launch_pe_topk<7>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      case 8: rc = launch_pe_topk<8>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
 #if WALT_SEEDPATTERN == 3  // patterns 5 / 7 stop at kMaxReadLen = 148 / 152 bases
-      case 10: rc = launch_pe_topk<10>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 16: rc = launch_pe_topk<16>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 32: rc = launch_pe_topk<32>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      default: rc = launch_pe_topk<64>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      case 10: rc = launch_pe_topk<10>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      case 16: rc = launch_pe_topk<16>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      case 32: rc = launch_pe_topk<32>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      default: rc = launch_pe_topk<64>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
 #else
-      default: rc = launch_pe_topk<10>(idx, view, w.codes2[m], offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
+      default: rc = launch_pe_topk<10>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
 #endif
     }
     if (rc) return rc;
-    launch_reduce_stats(w.shards[m], d_stats + 4 * m, stream);
+    if (count_short) launch_reduce_stats(w.shards[m], stats_of[m], stream);
+    else launch_reduce_stats_no_short(w.shards[m], stats_of[m], stream);
   }
   stream = user_stream;
   WALT_HIP(hipEventRecord(idx->pe_join[slot], stream_b));
@@ -1649,10 +1727,12 @@ static int pe_chunk(walt_index* idx, const uint8_t* d_bases1, const uint64_t* d_
   // both mates are mapped: mate 1's deferral list area is free and holds the heavy-pair list of the merge
   uint32_t* heavy_count = w.err + 128;
   uint32_t* heavy_list = w.defer_list[0];
-  hipLaunchKernelGGL(k_pe_merge, dim3(grid_for(n)), dim3(kBlock), 0, stream, idx->view, w.ranked[0], w.heap_n[0],
-                     w.ranked[1], w.heap_n[1], d_off1, d_off2, n, top_k, frag_range, max_mm, d_out, heavy_count,
-                     heavy_list);
-  hipLaunchKernelGGL(k_pe_merge_heavy, dim3(grid_for(n) < persistent_grid(idx) ? grid_for(n) : persistent_grid(idx)), dim3(kBlock),
+  const bool min_mm = run != kPePlain;
+  hipLaunchKernelGGL((min_mm ? k_pe_merge<true> : k_pe_merge<false>), dim3(grid_for(n)), dim3(kBlock), 0, stream, idx->view,
+                     w.ranked[0], w.heap_n[0], w.ranked[1], w.heap_n[1], d_off1, d_off2, n, top_k, frag_range, max_mm,
+                     d_out, heavy_count, heavy_list);
+  hipLaunchKernelGGL((min_mm ? k_pe_merge_heavy<true> : k_pe_merge_heavy<false>),
+                     dim3(grid_for(n) < persistent_grid(idx) ? grid_for(n) : persistent_grid(idx)), dim3(kBlock),
                      (size_t)(kBlock / 64) * 2 * top_k * sizeof(uint4), stream,
                      idx->view, w.ranked[0], w.heap_n[0], w.ranked[1], w.heap_n[1], d_off1, d_off2, top_k, frag_range,
                      max_mm, d_out, heavy_count, heavy_list);
@@ -1680,18 +1760,22 @@ using namespace walt;
 extern "C" {
 
 // bytes a call needs under geometry g: a call of several passes keeps two of them in flight (two workspaces)
-static size_t pe_bytes(const PeGeometry& g, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, bool serial) {
-  return (size_t)carve_pe(nullptr, g, nw, top_k, max_read_len).total_bytes * ((n > g.chunk && !serial) ? 2 : 1);
+// (rp: the random-PBAT call's, whose slots also hold the mate-exchanged orientation's records)
+static size_t pe_bytes(const PeGeometry& g, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, bool serial, bool rp = false) {
+  return (size_t)carve_pe(nullptr, g, nw, top_k, max_read_len, rp).total_bytes * ((n > g.chunk && !serial) ? 2 : 1);
 }
 // the geometry of a call whose workspace has `have` bytes (0: unknown -- the least): roomy when that fits (or is forced)
-static int pe_choose(const walt_options& opt, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, size_t have, PeGeometry* out) {
+static int pe_choose(const walt_options& opt, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, size_t have, PeGeometry* out,
+                     bool rp = false) {
   const PeGeometry g1 = pe_geometry(n, top_k, opt, true), g0 = pe_geometry(n, top_k, opt, false);
   const bool serial = opt.pe_serial != 0;
-  const bool roomy = opt.pe_roomy == 1 || (opt.pe_roomy < 0 && have >= pe_bytes(g1, n, nw, top_k, max_read_len, serial));
+  const bool roomy = opt.pe_roomy == 1 || (opt.pe_roomy < 0 && have >= pe_bytes(g1, n, nw, top_k, max_read_len, serial, rp));
   *out = roomy ? g1 : g0;
-  if (pe_bytes(*out, n, nw, top_k, max_read_len, serial) > have)
-    return fail(WALT_EINVAL, "walt_map_pe_batch_device: the workspace is smaller than this call needs under the index's options (" +
-                                 std::to_string(pe_bytes(*out, n, nw, top_k, max_read_len, serial)) + " bytes; walt_pe_workspace_bytes_best)");
+  if (pe_bytes(*out, n, nw, top_k, max_read_len, serial, rp) > have)
+    return fail(WALT_EINVAL, std::string(rp ? "walt_map_pe_rpbat_batch_device" : "walt_map_pe_batch_device") +
+                                 ": the workspace is smaller than this call needs under the index's options (" +
+                                 std::to_string(pe_bytes(*out, n, nw, top_k, max_read_len, serial, rp)) + " bytes; " +
+                                 (rp ? "walt_pe_rpbat_workspace_bytes_best)" : "walt_pe_workspace_bytes_best)"));
   return WALT_OK;
 }
 
@@ -1702,20 +1786,24 @@ size_t walt_pe_workspace_bytes(uint32_t n, uint32_t max_read_len, uint32_t top_k
   return pe_bytes(pe_geometry(n, top_k, defaults, false), n, nw, top_k, max_read_len, false);
 }
 
-size_t walt_pe_workspace_bytes_best(walt_index* idx, uint32_t n, uint32_t max_read_len, uint32_t top_k) {
-  if (!idx) return walt_pe_workspace_bytes(n, max_read_len, top_k);
+static size_t pe_workspace_best(walt_index* idx, uint32_t n, uint32_t max_read_len, uint32_t top_k, bool rp) {
   int nw = nw_for_len(max_read_len);
   if (!nw) nw = 64;
   const walt_options& opt = idx->opt;
   const bool serial = opt.pe_serial != 0;
-  const size_t small = pe_bytes(pe_geometry(n, top_k, opt, false), n, nw, top_k, max_read_len, serial);
-  const size_t roomy = pe_bytes(pe_geometry(n, top_k, opt, true), n, nw, top_k, max_read_len, serial);
+  const size_t small = pe_bytes(pe_geometry(n, top_k, opt, false), n, nw, top_k, max_read_len, serial, rp);
+  const size_t roomy = pe_bytes(pe_geometry(n, top_k, opt, true), n, nw, top_k, max_read_len, serial, rp);
   if (opt.pe_roomy == 0) return small;
   if (opt.pe_roomy == 1) return roomy;
   // roomy when idx's device has room for the roomy workspace and the batch's pair records beside what is allocated already
   size_t free_b = 0, total_b = 0;
   if (hipSetDevice(idx->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return small;
   return free_b >= roomy + (uint64_t)n * sizeof(PairResult) + (2ull << 30) ? roomy : small;
+}
+
+size_t walt_pe_workspace_bytes_best(walt_index* idx, uint32_t n, uint32_t max_read_len, uint32_t top_k) {
+  if (!idx) return walt_pe_workspace_bytes(n, max_read_len, top_k);
+  return pe_workspace_best(idx, n, max_read_len, top_k, false);
 }
 
 int walt_map_pe_batch_device(walt_index* idx, const void* d_bases1, const void* d_offsets1, const void* d_bases2,
@@ -1754,6 +1842,8 @@ int walt_map_pe_batch_device(walt_index* idx, const void* d_bases1, const void* 
       for (int j = 0; j < 2; ++j)
         if (idx->pe_stream[k][j]) (void)hipStreamSynchronize(idx->pe_stream[k][j]);
   };
+  unsigned long long* const stats_of[2] = {reinterpret_cast<unsigned long long*>(d_stats),
+                                           reinterpret_cast<unsigned long long*>(d_stats) + 4};
   uint32_t pass = 0;
   for (uint32_t start = 0; start < n; start += chunk, ++pass) {
     uint32_t cnt = n - start < chunk ? n - start : chunk;
@@ -1761,8 +1851,7 @@ int walt_map_pe_batch_device(walt_index* idx, const void* d_bases1, const void* 
     rc = pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases1), reinterpret_cast<const uint64_t*>(d_offsets1) + start,
                   reinterpret_cast<const uint8_t*>(d_bases2), reinterpret_cast<const uint64_t*>(d_offsets2) + start, cnt,
                   nw, max_read_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
-                  reinterpret_cast<unsigned long long*>(d_stats), w[slot], w[0].err, slot,
-                  two ? idx->pe_stream[slot][0] : stream);
+                  stats_of, true, w[slot], w[0].err, slot, two ? idx->pe_stream[slot][0] : stream);
     if (rc) { unwind(); return rc; }
   }
   if (two)
@@ -1838,12 +1927,14 @@ int walt_map_pe_batch(walt_index* idx, const char* bases1, const uint64_t* offse
   e = hipMemset(w.err, 0, 128 * sizeof(uint32_t));
   for (int m = 0; m < 2 && e == hipSuccess; ++m) e = hipMemset(w.shards[m], 0, kStatShardBytes);
   if (e != hipSuccess) return fail(WALT_EHIP, std::string("workspace setup failed: ") + hipGetErrorString(e));
+  unsigned long long* const stats_of[2] = {reinterpret_cast<unsigned long long*>(d_stats),
+                                           reinterpret_cast<unsigned long long*>(d_stats) + 4};
   for (uint32_t start = 0; start < n && !rc; start += chunk) {
     uint32_t cnt = n - start < chunk ? n - start : chunk;
     rc = pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases[0]), reinterpret_cast<const uint64_t*>(d_off[0]) + start,
                   reinterpret_cast<const uint8_t*>(d_bases[1]), reinterpret_cast<const uint64_t*>(d_off[1]) + start, cnt, nw,
                   max_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
-                  reinterpret_cast<unsigned long long*>(d_stats), w, w.err, 0, nullptr);
+                  stats_of, true, w, w.err, 0, nullptr);
     if (rc) break;
     if (hipDeviceSynchronize() != hipSuccess) { rc = fail(WALT_EHIP, "paired-end kernels failed"); break; }
     walt_candidate* rk[2] = {ranked1, ranked2};
@@ -1859,6 +1950,175 @@ int walt_map_pe_batch(walt_index* idx, const char* bases1, const uint64_t* offse
   if (!rc) rc = check_read_errors(d_ws, nullptr);
   if (!rc) {
     if (hipMemcpy(out, d_out, (size_t)n * sizeof(walt_pair_result), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(WALT_EHIP, "download failed");
+    if (!rc && stats && hipMemcpy(stats, d_stats, 2 * sizeof(walt_batch_stats), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(WALT_EHIP, "download of the statistics failed");
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// random PBAT (walt_map_pe_rpbat_batch): both orientations of every pass in its pipeline slot, then k_pe_rpbat_merge
+// ---------------------------------------------------------------------------
+size_t walt_pe_rpbat_workspace_bytes(uint32_t n, uint32_t max_read_len, uint32_t top_k) {
+  int nw = nw_for_len(max_read_len);
+  if (!nw) nw = 64;
+  const walt_options defaults;
+  return pe_bytes(pe_geometry(n, top_k, defaults, false), n, nw, top_k, max_read_len, false, true);
+}
+
+size_t walt_pe_rpbat_workspace_bytes_best(walt_index* idx, uint32_t n, uint32_t max_read_len, uint32_t top_k) {
+  if (!idx) return walt_pe_rpbat_workspace_bytes(n, max_read_len, top_k);
+  return pe_workspace_best(idx, n, max_read_len, top_k, true);
+}
+
+// locked: the caller (walt_map_pe_rpbat_batch) already holds idx->pe_busy
+static int map_pe_rpbat_device(walt_index* idx, const void* d_bases1, const void* d_offsets1, const void* d_bases2,
+                               const void* d_offsets2, uint32_t n, uint32_t max_read_len, uint32_t max_mismatches,
+                               uint32_t b, uint32_t top_k, int frag_range, void* d_out, void* d_conv, void* d_stats,
+                               void* d_workspace, size_t workspace_bytes, hipStream_t stream, bool locked) {
+  int nw = 0;
+  int rc = pe_check_args(idx, top_k, max_read_len, &nw);
+  if (rc) return rc;
+  if (n == 0) return WALT_OK;
+  if (!d_bases1 || !d_offsets1 || !d_bases2 || !d_offsets2 || !d_out || !d_conv || !d_stats || !d_workspace ||
+      (reinterpret_cast<uintptr_t>(d_out) & 15) || (reinterpret_cast<uintptr_t>(d_workspace) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_conv) & 1))
+    return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch_device: bad argument (null pointer, d_out / d_workspace not 16-byte "
+                             "aligned, or d_conv not 2-byte aligned)");
+  std::unique_lock<std::mutex> busy(idx->pe_busy, std::defer_lock);
+  if (!locked && !busy.try_lock())
+    return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: another paired-end call is running on this index (an index is not re-entrant)");
+  WALT_HIP(hipSetDevice(idx->device));
+  PeGeometry geo;
+  if ((rc = pe_choose(idx->opt, n, nw, top_k, max_read_len, workspace_bytes, &geo, true))) return rc;
+  const uint32_t chunk = geo.chunk;
+  if ((rc = pe_streams(idx))) return rc;
+  const bool serial = idx->opt.pe_serial != 0;
+  const bool two = n > chunk && !serial;
+  PeWorkspace w[2];
+  w[0] = carve_pe(d_workspace, geo, nw, top_k, max_read_len, true);
+  w[1] = two ? carve_pe(static_cast<uint8_t*>(d_workspace) + w[0].total_bytes, geo, nw, top_k, max_read_len, true) : w[0];
+  WALT_HIP(hipMemsetAsync(w[0].err, 0, 128 * sizeof(uint32_t), stream));
+  for (int k = 0; k < (two ? 2 : 1); ++k)
+    for (int m = 0; m < 2; ++m) WALT_HIP(hipMemsetAsync(w[k].shards[m], 0, kStatShardBytes, stream));
+  if (two) {
+    WALT_HIP(hipEventRecord(idx->pe_start, stream));
+    for (int k = 0; k < 2; ++k) WALT_HIP(hipStreamWaitEvent(idx->pe_stream[k][0], idx->pe_start, 0));
+  }
+  auto unwind = [&]() {
+    for (int k = 0; k < 2; ++k)
+      for (int j = 0; j < 2; ++j)
+        if (idx->pe_stream[k][j]) (void)hipStreamSynchronize(idx->pe_stream[k][j]);
+  };
+  const uint8_t* bases1 = reinterpret_cast<const uint8_t*>(d_bases1);
+  const uint8_t* bases2 = reinterpret_cast<const uint8_t*>(d_bases2);
+  const uint64_t* off1 = reinterpret_cast<const uint64_t*>(d_offsets1);
+  const uint64_t* off2 = reinterpret_cast<const uint64_t*>(d_offsets2);
+  unsigned long long* const st = reinterpret_cast<unsigned long long*>(d_stats);
+  // orientation T adds each mate's counters to its own block; orientation A's mate 1 is the user's mate 2, and its
+  // too_short is not added again (a read is short in either orientation)
+  unsigned long long* const stats_t[2] = {st, st + 4};
+  unsigned long long* const stats_a[2] = {st + 4, st};
+  const unsigned gm_cap = (unsigned)idx->n_cu * 4u;
+  uint32_t pass = 0;
+  for (uint32_t start = 0; start < n; start += chunk, ++pass) {
+    const uint32_t cnt = n - start < chunk ? n - start : chunk;
+    const int slot = two ? (int)(pass & 1) : 0;
+    hipStream_t s = two ? idx->pe_stream[slot][0] : stream;
+    PairResult* const out = reinterpret_cast<PairResult*>(d_out) + start;
+    // 1. orientation T into the caller's records; 2. orientation A (mates exchanged, the codes of 1. reused) into the
+    // slot's record array.  The second pass's kernels follow the first's merge on the slot's streams, so its ranked
+    // lists are consumed before they are overwritten.
+    rc = pe_chunk(idx, bases1, off1 + start, bases2, off2 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
+                  frag_range, out, stats_t, true, w[slot], w[0].err, slot, s, kPeRpT);
+    if (!rc)
+      rc = pe_chunk(idx, bases2, off2 + start, bases1, off1 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
+                    frag_range, w[slot].arec, stats_a, false, w[slot], w[0].err, slot, s, kPeRpA);
+    if (rc) { unwind(); return rc; }
+    // 3. the pair-level rule
+    const unsigned gm = grid_for(cnt) < gm_cap ? grid_for(cnt) : gm_cap;
+    hipLaunchKernelGGL(k_pe_rpbat_merge, dim3(gm), dim3(kBlock), 0, s, reinterpret_cast<uint4*>(out),
+                       reinterpret_cast<const uint4*>(w[slot].arec), reinterpret_cast<uint16_t*>(d_conv) + start, cnt);
+    if (hipGetLastError() != hipSuccess) { unwind(); return fail(WALT_EHIP, "k_pe_rpbat_merge launch failed"); }
+  }
+  if (two)
+    for (int k = 0; k < 2; ++k) {
+      if (hipEventRecord(idx->pe_done[k], idx->pe_stream[k][0]) != hipSuccess || hipStreamWaitEvent(stream, idx->pe_done[k], 0) != hipSuccess) {
+        unwind();
+        return fail(WALT_EHIP, "paired-end: joining the pipeline slots failed");
+      }
+    }
+  return WALT_OK;
+}
+
+int walt_map_pe_rpbat_batch_device(walt_index* idx, const void* d_bases1, const void* d_offsets1, const void* d_bases2,
+                                   const void* d_offsets2, uint32_t n, uint32_t max_read_len, uint32_t max_mismatches,
+                                   uint32_t b, uint32_t top_k, int frag_range, void* d_out, void* d_conv, void* d_stats,
+                                   void* d_workspace, size_t workspace_bytes, void* stream) {
+  return map_pe_rpbat_device(idx, d_bases1, d_offsets1, d_bases2, d_offsets2, n, max_read_len, max_mismatches, b, top_k,
+                             frag_range, d_out, d_conv, d_stats, d_workspace, workspace_bytes,
+                             reinterpret_cast<hipStream_t>(stream), false);
+}
+
+int walt_map_pe_rpbat_batch(walt_index* idx, const char* bases1, const uint64_t* offsets1, const char* bases2,
+                            const uint64_t* offsets2, uint32_t n, uint32_t max_mismatches, uint32_t b, uint32_t top_k,
+                            int frag_range, walt_pair_result* out, uint8_t* conv, walt_batch_stats* stats) {
+  if (!idx || !offsets1 || !offsets2 || (n && (!out || !conv))) return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: bad argument");
+  if (stats) memset(stats, 0, 2 * sizeof(*stats));
+  const uint64_t* offs[2] = {offsets1, offsets2};
+  const char* bases[2] = {bases1, bases2};
+  uint32_t max_len = 0;
+  for (int m = 0; m < 2; ++m) {
+    if (n && !bases[m] && offs[m][n] > offs[m][0]) return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: bad argument");
+    for (uint32_t i = 0; i < n; ++i) {
+      if (offs[m][i + 1] < offs[m][i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
+      uint64_t l = offs[m][i + 1] - offs[m][i];
+      if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
+      if (l > max_len) max_len = (uint32_t)l;
+    }
+  }
+  int nw = 0;
+  int rc = pe_check_args(idx, top_k, max_len, &nw);
+  if (rc) return rc;
+  if (n == 0) return WALT_OK;
+  // the index's paired-end lock before its host-call buffers are touched: a second call is refused, it cannot
+  // reallocate them under this one
+  std::unique_lock<std::mutex> busy(idx->pe_busy, std::try_to_lock);
+  if (!busy.owns_lock())
+    return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: another paired-end call is running on this index (an index is not re-entrant)");
+  WALT_HIP(hipSetDevice(idx->device));
+  void *d_bases[2] = {nullptr, nullptr}, *d_off[2] = {nullptr, nullptr}, *d_out = nullptr, *d_stats = nullptr,
+       *d_ws = nullptr, *d_conv = nullptr;
+  hipError_t e = hipSuccess;
+  for (int m = 0; m < 2 && e == hipSuccess; ++m) {
+    const uint64_t nbytes = offs[m][n] - offs[m][0];
+    const uint64_t* off_src = offs[m];
+    std::vector<uint64_t> rel;
+    if (offs[m][0] != 0) {  // a slice of a larger batch (several devices share one)
+      rel.resize((size_t)n + 1);
+      for (uint32_t i = 0; i <= n; ++i) rel[i] = offs[m][i] - offs[m][0];
+      off_src = rel.data();
+    }
+    if ((e = host_api_buffer(idx, m, nbytes + 16, &d_bases[m])) != hipSuccess) break;
+    if ((e = host_api_buffer(idx, 2 + m, ((size_t)n + 1) * sizeof(uint64_t), &d_off[m])) != hipSuccess) break;
+    if ((e = hipMemcpy(d_bases[m], bases[m] + offs[m][0], nbytes, hipMemcpyHostToDevice)) != hipSuccess) break;
+    e = hipMemcpy(d_off[m], off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
+  }
+  const size_t ws_bytes = walt_pe_rpbat_workspace_bytes_best(idx, n, max_len, top_k);
+  if (e == hipSuccess) e = host_api_buffer(idx, 4, (size_t)n * sizeof(walt_pair_result), &d_out);
+  if (e == hipSuccess) e = host_api_buffer(idx, 5, 2 * sizeof(walt_batch_stats), &d_stats);
+  if (e == hipSuccess) e = host_api_buffer(idx, 6, ws_bytes, &d_ws);
+  if (e == hipSuccess) e = host_api_buffer(idx, 7, 2 * (size_t)n, &d_conv);
+  if (e == hipSuccess) e = hipMemset(d_stats, 0, 2 * sizeof(walt_batch_stats));
+  if (e != hipSuccess) return fail(WALT_EHIP, std::string("paired-end upload failed: ") + hipGetErrorString(e));
+  rc = map_pe_rpbat_device(idx, d_bases[0], d_off[0], d_bases[1], d_off[1], n, max_len, max_mismatches, b, top_k,
+                           frag_range, d_out, d_conv, d_stats, d_ws, ws_bytes, nullptr, true);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(WALT_EHIP, "paired-end kernels failed");
+  if (!rc) rc = check_read_errors(d_ws, nullptr);
+  if (!rc) {
+    if (hipMemcpy(out, d_out, (size_t)n * sizeof(walt_pair_result), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(conv, d_conv, 2 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
       rc = fail(WALT_EHIP, "download failed");
     if (!rc && stats && hipMemcpy(stats, d_stats, 2 * sizeof(walt_batch_stats), hipMemcpyDeviceToHost) != hipSuccess)
       rc = fail(WALT_EHIP, "download of the statistics failed");

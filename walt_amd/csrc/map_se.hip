@@ -975,6 +975,9 @@ void launch_bin_deferred(uint32_t* d_ctl, const uint32_t* d_list, uint32_t* d_so
 void launch_reduce_stats(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream) {
   hipLaunchKernelGGL(k_reduce_stats<0>, dim3(1), dim3(kStatShards), 0, stream, d_shards, d_stats);
 }
+void launch_reduce_stats_no_short(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream) {
+  hipLaunchKernelGGL(k_reduce_stats<1>, dim3(1), dim3(kStatShards), 0, stream, d_shards, d_stats);
+}
 
 // pass 1: every read of the batch, one per lane (HEAVY = false); the one-kernel heavy pass over the heavy list (HEAVY = true)
 template <int NW, bool DIAG, bool HEAVY>

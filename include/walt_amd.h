@@ -37,6 +37,9 @@ extern "C" {
 #define WALT_STRANDS_CT 3u   /* single-end default (mapping.cpp:443-445) */
 #define WALT_STRANDS_GA 12u  /* single-end -A (mapping.cpp:446-449) */
 #define WALT_STRANDS_ALL 15u /* paired-end (paired.cpp:589-593) */
+/* also build the unconverted reference for the methylation calls (below): the genome sections of the strand files
+ * the mask does not load are read too (not their hash tables).  Without this bit walt_index_open is unchanged. */
+#define WALT_WITH_REFERENCE 16u
 
 /* BestMatch, mapping.hpp:39-52: 16 bytes, strand char at offset 8. */
 typedef struct {
@@ -285,6 +288,70 @@ int walt_map_pe_rpbat_batch_device(walt_index* idx, const void* d_bases1, const 
                                    uint32_t max_read_len, uint32_t max_mismatches, uint32_t b, uint32_t top_k,
                                    int frag_range, void* d_out, void* d_conv, void* d_stats /*[2]*/,
                                    void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- methylation calls: the methylation state of every cytosine position a mapped read covers -----------------
+ * The reference has no such mode (its users run a second program over the mapped records); the contract is defined
+ * here.  The alphabet is Bismark's XM one.
+ *
+ * Reference bases.  The index holds only converted genomes (makedb.cpp:67-73, reference.cpp:148-162), so the
+ * unconverted base is recovered from a pair of strand files: for strand '+', R[p] = 'C' where _GA10's genome byte at
+ * p is 'C', else _CT00's byte at p; for strand '-', R'[p] is the same from _GA11 and _CT01.  Both are indexed by
+ * genome_pos as the records use it (the '-' genomes are reverse-complemented chromosome by chromosome, so a '-'
+ * record's read lies on R' left to right).  For an N-free FASTA R is the FASTA.  Where the FASTA had N, each strand
+ * file holds its own fill and R is whatever this rule makes of them; nothing detects that.
+ * The two arrays are packed, 2 bits per base (2 x genome_len / 4 bytes plus a little slack), and exist only when asked
+ * for: walt_index_open with WALT_WITH_REFERENCE, or walt_index_enable_reference on an index that holds all four
+ * strands (WALT_STRANDS_ALL, walt_index_from_host / walt_index_build_device with four strands): one pass over the
+ * packed genomes it has resident.  WALT_EINVAL naming the missing strands otherwise; a second call changes nothing.
+ * walt_index_device_bytes includes the arrays once they exist.
+ *
+ * Per read.  Inputs: the sanitised bases (only ACGT) and offsets as given to the mapping call, the read's record, its
+ * conversion ('T': mapped C->T, 'A': mapped G->A, as the random-PBAT calls report it in conv) and an optional
+ * call_len (bases from call_len on get no call: an adaptor clipped by the caller).  With p = genome_pos, G = R or R'
+ * by the record's strand and [lo, hi) the chromosome that holds p, read position i < min(length, call_len) with
+ * q = p + i < hi gets a call
+ *   conversion 'T': when G[q] == 'C' and the read base is C (methylated) or T (unmethylated); context bases
+ *                   n1 = G[q+1], n2 = G[q+2], context key 'G';
+ *   conversion 'A': when G[q] == 'G' and the read base is G (methylated) or A (unmethylated); context bases
+ *                   n1 = G[q-1], n2 = G[q-2], context key 'C'.
+ * Context, first rule that applies: n1 outside [lo, hi): unknown (u / U); n1 == key: CpG (z / Z); n2 outside the
+ * chromosome: unknown; n2 == key: CHG (x / X); else CHH (h / H).  Upper case = methylated.  Every other position
+ * is '.' (not a cytosine position, a mismatch, beyond call_len, beyond the chromosome).  A record with times == 0
+ * gets all '.' and zero counts, and so does one whose genome_pos lies outside the genome, whose conversion is
+ * neither 'T' nor 'A', or whose read is longer than 1024 bases (possible only if the caller made it up; the kernel
+ * never reads beyond the arrays).  A record with times >= 2 is called at the position it holds.
+ *
+ * Outputs, each optional (NULL = not wanted): calls, one byte per base at the same offsets as bases, in read order as
+ * given; counts[n]; stats, ACCUMULATED into, not cleared, over the records with times == 1 only.
+ *
+ * records + i * record_stride is read i's walt_best_match (stride 16 for an array of them; 64 with a base of
+ * &out[0].m1 or &out[0].m2 for the mates of a walt_pair_result array).  conv + i * conv_stride is its conversion
+ * (stride 1 for walt_map_se_rpbat_batch's conv, 2 with a base of conv or conv + 1 for one mate of
+ * walt_map_pe_rpbat_batch's); conv == NULL: `conversion` for every read.  call_len: uint32_t[n] or NULL.
+ * WALT_EINVAL with a message naming the cause when the index has no reference, when a stride is smaller than its
+ * element (a record stride must also be a multiple of 4), or when a conversion is neither 'T' nor 'A' (host form: any
+ * read's; device form: `conversion` -- a device conv array cannot be checked by an asynchronous call, see above).
+ * Host form: offsets relative to offsets[0] like walt_map_se_batch; calls is written at calls[offsets[i]...].
+ * Device form: pointers are HBM addresses on idx's device, offsets[0] == 0, stream a hipStream_t or NULL;
+ * asynchronous.  d_records and d_call_len 4-byte aligned, d_counts and d_stats 8-byte aligned; d_bases and d_calls
+ * need no alignment (equal alignment modulo 16 is fastest).  No workspace.  The batch totals pass through counters
+ * that belong to the index: one methylation call with stats at a time per index. */
+typedef struct {
+  uint16_t meth[4], unmeth[4]; /* contexts in the order CpG, CHG, CHH, unknown */
+} walt_meth_counts;
+typedef struct {
+  uint64_t reads; /* records with times == 1 */
+  uint64_t meth[4], unmeth[4];
+} walt_meth_stats;
+int walt_index_enable_reference(walt_index* idx);
+int walt_index_has_reference(const walt_index* idx);
+int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                         size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                         const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats);
+int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                void* stream);
 
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment

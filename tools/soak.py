@@ -304,6 +304,71 @@ def run_soak_pe_rpbat(seeds, pattern=3):
             "(rules 1-5: %s)" % (pattern, len(seeds), pairs_total, list(rules[1:])))
 
 
+def run_soak_meth(seeds, pattern=3):
+    """Methylation calls (walt_meth_call_batch) on the genomes of `seeds`: reads of both conversions, partly
+    converted, mapped on the GPU and called; calls, per-read counts and batch totals of EVERY read compared with the
+    restatement of include/walt_amd.h's table in tests/test_gpu_meth.py, on an index opened with the strands of one
+    conversion plus the reference and on a four-strand index through walt_index_enable_reference.  Returns the summary
+    line, raises SoakMismatch at the first difference (tests/test_gpu_meth_soak.py)."""
+    import refio
+    import walt_amd
+    import test_gpu_meth as rule_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 260)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    reads_total = calls_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 15485863 + 7)  # a generator of its own: run_soak's draws for a seed stay as they are
+            tmp = tempfile.mkdtemp(prefix="walt_soak_meth_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                R = rule_of.reference_bases(db)
+                lengths = [lo + 2, 40, 47, 60, 100, 100, 131, min(150, hi), hi]
+                for conv, ag in (("CT", False), ("GA", True)):
+                    if rng.random() < 0.5:
+                        idx = walt_amd.Index.open(path, device=0, strands=(walt_amd.STRANDS_GA if ag else walt_amd.STRANDS_CT) |
+                                                  walt_amd.WITH_REFERENCE)
+                    else:
+                        idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL)
+                        idx.enable_reference()
+                    try:
+                        reads = sample(rng, seqs, 800, conv, lengths, refio)
+                        # (sample converts 90 % of the C / G: put some back, so that methylated calls are as common)
+                        frm, to = ("T", "C") if conv == "CT" else ("A", "G")
+                        reads = ["".join(to if (c == frm and rng.random() < 0.1) else c for c in r) for r in reads]
+                        call_len = None
+                        if rng.random() < 0.5:
+                            call_len = [rng.choice([len(r), len(r), len(r) // 2, 0, len(r) + 3]) for r in reads]
+                        bases, offs = walt_amd.pack_reads(reads)
+                        recs, _ = idx.map_se_batch(bases, offs, ag_wildcard=ag, max_mismatches=rng.choice([2, 6, 10]))
+                        got = idx.meth_call_batch(bases, offs, recs, "A" if ag else "T", call_len=call_len)
+                    finally:
+                        idx.close()
+                    want = rule_of.expected_batch(db, reads, recs, "A" if ag else "T", call_len, R=R)
+                    try:
+                        rule_of.assert_batch(got, reads, want, "seed %d %s" % (seed, conv))
+                    except AssertionError as e:
+                        raise SoakMismatch("MISMATCH methylation calls seed %d %s: %s" % (seed, conv, e))
+                    reads_total += len(reads)
+                    calls_total += int(want[1].sum())
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    return "soak ok: methylation calls, pattern %d, %d genomes, %d reads (%d calls) identical to the restatement" % (
+        pattern, len(seeds), reads_total, calls_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

@@ -46,6 +46,7 @@ LIB_PATH = lib_path(3)
 WALT_OK = 0
 STRAND_CT00, STRAND_CT01, STRAND_GA10, STRAND_GA11 = 1, 2, 4, 8
 STRANDS_CT, STRANDS_GA, STRANDS_ALL = 3, 12, 15
+WITH_REFERENCE = 16  # Index.open: also build the unconverted reference the methylation calls need
 
 
 def effective_cpus():
@@ -77,6 +78,10 @@ pair_result_dtype = np.dtype(
      ("best_i", "<i4"), ("best_j", "<i4"), ("pair_mm", "<u4"), ("pad", "V12")])
 batch_stats_dtype = np.dtype(
     [("too_short", "<u8"), ("probes", "<u8"), ("candidates", "<u8"), ("big_regions", "<u8")])
+meth_counts_dtype = np.dtype([("meth", "<u2", (4,)), ("unmeth", "<u2", (4,))])  # contexts: CpG, CHG, CHH, unknown
+meth_stats_dtype = np.dtype([("reads", "<u8"), ("meth", "<u8", (4,)), ("unmeth", "<u8", (4,))])
+METH_CONTEXTS = ("CpG", "CHG", "CHH", "unknown")
+assert meth_counts_dtype.itemsize == 16 and meth_stats_dtype.itemsize == 72
 assert best_match_dtype.itemsize == 16 and candidate_dtype.itemsize == 12
 assert pair_result_dtype.itemsize == 64 and batch_stats_dtype.itemsize == 32
 
@@ -191,6 +196,10 @@ def lib(pattern=None):
     L.walt_map_pe_rpbat_batch.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, ci, vp, vp, vp]
     L.walt_map_pe_rpbat_batch_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, u32, ci, vp, vp, vp, vp,
                                                  c.c_size_t, vp]
+    L.walt_index_enable_reference.argtypes = [vp]
+    L.walt_index_has_reference.argtypes = [vp]
+    L.walt_meth_call_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp]
+    L.walt_meth_call_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -484,6 +493,64 @@ class Index:
         self._ck(self._L.walt_map_se_rpbat_batch_device(self._h, d_bases, d_offsets, int(n), int(max_read_len),
                                                     int(max_mismatches), int(b), d_out, d_conv, d_stats, d_workspace,
                                                     int(workspace_bytes), stream))
+
+    # -- methylation calls (include/walt_amd.h states the rules) -------------------------------------------------
+    @property
+    def has_reference(self):
+        return bool(self._L.walt_index_has_reference(self._h))
+
+    def enable_reference(self):
+        """Builds the unconverted reference on an index that holds all four strands (walt_index_enable_reference)."""
+        self._ck(self._L.walt_index_enable_reference(self._h))
+
+    def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
+                        stats=None, want_stats=True):
+        """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
+        strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
+        read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
+        meth_counts_dtype[n], stats meth_stats_dtype scalar array); an output that is not wanted is None.  stats: an
+        existing 1-element meth_stats_dtype array to accumulate into."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        records = np.asarray(records)
+        if records.dtype != best_match_dtype or records.ndim != 1 or records.shape[0] != n:
+            raise ValueError("records: a 1-d best_match_dtype array (or view) with one element per read")
+        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
+        if rec_stride < 0:
+            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
+        conv_arr, conv_stride, conversion = None, 0, 0
+        if isinstance(conv, (str, bytes)):
+            conversion = ord(conv)
+        else:
+            conv_arr = np.asarray(conv)
+            if conv_arr.dtype != np.uint8 or conv_arr.ndim != 1 or conv_arr.shape[0] != n:
+                raise ValueError("conv: 'T', 'A' or a 1-d uint8 array with one element per read")
+            conv_stride = conv_arr.strides[0] if n > 1 else 1
+            if conv_stride <= 0:
+                conv_arr, conv_stride = np.ascontiguousarray(conv_arr), 1
+        cl = None if call_len is None else np.ascontiguousarray(call_len, dtype=np.uint32)
+        if cl is not None and cl.size != n:
+            raise ValueError("call_len: one element per read")
+        total = int(offsets[n] - offsets[0]) if n else 0
+        calls = np.zeros(total, dtype=np.uint8) if want_calls else None
+        counts = np.zeros(n, dtype=meth_counts_dtype) if want_counts else None
+        if stats is None and want_stats:
+            stats = np.zeros(1, dtype=meth_stats_dtype)
+        # calls is indexed like bases: offsets[0] bytes in front of the first read belong to neither
+        calls_ptr = None if calls is None else calls.ctypes.data - int(offsets[0]) if n else calls.ctypes.data
+        bases_ptr = bases.ctypes.data
+        self._ck(self._L.walt_meth_call_batch(self._h, bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None,
+                                              rec_stride, _ptr(conv_arr) if n else None, conv_stride, conversion,
+                                              _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats)))
+        return calls, counts, stats
+
+    def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
+                               conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0):
+        """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous."""
+        self._ck(self._L.walt_meth_call_batch_device(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride),
+                                                     d_conv, int(conv_stride), ord(conversion), d_call_len, d_calls,
+                                                     d_counts, d_stats, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
     def set_option(self, name, value):

@@ -68,6 +68,10 @@ struct walt_index {
   uint32_t window_records[4] = {0, 0, 0, 0};  // index slots with a dense candidate window (core.h StrandView::win)
   uint64_t window_eligible[4] = {0, 0, 0, 0};  // index slots in runs that qualify for one (more than the records when the budget ended first)
   unsigned strand_mask = 0;
+  // methylation calling (meth.hip): the unconverted reference, 2 bits per base, per orientation ('+', '-'); null until
+  // walt_index_open(WALT_WITH_REFERENCE) / walt_index_enable_reference builds it.  meth_shards: the batch totals' shards
+  uint32_t* ref[2] = {nullptr, nullptr};
+  unsigned long long* meth_shards = nullptr;
   // measurement hooks (walt_profile_enable / walt_profile_last)
   bool profile = false;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // before pack, before map, after map
@@ -193,6 +197,9 @@ int finish_strand_device(walt_index* idx, int strand, uint32_t* g2, const uint32
 int new_index(int device, const IndexHead& head, int dir_bits, int n_strands, walt_index** out);
 int finish_index_device(walt_index* idx);  // start_index, mask table
 int choose_dir_bits(uint64_t max_index_size, int requested, int n_strands, uint64_t device_bytes);
+// meth.hip: both packed references from the resident strands, the others' genome sections read from
+// <dbindex_path>_<strand> (null: all four strands must be resident)
+int build_reference(walt_index* idx, const char* dbindex_path);
 
 }  // namespace walt
 #endif

@@ -1033,6 +1033,7 @@ int walt_index_open(const char* dbindex_path, int device, unsigned strand_mask, 
     }
   }
   if (!rc) rc = finish_index_device(idx);
+  if (!rc && (strand_mask & WALT_WITH_REFERENCE)) rc = build_reference(idx, dbindex_path);
   if (rc) {
     std::string keep = walt_last_error();
     walt_index_close(idx);

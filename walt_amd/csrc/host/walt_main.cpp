@@ -50,6 +50,7 @@ struct Options {
   bool sam = false, ambiguous = false, unmapped = false, ag = false, verbose = false, pbat = false;
   bool rpbat = false;  // -R: single-end random PBAT, every read under both conversions (walt_map_se_rpbat_batch)
   bool rpbat_pe = false;  // -RP: paired-end random PBAT, every pair in both orientations (walt_map_pe_rpbat_batch)
+  bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -87,6 +88,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "P", "pbat")) o.pbat = true;  // README.md:64,100-104; no code in the reference snapshot
     else if (is_opt(a, "R", "random-pbat")) o.rpbat = true;  // extension: reads of either conversion (abismal's -R)
     else if (is_opt(a, "RP", "random-pbat-pe")) o.rpbat_pe = true;  // extension: pairs of either orientation
+    else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -244,8 +246,14 @@ static void put_seq_qual(Sink& f, View seq, View score, bool flip) {
 }
 // OutputSingleSAM, mapping.cpp:382-419
 // tag: appended to the main and -a lines (-R: "\tCV:A:T" / "\tCV:A:A", the conversion of the record), or null
+// xm: the read's methylation calls (-M), appended as XM:Z: in the order of SEQ; xm.p null: none
+static void put_xm(Sink& f, View xm, bool flip) {
+  if (!xm.p) return;
+  f.lit("\tXM:Z:");
+  if (flip) f.rev(xm); else f.put(xm);
+}
 static void out_single_sam(const walt_best_match& bm, View name, View seq, View score, const GenomeInfo& g,
-                           bool out_amb, bool out_unm, Sink& f, const char* tag = nullptr) {
+                           bool out_amb, bool out_unm, Sink& f, const char* tag = nullptr, View xm = View{nullptr, 0}) {
   uint32_t chr = chrom_id(g, bm.genome_pos);
   uint32_t start = bm.genome_pos - g.start[chr];
   if (bm.strand == '-') start = g.length[chr] - start - seq.len;
@@ -261,8 +269,42 @@ static void out_single_sam(const walt_best_match& bm, View name, View seq, View 
     put_seq_qual(f, seq, score, flip);
     f.lit("\tNM:i:"); f.u32(bm.mismatch);
     if (tag) f.lit(tag);
+    put_xm(f, xm, flip);
     f.ch('\n');
   }
+}
+
+// ---------------------------------------------------------------- -M: methylation calls
+// <out>.methstats: the batch totals over the records with times == 1 (walt_meth_stats), one block per mate
+static void put_meth_block(Sink& ms, const walt_meth_stats& st) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  char num[96];
+  snprintf(num, sizeof num, "reads\t%llu\n", (unsigned long long)st.reads);
+  ms.lit(num);
+  for (int c = 0; c < 4; ++c) {
+    const unsigned long long m = st.meth[c], u = st.unmeth[c];
+    if (m + u) snprintf(num, sizeof num, "%s\t%llu\t%llu\t%.6f\n", ctx[c], m, u, (double)m / (double)(m + u));
+    else snprintf(num, sizeof num, "%s\t%llu\t%llu\tNA\n", ctx[c], m, u);
+    ms.lit(num);
+  }
+}
+static void add_meth(walt_meth_stats& a, const walt_meth_stats& b) {
+  a.reads += b.reads;
+  for (int c = 0; c < 4; ++c) { a.meth[c] += b.meth[c]; a.unmeth[c] += b.unmeth[c]; }
+}
+// -C: where each read of the batch was clipped (the loader replaced the bases from there on by random ones)
+static void clip_points(const Batch& b, const string& adaptor, int T, vector<uint32_t>& out) {
+  out.resize(b.n);
+  const View ad{adaptor.data(), (uint32_t)adaptor.size()};
+#pragma omp parallel for schedule(static) num_threads(T)
+  for (uint32_t j = 0; j < b.n; ++j)
+    out[j] = hostio::adaptor_clip_point(View{b.base + (b.seq_v[j] >> 16), (uint32_t)(b.seq_v[j] & 0xFFFF)}, ad);
+}
+static void write_methstats(const string& out_file, const Sink& ms) {
+  OutFile mf;
+  if (!mf.open_append(out_file + ".methstats")) die("cannot open input file " + out_file + ".methstats");
+  mf.write(ms.p, ms.n);
+  mf.close();
 }
 
 static double g_t_main = 0;  // start of main (timeline under -v)
@@ -414,7 +456,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     rd.load(o.batch_size, o.adaptor, bt[0]);
   });
   DeviceSet dev;
-  dev.open(o, o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT);
+  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth ? WALT_WITH_REFERENCE : 0u));
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   OutFile fout;
@@ -427,6 +469,10 @@ static void process_se(const Options& o, const string& reads_file, const string&
   walt_best_match* res = nullptr;
   size_t res_cap = 0;
   vector<uint8_t> conv;  // -R: the conversion of every record ('T' / 'A')
+  vector<char> calls;    // -M -sam: the methylation calls of the batch, at the offsets of its bases
+  vector<uint32_t> clip; // -M -C: the clip point of every read
+  walt_meth_stats meth_total;
+  memset(&meth_total, 0, sizeof meth_total);
   vector<Sink> sinks((size_t)T * kSinks);
   vector<SeCounts> acc(T);
   // Only the ingest runs ahead.  Storing a batch's lines from a helper thread while the next batch is formatted was
@@ -458,14 +504,23 @@ static void process_se(const Options& o, const string& reads_file, const string&
     t0 = now_s();
     vector<uint64_t> short_of(dev.size(), 0);
     if (o.rpbat && conv.size() < n) conv.resize(n);
+    vector<walt_meth_stats> meth_of(dev.size());
+    memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
+    if (o.meth && o.sam && calls.size() < b.offsets[n]) calls.resize(b.offsets[n]);
+    if (o.meth && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
-      const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
-                             : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
+      int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
+                       : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
       short_of[d] = bs.too_short;
+      if (rc == WALT_OK && o.meth)  // on the device that mapped the share
+        rc = walt_meth_call_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
+                                  o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
+                                  o.sam ? calls.data() : nullptr, nullptr, &meth_of[d]);
       return rc;
     });
     for (uint64_t v : short_of) st.too_short += (uint32_t)v;
+    for (const walt_meth_stats& m : meth_of) add_meth(meth_total, m);
     t_map += now_s() - t0;
     if (!more) unlock_idle.start([&, cur]() { bt[cur ^ 1].release(); });
     t0 = now_s();
@@ -484,7 +539,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
         if (!o.sam) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
                                        s[kMain], s[kAmb1], s[kUnm1]);
         else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain],
-                            o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr);
+                            o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
+                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0});
       }
       acc[t] = c;
     }
@@ -516,6 +572,11 @@ static void process_se(const Options& o, const string& reads_file, const string&
     if (!mf.open_append(out_file + ".mapstats")) die("cannot open input file " + out_file + ".mapstats");
     mf.write(ms.p, ms.n);
     mf.close();
+  }
+  if (o.meth) {
+    Sink ms;
+    put_meth_block(ms, meth_total);
+    write_methstats(out_file, ms);
   }
   const double t_c0 = now_s();
   dev.close();
@@ -591,7 +652,7 @@ static int sam_flag(bool paired_mapped, bool unmapped, bool next_unmapped, bool 
 }
 static void sam_mate_line(Sink& f, View name, int flag, bool mapped, const string& chrom, uint32_t pos, uint32_t read_len,
                           const string& rnext, uint32_t pnext, int tlen, View seq, View score, bool flip, uint32_t mm,
-                          const char* tag) {
+                          const char* tag, View xm) {
   f.put(name); f.ch('\t'); f.i32(flag); f.ch('\t');
   if (mapped) { f.put(chrom); f.ch('\t'); f.u32(pos); f.lit("\t255\t"); f.u32(read_len); f.lit("M\t"); }
   else { f.lit("*\t"); f.u32(pos); f.lit("\t255\t*\t"); }
@@ -599,6 +660,7 @@ static void sam_mate_line(Sink& f, View name, int flag, bool mapped, const strin
   put_seq_qual(f, seq, score, flip);
   f.lit("\tNM:i:"); f.u32(mm);
   if (tag) f.lit(tag);
+  if (mapped) put_xm(f, xm, flip);
   f.ch('\n');
 }
 // OutputPairedSAM, paired.cpp:333-435
@@ -606,7 +668,7 @@ static void sam_mate_line(Sink& f, View name, int flag, bool mapped, const strin
 static void out_paired_sam(const walt_best_match& b1, const walt_best_match& b2, const GenomeInfo& g, View name,
                            View seq1, View scr1, View seq2, View scr2, int len, int flag_1, int flag_2, bool out_amb,
                            bool out_unm, bool second_first, Sink& fout, const char* tag_1 = nullptr,
-                           const char* tag_2 = nullptr) {
+                           const char* tag_2 = nullptr, View xm1 = View{nullptr, 0}, View xm2 = View{nullptr, 0}) {
   uint32_t c1 = chrom_id(g, b1.genome_pos), c2 = chrom_id(g, b2.genome_pos);
   uint32_t s1, s2, e1, e2;
   forward_pos(b1.genome_pos, b1.strand, c1, seq1.len, g, s1, e1);
@@ -623,15 +685,15 @@ static void out_paired_sam(const walt_best_match& b1, const walt_best_match& b2,
   }
   auto first = [&]() {
     if (b1.times == 0 && out_unm)
-      sam_mate_line(fout, name, flag_1, false, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1);
+      sam_mate_line(fout, name, flag_1, false, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1, xm1);
     else if (b1.times == 1 || (b1.times >= 2 && out_amb))
-      sam_mate_line(fout, name, flag_1, true, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1);
+      sam_mate_line(fout, name, flag_1, true, g.name[c1], s1, seq1.len, rn2, s2, len1, seq1, scr1, b1.strand == '-', mm1, tag_1, xm1);
   };
   auto second = [&]() {
     if (b2.times == 0 && out_unm)
-      sam_mate_line(fout, name, flag_2, false, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2);
+      sam_mate_line(fout, name, flag_2, false, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2, xm2);
     else if (b2.times == 1 || (b2.times >= 2 && out_amb))
-      sam_mate_line(fout, name, flag_2, true, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2);
+      sam_mate_line(fout, name, flag_2, true, g.name[c2], s2, seq2.len, rn1, s1, len2, seq2, scr2, b2.strand == '-', mm2, tag_2, xm2);
   };
   if (second_first) { second(); first(); } else { first(); second(); }
 }
@@ -664,7 +726,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   const int T_bg = std::max(1, T / 4);
   double t0 = now_s();
   DeviceSet dev;
-  dev.open(o, WALT_STRANDS_ALL);
+  dev.open(o, WALT_STRANDS_ALL | (o.meth ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   hostio::FastqReader rd[2];
@@ -687,6 +749,10 @@ static void process_pe(const Options& o, const string& file1, const string& file
   walt_pair_result* pr = nullptr;
   size_t pr_cap = 0;
   vector<uint8_t> conv;  // -RP: the conversion of each mate's record ('T' / 'A'), two per pair
+  vector<char> calls[2];     // -M -sam: the methylation calls of each slot's batch, at the offsets of its bases
+  vector<uint32_t> clip[2];  // -M -C: the clip points
+  walt_meth_stats meth_total[2];  // per slot
+  memset(meth_total, 0, sizeof meth_total);
   vector<Sink> sinks((size_t)T * kSinks);
   vector<PeAcc> acc(T);
   Prefetch pre, unlock_idle;  // (the idle buffers of the last batch: see process_se)
@@ -721,17 +787,29 @@ static void process_pe(const Options& o, const string& file1, const string& file
     // the best pair's two candidates come back inside walt_pair_result (m1/m2), so the ranked lists stay on the GPU
     vector<uint64_t> short1(dev.size(), 0), short2(dev.size(), 0);
     if (rp && conv.size() < 2 * (size_t)n) conv.resize(2 * (size_t)n);
+    vector<walt_meth_stats> meth_of(2 * dev.size());
+    memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
+    for (int k = 0; k < 2 && o.meth; ++k) {
+      if (o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
+      if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
+    }
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs[2];
-      const int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
+      int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
                                                   hi - lo, o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo,
                                                   conv.data() + 2 * (size_t)lo, bs)
                         : walt_map_pe_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo, hi - lo,
                                             o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
       short1[d] = bs[0].too_short;
       short2[d] = bs[1].too_short;
+      for (int k = 0; k < 2 && rc == WALT_OK && o.meth; ++k)  // slot 0 was mapped C->T, slot 1 G->A (-RP: as conv says)
+        rc = walt_meth_call_batch(dev.idx[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
+                                  sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
+                                  clip[k].empty() ? nullptr : clip[k].data() + lo, o.sam ? calls[k].data() : nullptr, nullptr,
+                                  &meth_of[2 * d + k]);
       return rc;
     });
+    for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
     for (size_t d = 0; d < dev.size(); ++d) { st1.too_short += (uint32_t)short1[d]; st2.too_short += (uint32_t)short2[d]; }
     t_map += now_s() - t0;
     if (!more) unlock_idle.start([&, cur]() { bts[cur ^ 1][0].release(); bts[cur ^ 1][1].release(); });
@@ -777,7 +855,9 @@ static void process_pe(const Options& o, const string& file1, const string& file
           int fl1 = sam_flag(is_paired, bm1.times == 0, bm2.times == 0, bm1.strand == '-', bm2.strand == '-', !pbat, bm1.times >= 2);
           int fl2 = sam_flag(is_paired, bm2.times == 0, bm1.times == 0, bm2.strand == '-', bm1.strand == '-', pbat, bm2.times >= 2);
           out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain],
-                         rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr);
+                         rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
+                         o.meth ? View{calls[0].data() + bt[0].offsets[j], q1.len} : View{nullptr, 0},
+                         o.meth ? View{calls[1].data() + bt[1].offsets[j], q2.len} : View{nullptr, 0});
         }
       }
       acc[t] = std::move(a);
@@ -828,6 +908,12 @@ static void process_pe(const Options& o, const string& file1, const string& file
     mf.write(ms.p, ms.n);
     mf.close();
   }
+  if (o.meth) {  // in the user's order (-P: the user's mate 1 sits in slot 1)
+    Sink ms;
+    ms.lit("mate1\n"); put_meth_block(ms, meth_total[pbat ? 1 : 0]);
+    ms.lit("mate2\n"); put_meth_block(ms, meth_total[pbat ? 0 : 1]);
+    write_methstats(out_file, ms);
+  }
   dev.close();
   if (o.verbose)
     fprintf(stderr, "[walt_amd: %d host threads, %zu GPU(s); index %.2f s, ingest not hidden behind the previous batch %.2f s, map %.2f s, "
@@ -839,7 +925,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -855,6 +941,7 @@ int main(int argc, const char** argv) {
     if (outs.size() != 1 && outs.size() != se.size() + p1.size()) die("wrong number of output files: " + o.out_csv);
     if (outs.size() == 1) outs.assign(se.size() + p1.size(), outs[0]);
     for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
+    if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");
     size_t k = 0;

@@ -1,0 +1,396 @@
+// meth.hip -- per-read methylation calling on the device (include/walt_amd.h, "methylation calls"): the unconverted
+// reference rebuilt from the converted strand genomes, and the streaming kernel that classifies every base of every
+// read of a mapped batch against it.  The reference has no such mode; the contract is the header's.
+#include <fcntl.h>
+#include <string.h>
+#include <unistd.h>
+
+#include <algorithm>
+
+#include <hip/hip_runtime.h>
+
+#include "map_common.h"
+#include "meth_core.h"
+
+namespace walt {
+
+constexpr uint32_t kRefPadWords = 16;    // zero words behind a packed reference (meth_core.h meth_ref_ext reads three words)
+constexpr uint32_t kMethShards = 64;     // shards of the batch totals (one 128-byte line each, like map_common.h kStatShards)
+constexpr uint32_t kMethShardWords = 16;
+constexpr uint32_t kMethGroup = 8;       // lanes that share a read
+constexpr uint32_t kMethTotals = 9;      // walt_meth_stats: reads, meth[4], unmeth[4]
+constexpr uint64_t kMaxReadLenAny = 1024;  // walt_max_read_len() of the widest pattern: 16-bit counts hold a read's calls
+
+// ---------------------------------------------------------------------------
+// the unconverted reference: a position is C exactly where the G->A genome says C, else what the C->T genome says
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t pack16(const uint8_t* __restrict__ bytes, uint64_t b0, uint32_t len) {
+  uint32_t v = 0;
+  if (b0 + 16 <= len) {
+    const uint4 q = *reinterpret_cast<const uint4*>(bytes + b0);  // hipMalloc base is 256-B aligned
+    const uint32_t qs[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v |= (base_code((uint8_t)(qs[i] >> (8 * k))) & 3u) << (2 * (4 * i + k));
+  } else {
+    for (uint32_t k = 0; k < 16; ++k)
+      if (b0 + k < len) v |= (base_code(bytes[b0 + k]) & 3u) << (2 * k);
+  }
+  return v;
+}
+// one packed word per thread; each side comes packed (a resident strand) or as the strand file's bytes
+__global__ void k_ref_build(const uint32_t* __restrict__ ct_g2, const uint8_t* __restrict__ ct_bytes,
+                            const uint32_t* __restrict__ ga_g2, const uint8_t* __restrict__ ga_bytes, uint32_t len,
+                            uint32_t nwords, uint32_t* __restrict__ out) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nwords) return;
+  const uint32_t ct = ct_g2 ? ct_g2[w] : pack16(ct_bytes, (uint64_t)w * 16, len);
+  const uint32_t ga = ga_g2 ? ga_g2[w] : pack16(ga_bytes, (uint64_t)w * 16, len);
+  const uint32_t c = meth_eq2(ga, 1u);
+  uint32_t v = (ct & ~(c * 3u)) | c;
+  if ((uint64_t)w * 16 + 16 > len) v &= (1u << (2 * (len - w * 16))) - 1u;  // the last word: nothing beyond the genome
+  out[w] = v;
+}
+
+static uint32_t ref_words(const walt_index* idx) { return (idx->head.genome_len + 15) / 16 + kRefPadWords; }
+
+static int ref_alloc(walt_index* idx, void** p, uint64_t bytes) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) return fail(WALT_ENOMEM, std::string("hipMalloc failed (reference): ") + hipGetErrorString(e));
+  idx->allocs.push_back(*p);
+  idx->device_bytes += bytes;
+  return WALT_OK;
+}
+
+// genome section of a strand file (offset 1, genome_len bytes; reference.cpp:302-322) -> device bytes
+static int read_genome_section(const std::string& path, uint32_t genome_len, uint8_t* d_bytes) {
+  int fd = ::open(path.c_str(), O_RDONLY);
+  if (fd < 0) return fail(WALT_EIO, "cannot open input file " + path);
+  const size_t piece = 32u << 20;
+  std::vector<char> buf(std::min<size_t>(piece, (size_t)genome_len + 1));
+  int rc = WALT_OK;
+  for (uint64_t at = 0; at < genome_len && !rc;) {
+    const size_t want = (size_t)std::min<uint64_t>(piece, genome_len - at);
+    size_t got = 0;
+    while (got < want) {
+      const ssize_t r = pread(fd, buf.data() + got, want - got, (off_t)(1 + at + got));
+      if (r <= 0) break;
+      got += (size_t)r;
+    }
+    if (got != want) rc = fail(WALT_EFORMAT, "read file error (strand index): file too short: " + path);
+    else if (hipMemcpy(d_bytes + at, buf.data(), want, hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(WALT_EHIP, "upload of a strand genome failed");
+    at += want;
+  }
+  ::close(fd);
+  return rc;
+}
+
+// Builds both packed references.  A strand the index holds is taken from its packed genome; any other is read from
+// <dbindex_path>_<strand> (its genome section alone), which needs dbindex_path.
+int build_reference(walt_index* idx, const char* dbindex_path) {
+  if (idx->ref[0]) return WALT_OK;
+  static const char* sfx[4] = {"_CT00", "_CT01", "_GA10", "_GA11"};
+  const uint32_t genome_len = idx->head.genome_len, nwords = (genome_len + 15) / 16, total = ref_words(idx);
+  if (!dbindex_path && (idx->strand_mask & 15u) != 15u) {
+    std::string missing;
+    for (int s = 0; s < 4; ++s)
+      if (!((idx->strand_mask >> s) & 1u)) missing += std::string(missing.empty() ? "" : ", ") + (sfx[s] + 1);
+    return fail(WALT_EINVAL, "walt_index_enable_reference: the reference needs all four strands resident; missing: " +
+                                 missing + " (open the index with WALT_WITH_REFERENCE instead)");
+  }
+  WALT_HIP(hipSetDevice(idx->device));
+  struct Scoped {
+    void* p = nullptr;
+    ~Scoped() { if (p) (void)hipFree(p); }
+  };
+  const size_t allocs_before = idx->allocs.size();
+  const uint64_t bytes_before = idx->device_bytes;
+  uint32_t* ref[2] = {nullptr, nullptr};
+  unsigned long long* shards = nullptr;
+  int rc = WALT_OK;
+  for (int o = 0; o < 2 && !rc; ++o) {
+    Scoped tmp[2];
+    const uint32_t* g2[2] = {nullptr, nullptr};
+    const uint8_t* bytes[2] = {nullptr, nullptr};
+    for (int c = 0; c < 2 && !rc; ++c) {  // c = 0: the C->T strand of this orientation, 1: the G->A strand
+      const int s = 2 * c + o;
+      if ((idx->strand_mask >> s) & 1u) { g2[c] = idx->view.s[s].g2; continue; }
+      if (hipMalloc(&tmp[c].p, (size_t)genome_len + 16) != hipSuccess) { rc = fail(WALT_ENOMEM, "hipMalloc failed (strand genome)"); break; }
+      rc = read_genome_section(std::string(dbindex_path) + sfx[s], genome_len, static_cast<uint8_t*>(tmp[c].p));
+      bytes[c] = static_cast<const uint8_t*>(tmp[c].p);
+    }
+    if (!rc) rc = ref_alloc(idx, reinterpret_cast<void**>(&ref[o]), (uint64_t)total * 4);
+    if (!rc && hipMemset(ref[o] + nwords, 0, (size_t)kRefPadWords * 4) != hipSuccess) rc = fail(WALT_EHIP, "hipMemset failed (reference)");
+    if (!rc && nwords) {
+      hipLaunchKernelGGL(k_ref_build, dim3(grid_for(nwords)), dim3(kBlock), 0, nullptr, g2[0], bytes[0], g2[1], bytes[1],
+                         genome_len, nwords, ref[o]);
+      if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = fail(WALT_EHIP, "building the reference failed");
+    }
+  }
+  if (!rc) rc = ref_alloc(idx, reinterpret_cast<void**>(&shards), (uint64_t)kMethShards * kMethShardWords * 8);
+  if (!rc && hipMemset(shards, 0, (size_t)kMethShards * kMethShardWords * 8) != hipSuccess) rc = fail(WALT_EHIP, "hipMemset failed (reference)");
+  if (rc) {  // the index stays as it was
+    while (idx->allocs.size() > allocs_before) { (void)hipFree(idx->allocs.back()); idx->allocs.pop_back(); }
+    idx->device_bytes = bytes_before;
+    return rc;
+  }
+  idx->ref[0] = ref[0]; idx->ref[1] = ref[1];
+  idx->meth_shards = shards;
+  return WALT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the calling kernel
+// ---------------------------------------------------------------------------
+struct MethArgs {
+  const uint32_t* ref[2];      // '+' and '-' orientation
+  uint32_t ref_last;           // last word index of a reference array
+  uint32_t genome_len;
+  const uint32_t* start_index;
+  uint32_t n_chrom;
+  const uint8_t* bases;
+  const uint64_t* offsets;
+  uint32_t n;
+  const uint8_t* records;
+  uint64_t rec_stride;
+  const uint8_t* conv;         // null: `conversion` for every read
+  uint64_t conv_stride;
+  uint32_t conversion;
+  const uint32_t* call_len;    // null: the whole read
+  uint8_t* calls;              // null: not wanted
+  unsigned long long* counts;  // null: not wanted (two words per read: walt_meth_counts)
+  unsigned long long* shards;  // null: no batch totals
+};
+
+// Eight lanes per read, one 16-base slice per lane and trip.  Slices are cut at the 16-byte boundaries of the CALLS
+// array, so a whole slice is one aligned 16-byte store and the eight lanes of a group write 128 contiguous bytes; the
+// first and last slice of a read are partial (offsets are not multiples of 16) and touch only the read's own bytes.
+__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) {
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  __shared__ unsigned long long s_red[kBlock / 64][kMethTotals];
+  const ChromTab tab = chrom_tab_of(a.n_chrom);
+  chrom_tab_stage(s_start, a.start_index, tab);
+  __syncthreads();
+  const uint32_t sub = threadIdx.x & (kMethGroup - 1);
+  const uint64_t groups = (uint64_t)gridDim.x * (kBlock / kMethGroup);
+  const uint64_t batch_bytes = a.offsets[a.n];
+  uint32_t tot[kMethTotals];  // this lane's share of the batch totals (group leaders only)
+#pragma unroll
+  for (uint32_t i = 0; i < kMethTotals; ++i) tot[i] = 0;
+  for (uint64_t r = (uint64_t)blockIdx.x * (kBlock / kMethGroup) + threadIdx.x / kMethGroup; r < a.n; r += groups) {
+    const uint64_t off = a.offsets[r], end = a.offsets[r + 1];
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(a.records + r * a.rec_stride);
+    const uint32_t pos = rec[0], times = rec[1], strand = rec[2] & 0xFFu;
+    const uint32_t cv = a.conv ? a.conv[r * a.conv_stride] : a.conversion;
+    const uint32_t len = end > off && end - off <= kMaxReadLenAny ? (uint32_t)(end - off) : 0u;
+    uint32_t limit = a.call_len ? a.call_len[r] : len;
+    limit = limit < len ? limit : len;
+    // unmapped, made up (a position outside the genome, an unknown conversion) or empty: no call anywhere
+    const bool valid = times != 0 && pos < a.genome_len && (cv == 'T' || cv == 'A');
+    const bool mapped = valid && limit != 0;
+    uint32_t c_lo = 0, c_hi = 0;
+    if (mapped) chrom_bounds(s_start, a.start_index, tab, pos, c_lo, c_hi);
+    const uint32_t ga = cv == 'A' ? 1u : 0u;
+    const uint32_t* __restrict__ ref = a.ref[strand == '-' ? 1 : 0];
+    unsigned long long meth = 0, unmeth = 0;
+    if (end > off && (mapped || a.calls)) {
+      // (bytes of calls to write: the read's own; a read longer than any pattern allows is written in pieces of 2^30)
+      const uint8_t* rb = a.bases + off;
+      uint8_t* cb = a.calls ? a.calls + off : nullptr;
+      // slice grid: by the calls array's address (by the bases' when no calls are wanted)
+      const int head = (int)((a.calls ? (uintptr_t)cb : (uintptr_t)rb) & 15u);
+      for (uint64_t done = 0; done < end - off; done += 1u << 30) {  // (one trip unless the caller made the offsets up)
+        const int total = (int)(end - off - done < (1u << 30) ? end - off - done : (1u << 30));
+        const int h = done ? 0 : head;
+        for (int i0 = -h + 16 * (int)sub; i0 < total; i0 += 16 * (int)kMethGroup) {
+          uint32_t out[4];
+          meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                          batch_bytes - off - done, out, meth, unmeth);
+          if (cb) meth_store_slice(cb + done, total, i0, out);
+        }
+      }
+    }
+    // the group's eight partial counts (16-bit fields: a read holds at most 1024 bases)
+#pragma unroll
+    for (uint32_t d = 1; d < kMethGroup; d <<= 1) {
+      meth += __shfl_xor(meth, d, kMethGroup);
+      unmeth += __shfl_xor(unmeth, d, kMethGroup);
+    }
+    if (sub == 0) {
+      if (a.counts) { a.counts[2 * r] = meth; a.counts[2 * r + 1] = unmeth; }
+      if (times == 1 && valid) {
+        tot[0] += 1;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+          tot[1 + i] += (uint32_t)(meth >> (16 * i)) & 0xFFFFu;
+          tot[5 + i] += (uint32_t)(unmeth >> (16 * i)) & 0xFFFFu;
+        }
+      }
+    }
+  }
+  if (!a.shards) return;  // (uniform)
+  // batch totals: wavefront, block, then one shard per block (one atomic per lane would serialise at a single line)
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (uint32_t i = 0; i < kMethTotals; ++i) {
+    unsigned long long v = tot[i];
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+    if (lane == 0) s_red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kMethTotals) {
+    unsigned long long t = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_red[w][threadIdx.x];
+    if (t) atomicAdd(&a.shards[(uint64_t)(blockIdx.x % kMethShards) * kMethShardWords + threadIdx.x], t);
+  }
+}
+
+// folds the shards into walt_meth_stats (accumulating) and clears them
+__global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
+  const uint32_t t = threadIdx.x;  // one thread per total
+  unsigned long long sum = 0;
+  for (uint32_t k = 0; k < kMethShards; ++k) {
+    sum += shards[(uint64_t)k * kMethShardWords + t];
+    shards[(uint64_t)k * kMethShardWords + t] = 0;
+  }
+  if (sum) atomicAdd(&stats[t], sum);
+}
+
+static int meth_args_check(const walt_index* idx, const char* who, size_t rec_stride, const void* conv, size_t conv_stride,
+                           int conversion) {
+  if (!idx) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
+  if (!idx->ref[0])
+    return fail(WALT_EINVAL, std::string(who) + ": the index holds no reference (open it with WALT_WITH_REFERENCE or "
+                                                "call walt_index_enable_reference)");
+  if (rec_stride < sizeof(walt_best_match) || rec_stride % 4)
+    return fail(WALT_EINVAL, std::string(who) + ": record stride " + std::to_string(rec_stride) +
+                                 " is smaller than a walt_best_match (16) or not a multiple of 4");
+  if (conv && conv_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": conv stride 0 is smaller than its element (1)");
+  if (!conv && conversion != 'T' && conversion != 'A')
+    return fail(WALT_EINVAL, std::string(who) + ": conversion " + std::to_string(conversion) + " is neither 'T' nor 'A'");
+  return WALT_OK;
+}
+
+static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, const void* d_records,
+                       size_t rec_stride, const void* d_conv, size_t conv_stride, int conversion, const void* d_call_len,
+                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream) {
+  if (n == 0 || (!d_calls && !d_counts && !d_stats)) return WALT_OK;
+  WALT_HIP(hipSetDevice(idx->device));
+  MethArgs a;
+  a.ref[0] = idx->ref[0]; a.ref[1] = idx->ref[1];
+  a.ref_last = ref_words(idx) - 1;
+  a.genome_len = idx->head.genome_len;
+  a.start_index = idx->view.start_index;
+  a.n_chrom = idx->view.n_chrom;
+  a.bases = static_cast<const uint8_t*>(d_bases);
+  a.offsets = static_cast<const uint64_t*>(d_offsets);
+  a.n = n;
+  a.records = static_cast<const uint8_t*>(d_records);
+  a.rec_stride = rec_stride;
+  a.conv = static_cast<const uint8_t*>(d_conv);
+  a.conv_stride = conv_stride;
+  a.conversion = (uint32_t)conversion;
+  a.call_len = static_cast<const uint32_t*>(d_call_len);
+  a.calls = static_cast<uint8_t*>(d_calls);
+  a.counts = static_cast<unsigned long long*>(d_counts);
+  a.shards = d_stats ? idx->meth_shards : nullptr;
+  const uint64_t want = ((uint64_t)n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
+  const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
+  hipLaunchKernelGGL(k_meth_call, dim3(grid), dim3(kBlock), 0, stream, a);
+  if (d_stats)
+    hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
+                       static_cast<unsigned long long*>(d_stats));
+  WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+}  // namespace walt
+
+using namespace walt;
+
+extern "C" {
+
+int walt_index_enable_reference(walt_index* idx) {
+  if (!idx) return fail(WALT_EINVAL, "walt_index_enable_reference: bad argument");
+  return build_reference(idx, nullptr);
+}
+
+int walt_index_has_reference(const walt_index* idx) { return idx && idx->ref[0] ? 1 : 0; }
+
+int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                void* stream) {
+  int rc = meth_args_check(idx, "walt_meth_call_batch_device", record_stride, d_conv, conv_stride, conversion);
+  if (rc) return rc;
+  if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, "walt_meth_call_batch_device: bad argument");
+  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
+    return fail(WALT_EINVAL, "walt_meth_call_batch_device: records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
+  return meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
+                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream));
+}
+
+int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                         size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                         const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
+  int rc = meth_args_check(idx, "walt_meth_call_batch", record_stride, conv, conv_stride, conversion);
+  if (rc) return rc;
+  if (n == 0) return WALT_OK;
+  if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, "walt_meth_call_batch: bad argument");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
+    if (offsets[i + 1] - offsets[i] > kMaxReadLenAny) return fail(WALT_EINVAL, "read length above 1024 is not supported");
+    if (conv && conv[(size_t)i * conv_stride] != 'T' && conv[(size_t)i * conv_stride] != 'A')
+      return fail(WALT_EINVAL, "walt_meth_call_batch: conversion " + std::to_string((int)conv[(size_t)i * conv_stride]) +
+                                   " of read " + std::to_string(i) + " is neither 'T' nor 'A'");
+  }
+  if (!calls && !counts && !stats) return WALT_OK;
+  WALT_HIP(hipSetDevice(idx->device));
+  const uint64_t nbytes = offsets[n] - offsets[0];
+  // the records and conversions as the kernel reads them: packed (the caller's strides stay on the host)
+  std::vector<walt_best_match> rec((size_t)n);
+  std::vector<uint8_t> cv;
+  for (uint32_t i = 0; i < n; ++i) memcpy(&rec[i], static_cast<const char*>(records) + (size_t)i * record_stride, sizeof(walt_best_match));
+  if (conv) {
+    cv.resize(n);
+    for (uint32_t i = 0; i < n; ++i) cv[i] = conv[(size_t)i * conv_stride];
+  }
+  std::vector<uint64_t> rel((size_t)n + 1);
+  for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
+  struct Scoped {
+    void* p = nullptr;
+    ~Scoped() { if (p) (void)hipFree(p); }
+    int get(size_t bytes) {
+      return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (methylation calls)");
+    }
+  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats;
+  if ((rc = d_bases.get(nbytes + 16)) || (rc = d_off.get(((size_t)n + 1) * 8)) || (rc = d_rec.get((size_t)n * 16))) return rc;
+  if (conv && (rc = d_conv.get(n))) return rc;
+  if (call_len && (rc = d_len.get((size_t)n * 4))) return rc;
+  if (calls && (rc = d_calls.get(nbytes + 16))) return rc;
+  if (counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts)))) return rc;
+  if (stats && (rc = d_stats.get(sizeof(walt_meth_stats)))) return rc;
+  WALT_HIP(hipMemcpy(d_bases.p, bases + offsets[0], nbytes, hipMemcpyHostToDevice));
+  WALT_HIP(hipMemcpy(d_off.p, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+  WALT_HIP(hipMemcpy(d_rec.p, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+  if (conv) WALT_HIP(hipMemcpy(d_conv.p, cv.data(), n, hipMemcpyHostToDevice));
+  if (call_len) WALT_HIP(hipMemcpy(d_len.p, call_len, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
+  rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
+                   d_stats.p, nullptr);
+  if (rc) return rc;
+  WALT_HIP(hipStreamSynchronize(nullptr));
+  if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
+  if (counts) WALT_HIP(hipMemcpy(counts, d_counts.p, (size_t)n * sizeof(walt_meth_counts), hipMemcpyDeviceToHost));
+  if (stats) {
+    walt_meth_stats st;
+    WALT_HIP(hipMemcpy(&st, d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    stats->reads += st.reads;
+    for (int i = 0; i < 4; ++i) { stats->meth[i] += st.meth[i]; stats->unmeth[i] += st.unmeth[i]; }
+  }
+  return WALT_OK;
+}
+
+}  // extern "C"

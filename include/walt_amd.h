@@ -353,6 +353,77 @@ int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void
                                 int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                 void* stream);
 
+/* ---- methylation pile-up: two counters per cytosine of the genome, fed by the calls above ----------------------
+ * The reference has no such mode (its users sort the mapped records and run a second program over them); the contract
+ * is defined here.  A pile-up belongs to one index, which must hold the reference (WALT_EINVAL otherwise), and lives on
+ * its device; it must be destroyed before the index is closed.
+ *
+ * Which calls count.  A call is what walt_meth_call_batch writes as a letter other than '.' at read position i of a
+ * record.  Only records with times == 1 are piled up: the set walt_meth_stats sums.  A record with times >= 2 adds
+ * nothing (its calls string is still written), and neither does one that gets no call above: genome_pos outside the
+ * genome, a conversion that is neither 'T' nor 'A', a read longer than 1024 bases.  call_len bounds the called
+ * positions as there.  Overlapping mates of a pair are both counted, as walt_meth_stats counts them.
+ *
+ * Where a call lands.  With [lo, hi) the chromosome that holds genome_pos and q = genome_pos + i, the forward position
+ * is f = q for a '+' record and f = lo + hi - 1 - q for a '-' record (both strands share the chromosome starts).  The
+ * call adds 1 to meth[f] for an upper-case letter, 1 to unmeth[f] for a lower-case one.  ('+', 'T') and ('-', 'A')
+ * records land on a forward C, a cytosine of the '+' strand; ('+', 'A') and ('-', 'T') on a forward G, a cytosine of
+ * the '-' strand.  A read and its reverse complement pile onto the same sites.
+ *
+ * What a site is.  A forward position f with meth[f] + unmeth[f] > 0 whose '+' reference base R[f] is C or G.  Strand
+ * and context come from R alone, so that every read that reaches f agrees:
+ *   R[f] == 'C': strand '+', n1 = R[f+1], n2 = R[f+2], key 'G';
+ *   R[f] == 'G': strand '-', n1 = R[f-1], n2 = R[f-2], key 'C';
+ * context by the rule above, first match: n1 outside [lo, hi): unknown; n1 == key: CpG; n2 outside: unknown;
+ * n2 == key: CHG; else CHH.  On an N-free genome R' is R reverse-complemented per chromosome, so this is the context of
+ * every letter that landed on f, and the per-context sums over all sites equal the walt_meth_stats of the same
+ * records.  Where the FASTA had N the strand files hold independent fills (see above; nothing detects that), and
+ * R[f] can be A or T under a call made on R'.  Such positions are not sites; their calls are summed into the
+ * "off-reference" pair the extraction returns, so on any genome reported calls + off-reference calls = the totals.
+ *
+ * Counts are exact up to 2^32 - 1 each (beyond that a counter wraps).  The counters take 8 x genome_len bytes of
+ * device memory (25 GB at 3.1 Gbp) and the extraction's table 1 MiB: walt_pileup_device_bytes = 8 x genome_len +
+ * 1048576; walt_index_device_bytes does not include it.  walt_pileup_create zeroes the counters; when the memory
+ * is not there it returns WALT_ENOMEM naming the bytes it wanted and leaves the index usable.
+ *
+ * Feeding.  walt_meth_pileup_batch[_device] are walt_meth_call_batch[_device] with one more destination: every
+ * argument, output, alignment and error as there (calls, counts and stats stay optional; with all three NULL only the
+ * pile-up is fed), the batch read once; plus WALT_EINVAL for a null pile-up or one of another index.  The adds are
+ * ordered by the stream they are launched on, and two streams may feed one pile-up at the same time (the batch totals
+ * behind d_stats stay one call at a time per index).  The host forms, walt_pileup_clear and walt_pileup_extract wait
+ * for all work on the device first.
+ *
+ * Extraction.  walt_pileup_extract writes the sites of the forward positions [pos_lo, pos_hi), ascending by pos, and
+ * sets *n_sites to how many there are -- also when cap is too small: then WALT_EINVAL naming both numbers, and nothing
+ * is written.  offref (optional): the methylated and unmethylated calls in the range that lie on an A or T of R.  A
+ * range may cut a chromosome; contexts do not depend on it, nor on the index's options.  WALT_EINVAL when
+ * pos_lo > pos_hi or pos_hi > genome_len.  Device form: d_sites (16-byte aligned, cap records), d_n_sites (uint64_t)
+ * and d_offref (uint64_t[2], optional; both 8-byte aligned) are HBM addresses; asynchronous on `stream`, so a cap that
+ * is too small cannot come back as the status: *d_n_sites > cap says that nothing was written.  One extraction at a
+ * time per pile-up (its table belongs to the pile-up), ordered after the adds of its stream. */
+typedef struct walt_pileup walt_pileup;
+typedef struct {
+  uint32_t pos, meth, unmeth;
+  uint8_t strand;  /* '+' or '-' */
+  uint8_t context; /* 0 CpG, 1 CHG, 2 CHH, 3 unknown */
+  uint16_t reserved; /* written as 0 */
+} walt_meth_site; /* 16 bytes */
+int walt_pileup_create(walt_index* idx, walt_pileup** out);
+void walt_pileup_destroy(walt_pileup* p);
+int walt_pileup_clear(walt_pileup* p);
+uint64_t walt_pileup_device_bytes(const walt_pileup* p);
+int walt_meth_pileup_batch(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                           const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                           const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats);
+int walt_meth_pileup_batch_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                  const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                  int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                  void* stream);
+int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_meth_site* sites, uint64_t cap,
+                        uint64_t* n_sites, uint64_t* offref /*[2]: meth, unmeth*/);
+int walt_pileup_extract_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_sites, uint64_t cap,
+                               void* d_n_sites, void* d_offref, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only
@@ -379,6 +450,8 @@ int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void
  *   pe_serial      0  mates and passes on one stream (profiling)   pe_push_wide 0  4-byte heap entries in the push kernel (A/B)
  *   pe_defer_min  -1  as se_defer_min                      pe_roomy    -1  -1: by the workspace's size, 0 / 1: forced
  *   pe_lit_fuse    1  the literal round's three seed shifts in one launch when its list is short (0: seed by seed)
+ *   pile_rows      0  pile-up adds with neighbouring lanes on neighbouring positions instead of one lane per 16-base slice (A/B)
+ *   pile_extract_blocks 0  blocks of the pile-up's extraction kernels (0: by the range; a test hook: the table is the same)
  * Set between calls, not during one.  WALT_EINVAL for an unknown name. */
 int walt_index_set_option(walt_index* idx, const char* name, long long value);
 int walt_index_get_option(const walt_index* idx, const char* name, long long* value);

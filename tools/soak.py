@@ -369,6 +369,77 @@ def run_soak_meth(seeds, pattern=3):
         pattern, len(seeds), reads_total, calls_total)
 
 
+def run_soak_pileup(seeds, pattern=3):
+    """Per-cytosine pile-up (walt_meth_pileup_batch, walt_pileup_extract) on the genomes of `seeds` (many of them with
+    hundreds of short chromosomes): reads of both conversions and both strands, some with call_len, mapped on the GPU and
+    piled into ONE pile-up per genome; the WHOLE extracted table compared with the restatement in
+    tests/test_gpu_pileup.py, under either shape of the adds and a random extraction grid.  Returns the summary line,
+    raises SoakMismatch at the first difference (tests/test_gpu_pileup_soak.py)."""
+    import refio
+    import walt_amd
+    import test_gpu_meth as rule_of
+    import test_gpu_pileup as pile_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 260)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    reads_total = sites_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 32452843 + 11)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_pile_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                R = rule_of.reference_bases(db)
+                lengths = [lo + 2, 40, 47, 60, 100, 100, 131, min(150, hi), hi]
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                pile = None
+                try:
+                    idx.set_option("pile_rows", rng.choice([0, 1]))
+                    idx.set_option("pile_extract_blocks", rng.choice([0, 0, 1, 3, 64, 5000]))
+                    pile = idx.pileup()
+                    acc = None
+                    for conv, ag in (("CT", False), ("GA", True)):
+                        reads = sample(rng, seqs, 800, conv, lengths, refio)
+                        frm, to = ("T", "C") if conv == "CT" else ("A", "G")
+                        reads = ["".join(to if (c == frm and rng.random() < 0.1) else c for c in r) for r in reads]
+                        call_len = None
+                        if rng.random() < 0.5:
+                            call_len = [rng.choice([len(r), len(r), len(r) // 2, 0, len(r) + 3]) for r in reads]
+                        bases, offs = walt_amd.pack_reads(reads)
+                        recs, _ = idx.map_se_batch(bases, offs, ag_wildcard=ag, max_mismatches=rng.choice([2, 6, 10]))
+                        cv = "A" if ag else "T"
+                        got = pile.add_batch(bases, offs, recs, cv, call_len=call_len)
+                        plain = idx.meth_call_batch(bases, offs, recs, cv, call_len=call_len)
+                        if any(g.tobytes() != p.tobytes() for g, p in zip(got, plain)):
+                            raise SoakMismatch("MISMATCH pile-up seed %d %s: per-read outputs differ from meth_call_batch" % (seed, conv))
+                        acc = pile_of.expected_counts(R, db.start_index, reads, recs, cv, call_len, into=acc)
+                        reads_total += len(reads)
+                    try:
+                        sites = pile_of.assert_table(pile.extract(), R[0], db.start_index, acc[0], acc[1], "seed %d" % seed)
+                    except AssertionError as e:
+                        raise SoakMismatch("MISMATCH pile-up seed %d: %s" % (seed, e))
+                    sites_total += int(sites.size)
+                finally:
+                    if pile is not None:
+                        pile.close()
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    return "soak ok: pile-up, pattern %d, %d genomes, %d reads, %d sites identical to the restatement" % (
+        pattern, len(seeds), reads_total, sites_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

@@ -81,6 +81,10 @@ batch_stats_dtype = np.dtype(
 meth_counts_dtype = np.dtype([("meth", "<u2", (4,)), ("unmeth", "<u2", (4,))])  # contexts: CpG, CHG, CHH, unknown
 meth_stats_dtype = np.dtype([("reads", "<u8"), ("meth", "<u8", (4,)), ("unmeth", "<u8", (4,))])
 METH_CONTEXTS = ("CpG", "CHG", "CHH", "unknown")
+# walt_meth_site: one covered cytosine of the pile-up (strand ord('+') / ord('-'), context an index into METH_CONTEXTS)
+meth_site_dtype = np.dtype([("pos", "<u4"), ("meth", "<u4"), ("unmeth", "<u4"), ("strand", "u1"), ("context", "u1"),
+                            ("reserved", "<u2")])
+assert meth_site_dtype.itemsize == 16
 assert meth_counts_dtype.itemsize == 16 and meth_stats_dtype.itemsize == 72
 assert best_match_dtype.itemsize == 16 and candidate_dtype.itemsize == 12
 assert pair_result_dtype.itemsize == 64 and batch_stats_dtype.itemsize == 32
@@ -200,6 +204,16 @@ def lib(pattern=None):
     L.walt_index_has_reference.argtypes = [vp]
     L.walt_meth_call_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp]
     L.walt_meth_call_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp]
+    L.walt_pileup_create.argtypes = [vp, c.POINTER(vp)]
+    L.walt_pileup_destroy.argtypes = [vp]
+    L.walt_pileup_destroy.restype = None
+    L.walt_pileup_clear.argtypes = [vp]
+    L.walt_pileup_device_bytes.argtypes = [vp]
+    L.walt_pileup_device_bytes.restype = u64
+    L.walt_meth_pileup_batch.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp]
+    L.walt_meth_pileup_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp]
+    L.walt_pileup_extract.argtypes = [vp, u32, u32, vp, u64, c.POINTER(u64), vp]
+    L.walt_pileup_extract_device.argtypes = [vp, u32, u32, vp, u64, vp, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -510,6 +524,15 @@ class Index:
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
         meth_counts_dtype[n], stats meth_stats_dtype scalar array); an output that is not wanted is None.  stats: an
         existing 1-element meth_stats_dtype array to accumulate into."""
+        return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats)
+
+    def pileup(self):
+        """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
+        return Pileup(self)
+
+    def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
+                    stats=None, want_stats=True):
+        """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -540,9 +563,12 @@ class Index:
         # calls is indexed like bases: offsets[0] bytes in front of the first read belong to neither
         calls_ptr = None if calls is None else calls.ctypes.data - int(offsets[0]) if n else calls.ctypes.data
         bases_ptr = bases.ctypes.data
-        self._ck(self._L.walt_meth_call_batch(self._h, bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None,
-                                              rec_stride, _ptr(conv_arr) if n else None, conv_stride, conversion,
-                                              _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats)))
+        tail = (bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
+                conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats))
+        if pile is None:
+            self._ck(self._L.walt_meth_call_batch(self._h, *tail))
+        else:
+            self._ck(self._L.walt_meth_pileup_batch(self._h, pile, *tail))
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
@@ -633,3 +659,70 @@ class Index:
     def pe_rpbat_workspace_bytes(self, n, max_read_len, top_k):
         """What a random-PBAT paired-end call uses best on this index's device now (walt_pe_rpbat_workspace_bytes_best)."""
         return self._L.walt_pe_rpbat_workspace_bytes_best(self._h, int(n), int(max_read_len), int(top_k))
+
+
+class Pileup:
+    """Per-cytosine methylation pile-up of an Index (include/walt_amd.h, "methylation pile-up"): two exact 32-bit
+    counters per forward position on the index's device, fed by the methylation calls of uniquely mapped records."""
+
+    def __init__(self, index):
+        self._index = index
+        self._L = index._L
+        h = ctypes.c_void_p()
+        index._ck(self._L.walt_pileup_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
+                  want_stats=True):
+        """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
+        return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
+                                       want_stats)
+
+    def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
+                         conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0):
+        """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous."""
+        self._index._ck(self._L.walt_meth_pileup_batch_device(
+            self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+            ord(conversion), d_call_len, d_calls, d_counts, d_stats, stream))
+
+    def extract(self, pos_lo=0, pos_hi=None):
+        """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the
+        methylated / unmethylated calls of the range that lie on an A or T of the reference)."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        n = ctypes.c_uint64(0)
+        offref = np.zeros(2, dtype=np.uint64)
+        rc = self._L.walt_pileup_extract(self._h, int(pos_lo), int(pos_hi), None, 0, ctypes.byref(n), _ptr(offref))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        sites = np.zeros(n.value, dtype=meth_site_dtype)
+        if n.value:
+            self._index._ck(self._L.walt_pileup_extract(self._h, int(pos_lo), int(pos_hi), _ptr(sites), n.value,
+                                                        ctypes.byref(n), _ptr(offref)))
+        return sites, offref
+
+    def extract_device(self, pos_lo, pos_hi, d_sites, cap, d_n_sites, d_offref=None, stream=0):
+        """Device-pointer form (walt_pileup_extract_device); asynchronous."""
+        self._index._ck(self._L.walt_pileup_extract_device(self._h, int(pos_lo), int(pos_hi), d_sites, int(cap), d_n_sites,
+                                                           d_offref, stream))
+
+    def clear(self):
+        self._index._ck(self._L.walt_pileup_clear(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._L.walt_pileup_device_bytes(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.walt_pileup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -49,6 +49,9 @@ struct walt_options {
   long long pe_defer_min = -1;
   int pe_lit_fuse = 1;        // the literal round's three seed shifts in one launch when its list is short (0: seed by seed; A/B)
   int pe_roomy = -1;          // -1: decided once per index from the device's free memory
+  // methylation pile-up
+  int pile_rows = 0;          // the adds with neighbouring lanes on neighbouring positions (meth.hip pile_rows; A/B) instead of lane by slice
+  long long pile_extract_blocks = 0;  // blocks of the extraction kernels (0: by the range; test hook: the table does not depend on it)
 };
 
 struct walt_index {
@@ -101,6 +104,15 @@ struct walt_index {
   // hipFree pair per buffer and call costs milliseconds each.  One call at a time per index.
   void* host_api_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t host_api_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+// Per-cytosine pile-up (pileup.hip): two planes of 32-bit counters indexed by forward position -- methylated,
+// unmethylated -- and the extraction's table (block offsets, then the totals in its last words).
+struct walt_pileup {
+  walt_index* idx = nullptr;
+  uint32_t* plane[2] = {nullptr, nullptr};
+  unsigned long long* table = nullptr;
+  uint64_t device_bytes = 0;
 };
 
 namespace walt {

@@ -51,6 +51,7 @@ struct Options {
   bool rpbat = false;  // -R: single-end random PBAT, every read under both conversions (walt_map_se_rpbat_batch)
   bool rpbat_pe = false;  // -RP: paired-end random PBAT, every pair in both orientations (walt_map_pe_rpbat_batch)
   bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
+  bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -89,6 +90,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "R", "random-pbat")) o.rpbat = true;  // extension: reads of either conversion (abismal's -R)
     else if (is_opt(a, "RP", "random-pbat-pe")) o.rpbat_pe = true;  // extension: pairs of either orientation
     else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
+    else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -307,6 +309,72 @@ static void write_methstats(const string& out_file, const Sink& ms) {
   mf.close();
 }
 
+// ---------------------------------------------------------------- -MC: per-cytosine pile-up
+// One pile-up per device of the run; a share's calls go into the pile-up of the device that mapped it.  At the end of
+// a read file the table is written window by window of forward positions (a bounded buffer per device: a window holds
+// at most as many sites as positions), the windows of several devices merged by position with their counts added.
+struct PileSet {
+  vector<walt_pileup*> p;
+  void open(const vector<walt_index*>& idx) {
+    p.assign(idx.size(), nullptr);
+    for (size_t d = 0; d < idx.size(); ++d)
+      if (walt_pileup_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+  }
+  void close() {
+    for (walt_pileup*& q : p) { if (q) walt_pileup_destroy(q); q = nullptr; }
+  }
+  bool on() const { return !p.empty(); }
+};
+static const uint32_t kCountsWindow = 1u << 22;  // positions per extraction (64 MB of records per device at most)
+static void write_methcounts(const string& out_file, PileSet& ps, const GenomeInfo& g, bool verbose) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  OutFile mf;
+  if (!mf.open_append(out_file + ".methcounts")) die("cannot open input file " + out_file + ".methcounts");
+  const uint64_t genome_len = g.start.back();
+  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+  vector<vector<walt_meth_site>> buf(ps.p.size(), vector<walt_meth_site>((size_t)window));  // allocated once
+  vector<walt_meth_site> merged, other;
+  uint64_t off[2] = {0, 0}, n_total = 0;
+  uint32_t chr = 0;
+  Sink out;
+  for (uint64_t lo = 0; lo < genome_len; lo += window) {
+    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
+    const walt_meth_site* rows = buf[0].data();
+    uint64_t n_rows = 0;
+    for (size_t d = 0; d < ps.p.size(); ++d) {
+      uint64_t n = 0, o2[2] = {0, 0};
+      check(walt_pileup_extract(ps.p[d], (uint32_t)lo, (uint32_t)hi, buf[d].data(), window, &n, o2));
+      off[0] += o2[0]; off[1] += o2[1];
+      if (d == 0) { n_rows = n; continue; }
+      other.clear();  // merge by position, adding the counts
+      const walt_meth_site* b = buf[d].data();
+      uint64_t i = 0, j = 0;
+      while (i < n_rows || j < n) {
+        if (j == n || (i < n_rows && rows[i].pos < b[j].pos)) other.push_back(rows[i++]);
+        else if (i == n_rows || b[j].pos < rows[i].pos) other.push_back(b[j++]);
+        else { walt_meth_site s = rows[i++]; s.meth += b[j].meth; s.unmeth += b[j].unmeth; ++j; other.push_back(s); }
+      }
+      merged.swap(other);
+      rows = merged.data();
+      n_rows = merged.size();
+    }
+    out.clear();
+    for (uint64_t k = 0; k < n_rows; ++k) {
+      const walt_meth_site& s = rows[k];
+      while (s.pos >= g.start[chr + 1]) ++chr;  // (ascending positions)
+      out.put(g.name[chr]); out.ch('\t'); out.u32(s.pos - g.start[chr]); out.ch('\t'); out.ch((char)s.strand); out.ch('\t');
+      out.lit(ctx[s.context & 3]); out.ch('\t'); out.u32(s.meth); out.ch('\t'); out.u32(s.unmeth); out.ch('\n');
+    }
+    n_total += n_rows;
+    if (out.n) mf.write(out.p, out.n);
+  }
+  mf.close();
+  if (verbose)
+    fprintf(stderr, "[walt_amd methcounts: %llu sites; off-reference calls (on an A or T of the reference): %llu methylated, %llu unmethylated]\n",
+            (unsigned long long)n_total, (unsigned long long)off[0], (unsigned long long)off[1]);
+  for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
+}
+
 static double g_t_main = 0;  // start of main (timeline under -v)
 static int host_threads(const Options& o) { return o.threads > 0 ? o.threads : hostio::effective_cpus(); }
 static double now_s() {
@@ -456,7 +524,9 @@ static void process_se(const Options& o, const string& reads_file, const string&
     rd.load(o.batch_size, o.adaptor, bt[0]);
   });
   DeviceSet dev;
-  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth ? WALT_WITH_REFERENCE : 0u));
+  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));
+  PileSet pile;
+  if (o.methcounts) pile.open(dev.idx);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   OutFile fout;
@@ -507,13 +577,17 @@ static void process_se(const Options& o, const string& reads_file, const string&
     vector<walt_meth_stats> meth_of(dev.size());
     memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
     if (o.meth && o.sam && calls.size() < b.offsets[n]) calls.resize(b.offsets[n]);
-    if (o.meth && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
+    if ((o.meth || o.methcounts) && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
       int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
                        : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
       short_of[d] = bs.too_short;
-      if (rc == WALT_OK && o.meth)  // on the device that mapped the share
+      if (rc == WALT_OK && o.methcounts)  // on the device that mapped the share; with -M both in one call
+        rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
+                                    o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
+                                    o.meth && o.sam ? calls.data() : nullptr, nullptr, o.meth ? &meth_of[d] : nullptr);
+      else if (rc == WALT_OK && o.meth)  // on the device that mapped the share
         rc = walt_meth_call_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
                                   o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
                                   o.sam ? calls.data() : nullptr, nullptr, &meth_of[d]);
@@ -578,6 +652,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     put_meth_block(ms, meth_total);
     write_methstats(out_file, ms);
   }
+  if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
   const double t_c0 = now_s();
   dev.close();
   if (o.verbose)
@@ -726,7 +801,9 @@ static void process_pe(const Options& o, const string& file1, const string& file
   const int T_bg = std::max(1, T / 4);
   double t0 = now_s();
   DeviceSet dev;
-  dev.open(o, WALT_STRANDS_ALL | (o.meth ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
+  dev.open(o, WALT_STRANDS_ALL | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
+  PileSet pile;  // -MC: both mates into the same pile-up
+  if (o.methcounts) pile.open(dev.idx);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   hostio::FastqReader rd[2];
@@ -789,8 +866,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
     if (rp && conv.size() < 2 * (size_t)n) conv.resize(2 * (size_t)n);
     vector<walt_meth_stats> meth_of(2 * dev.size());
     memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
-    for (int k = 0; k < 2 && o.meth; ++k) {
-      if (o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
+    for (int k = 0; k < 2 && (o.meth || o.methcounts); ++k) {
+      if (o.meth && o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
       if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
     }
     dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
@@ -802,7 +879,12 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                             o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
       short1[d] = bs[0].too_short;
       short2[d] = bs[1].too_short;
-      for (int k = 0; k < 2 && rc == WALT_OK && o.meth; ++k)  // slot 0 was mapped C->T, slot 1 G->A (-RP: as conv says)
+      for (int k = 0; k < 2 && rc == WALT_OK && o.methcounts; ++k)  // both mates into the device's pile-up; with -M in one call
+        rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
+                                    sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
+                                    clip[k].empty() ? nullptr : clip[k].data() + lo, o.meth && o.sam ? calls[k].data() : nullptr,
+                                    nullptr, o.meth ? &meth_of[2 * d + k] : nullptr);
+      for (int k = 0; k < 2 && rc == WALT_OK && o.meth && !o.methcounts; ++k)  // slot 0 was mapped C->T, slot 1 G->A (-RP: as conv says)
         rc = walt_meth_call_batch(dev.idx[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
                                   sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
                                   clip[k].empty() ? nullptr : clip[k].data() + lo, o.sam ? calls[k].data() : nullptr, nullptr,
@@ -914,6 +996,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     ms.lit("mate2\n"); put_meth_block(ms, meth_total[pbat ? 0 : 1]);
     write_methstats(out_file, ms);
   }
+  if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
   dev.close();
   if (o.verbose)
     fprintf(stderr, "[walt_amd: %d host threads, %zu GPU(s); index %.2f s, ingest not hidden behind the previous batch %.2f s, map %.2f s, "
@@ -925,7 +1008,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -942,6 +1025,7 @@ int main(int argc, const char** argv) {
     if (outs.size() == 1) outs.assign(se.size() + p1.size(), outs[0]);
     for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
     if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
+    if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");
     size_t k = 0;

@@ -11,6 +11,7 @@
 
 #include "map_common.h"
 #include "meth_core.h"
+#include "pileup_core.h"
 
 namespace walt {
 
@@ -162,12 +163,42 @@ struct MethArgs {
   uint8_t* calls;              // null: not wanted
   unsigned long long* counts;  // null: not wanted (two words per read: walt_meth_counts)
   unsigned long long* shards;  // null: no batch totals
+  uint32_t* pile[2];           // the pile-up's counters by forward position: methylated, unmethylated (k_meth_pile* only)
 };
+
+// One call of the pile-up: a 32-bit add whose result nobody reads (no value comes back from the memory side).
+__device__ __forceinline__ void pile_add(uint32_t* __restrict__ plane, uint32_t f) {
+  (void)__hip_atomic_fetch_add(plane + f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// kPile = 2: the eight slices of a group's trip taken one after the other, lane t of the group adding the calls at
+// slice positions t and t + 8: the lanes of one instruction hold neighbouring positions (8 x 4 bytes of one plane),
+// where kPile = 1 has every lane walk its own slice (16 positions apart from its neighbour's).  All eight lanes of a
+// group arrive together (the trip count is the group's); q0 = the genome position of slice 0, position 0.
+__device__ __forceinline__ void pile_rows(uint32_t cm, uint32_t cu, long long q0, uint32_t sub, bool minus, uint32_t lo,
+                                          uint32_t hi, uint32_t* const plane[2]) {
+#pragma unroll
+  for (uint32_t s = 0; s < kMethGroup; ++s) {
+    const uint32_t bm = (uint32_t)__shfl((int)cm, (int)s, kMethGroup), bu = (uint32_t)__shfl((int)cu, (int)s, kMethGroup);
+    if (!(bm | bu)) continue;  // (the same for the whole group)
+#pragma unroll
+    for (uint32_t half = 0; half < 2; ++half) {
+      const uint32_t k = sub + 8u * half;
+      const uint32_t f = pile_forward(q0 + 16 * (long long)s + k, minus, lo, hi);
+      if ((bm >> (2u * k)) & 1u) pile_add(plane[0], f);
+      if ((bu >> (2u * k)) & 1u) pile_add(plane[1], f);
+    }
+  }
+}
 
 // Eight lanes per read, one 16-base slice per lane and trip.  Slices are cut at the 16-byte boundaries of the CALLS
 // array, so a whole slice is one aligned 16-byte store and the eight lanes of a group write 128 contiguous bytes; the
 // first and last slice of a read are partial (offsets are not multiples of 16) and touch only the read's own bytes.
-__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) {
+//
+// kPile: 0 the calling alone (k_meth_call), 1 / 2 the same with every call of a record with times == 1 added to the
+// pile-up (include/walt_amd.h, "methylation pile-up"), the batch read once.  1: every lane adds its own slice's calls
+// (pile_slice); 2: pile_rows.
+template <int kPile>
+__device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   __shared__ uint32_t s_start[kLdsChroms + 1];
   __shared__ unsigned long long s_red[kBlock / 64][kMethTotals];
   const ChromTab tab = chrom_tab_of(a.n_chrom);
@@ -195,7 +226,26 @@ __global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) {
     const uint32_t ga = cv == 'A' ? 1u : 0u;
     const uint32_t* __restrict__ ref = a.ref[strand == '-' ? 1 : 0];
     unsigned long long meth = 0, unmeth = 0;
-    if (end > off && (mapped || a.calls)) {
+    if (kPile == 2 && end > off && (mapped || a.calls)) {  // as below, every lane of the group taking every trip
+      const uint8_t* rb = a.bases + off;
+      uint8_t* cb = a.calls ? a.calls + off : nullptr;
+      const int head = (int)((a.calls ? (uintptr_t)cb : (uintptr_t)rb) & 15u);
+      for (uint64_t done = 0; done < end - off; done += 1u << 30) {
+        const int total = (int)(end - off - done < (1u << 30) ? end - off - done : (1u << 30));
+        const int h = done ? 0 : head;
+        for (int base = -h; base < total; base += 16 * (int)kMethGroup) {
+          const int i0 = base + 16 * (int)sub;
+          uint32_t cm = 0, cu = 0;
+          if (i0 < total) {
+            uint32_t out[4];
+            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                            batch_bytes - off - done, out, meth, unmeth, cm, cu);
+            if (cb) meth_store_slice(cb + done, total, i0, out);
+          }
+          if (times == 1) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
+        }
+      }
+    } else if (end > off && (mapped || a.calls)) {
       // (bytes of calls to write: the read's own; a read longer than any pattern allows is written in pieces of 2^30)
       const uint8_t* rb = a.bases + off;
       uint8_t* cb = a.calls ? a.calls + off : nullptr;
@@ -206,8 +256,17 @@ __global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) {
         const int h = done ? 0 : head;
         for (int i0 = -h + 16 * (int)sub; i0 < total; i0 += 16 * (int)kMethGroup) {
           uint32_t out[4];
-          meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                          batch_bytes - off - done, out, meth, unmeth);
+          if (kPile == 1) {
+            uint32_t cm, cu;
+            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                            batch_bytes - off - done, out, meth, unmeth, cm, cu);
+            if (times == 1)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
+              pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
+                         [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
+          } else {
+            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                            batch_bytes - off - done, out, meth, unmeth);
+          }
           if (cb) meth_store_slice(cb + done, total, i0, out);
         }
       }
@@ -247,6 +306,10 @@ __global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) {
   }
 }
 
+__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) { meth_call_body<0>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile(const MethArgs a) { meth_call_body<1>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows(const MethArgs a) { meth_call_body<2>(a); }
+
 // folds the shards into walt_meth_stats (accumulating) and clears them
 __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
   const uint32_t t = threadIdx.x;  // one thread per total
@@ -273,10 +336,16 @@ static int meth_args_check(const walt_index* idx, const char* who, size_t rec_st
   return WALT_OK;
 }
 
+static int pile_check(const walt_index* idx, const walt_pileup* p, const char* who) {
+  if (!p) return fail(WALT_EINVAL, std::string(who) + ": bad argument (null pile-up)");
+  if (p->idx != idx) return fail(WALT_EINVAL, std::string(who) + ": the pile-up belongs to another index");
+  return WALT_OK;
+}
+
 static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, const void* d_records,
                        size_t rec_stride, const void* d_conv, size_t conv_stride, int conversion, const void* d_call_len,
-                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream) {
-  if (n == 0 || (!d_calls && !d_counts && !d_stats)) return WALT_OK;
+                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream, walt_pileup* pile = nullptr) {
+  if (n == 0 || (!d_calls && !d_counts && !d_stats && !pile)) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   MethArgs a;
   a.ref[0] = idx->ref[0]; a.ref[1] = idx->ref[1];
@@ -296,9 +365,12 @@ static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offse
   a.calls = static_cast<uint8_t*>(d_calls);
   a.counts = static_cast<unsigned long long*>(d_counts);
   a.shards = d_stats ? idx->meth_shards : nullptr;
+  a.pile[0] = pile ? pile->plane[0] : nullptr;
+  a.pile[1] = pile ? pile->plane[1] : nullptr;
   const uint64_t want = ((uint64_t)n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
-  hipLaunchKernelGGL(k_meth_call, dim3(grid), dim3(kBlock), 0, stream, a);
+  hipLaunchKernelGGL(!pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile, dim3(grid), dim3(kBlock), 0,
+                     stream, a);
   if (d_stats)
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
                        static_cast<unsigned long long*>(d_stats));
@@ -319,34 +391,41 @@ int walt_index_enable_reference(walt_index* idx) {
 
 int walt_index_has_reference(const walt_index* idx) { return idx && idx->ref[0] ? 1 : 0; }
 
-int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
-                                const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
-                                int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
-                                void* stream) {
-  int rc = meth_args_check(idx, "walt_meth_call_batch_device", record_stride, d_conv, conv_stride, conversion);
+}  // extern "C"
+
+namespace walt {
+// the two device forms (pile null: walt_meth_call_batch_device)
+static int meth_batch_device(const char* who, walt_index* idx, walt_pileup* pile, const void* d_bases, const void* d_offsets,
+                             uint32_t n, const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                             int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                             void* stream) {
+  int rc = meth_args_check(idx, who, record_stride, d_conv, conv_stride, conversion);
   if (rc) return rc;
-  if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, "walt_meth_call_batch_device: bad argument");
+  if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
-    return fail(WALT_EINVAL, "walt_meth_call_batch_device: records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
+    return fail(WALT_EINVAL, std::string(who) + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
   return meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
-                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream));
+                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile);
 }
 
-int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
-                         size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
-                         const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
-  int rc = meth_args_check(idx, "walt_meth_call_batch", record_stride, conv, conv_stride, conversion);
+// the two host forms (pile null: walt_meth_call_batch)
+static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile, const char* bases, const uint64_t* offsets,
+                           uint32_t n, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                           int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                           walt_meth_stats* stats) {
+  const std::string who(who_c);
+  int rc = meth_args_check(idx, who_c, record_stride, conv, conv_stride, conversion);
   if (rc) return rc;
   if (n == 0) return WALT_OK;
-  if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, "walt_meth_call_batch: bad argument");
+  if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument");
   for (uint32_t i = 0; i < n; ++i) {
     if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
     if (offsets[i + 1] - offsets[i] > kMaxReadLenAny) return fail(WALT_EINVAL, "read length above 1024 is not supported");
     if (conv && conv[(size_t)i * conv_stride] != 'T' && conv[(size_t)i * conv_stride] != 'A')
-      return fail(WALT_EINVAL, "walt_meth_call_batch: conversion " + std::to_string((int)conv[(size_t)i * conv_stride]) +
+      return fail(WALT_EINVAL, who + ": conversion " + std::to_string((int)conv[(size_t)i * conv_stride]) +
                                    " of read " + std::to_string(i) + " is neither 'T' nor 'A'");
   }
-  if (!calls && !counts && !stats) return WALT_OK;
+  if (!calls && !counts && !stats && !pile) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   // the records and conversions as the kernel reads them: packed (the caller's strides stay on the host)
@@ -379,7 +458,7 @@ int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* off
   if (call_len) WALT_HIP(hipMemcpy(d_len.p, call_len, (size_t)n * 4, hipMemcpyHostToDevice));
   if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
   rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
-                   d_stats.p, nullptr);
+                   d_stats.p, nullptr, pile);
   if (rc) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
@@ -391,6 +470,45 @@ int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* off
     for (int i = 0; i < 4; ++i) { stats->meth[i] += st.meth[i]; stats->unmeth[i] += st.unmeth[i]; }
   }
   return WALT_OK;
+}
+}  // namespace walt
+
+extern "C" {
+
+int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                void* stream) {
+  return meth_batch_device("walt_meth_call_batch_device", idx, nullptr, d_bases, d_offsets, n, d_records, record_stride, d_conv,
+                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream);
+}
+
+int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                         size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                         const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
+  return meth_batch_host("walt_meth_call_batch", idx, nullptr, bases, offsets, n, records, record_stride, conv, conv_stride,
+                         conversion, call_len, calls, counts, stats);
+}
+
+int walt_meth_pileup_batch_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                  const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                  int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                  void* stream) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_device: bad argument");
+  const int rc = pile_check(idx, p, "walt_meth_pileup_batch_device");
+  if (rc) return rc;
+  return meth_batch_device("walt_meth_pileup_batch_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
+                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream);
+}
+
+int walt_meth_pileup_batch(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                           const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                           const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch: bad argument");
+  const int rc = pile_check(idx, p, "walt_meth_pileup_batch");
+  if (rc) return rc;
+  return meth_batch_host("walt_meth_pileup_batch", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
+                         conversion, call_len, calls, counts, stats);
 }
 
 }  // extern "C"

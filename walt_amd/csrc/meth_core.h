@@ -42,6 +42,7 @@ WALT_HD uint32_t meth_spread(uint32_t m) {
 struct MethSlice {
   uint32_t out[4];             // the 16 call characters
   unsigned long long meth, unmeth;  // four 16-bit counts each: CpG, CHG, CHH, unknown (the layout of walt_meth_counts)
+  uint32_t cm, cu;             // field masks of the positions called methylated / unmethylated (the pile-up's input)
 };
 
 // One slice: slice position k is read position i0 + k and genome position q0 + k.
@@ -83,6 +84,8 @@ WALT_HD MethSlice meth_slice(const uint32_t rd[4], unsigned long long ext, uint3
   s.meth = WALT_METH_POPC(z & m) | (WALT_METH_POPC(x & m) << 16) | (WALT_METH_POPC(h & m) << 32) | (WALT_METH_POPC(un & m) << 48);
   s.unmeth = WALT_METH_POPC(z & u) | (WALT_METH_POPC(x & u) << 16) | (WALT_METH_POPC(h & u) << 32) | (WALT_METH_POPC(un & u) << 48);
 #undef WALT_METH_POPC
+  s.cm = cm;
+  s.cu = c & u;
   return s;
 }
 
@@ -121,11 +124,14 @@ WALT_HD unsigned long long meth_ref_ext(const uint32_t* ref, long long qs, uint3
 // limit = min(length, call_len); mapped: the record can be called at all.  before / after: the bytes of the batch's
 // bases in front of rb and from rb on: a partial slice (a read's head or tail) is loaded whole where the 16 bytes lie
 // inside the batch (the neighbouring read's bases are masked out by the flags), byte by byte at the batch's two ends.
+// cm / cu = the slice's positions called methylated / unmethylated (field masks; 0 where nothing is called): what a
+// per-cytosine pile-up adds (pileup_core.h).
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
                              uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
                              unsigned long long before, unsigned long long after, uint32_t out[4],
-                             unsigned long long& meth, unsigned long long& unmeth) {
+                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu) {
   out[0] = out[1] = out[2] = out[3] = 0x2E2E2E2Eu;
+  cm = cu = 0;
   if (!mapped || i0 >= (int)limit) return;
   uint32_t call, v1, v2;
   meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2);
@@ -142,6 +148,14 @@ WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool 
   const MethSlice s = meth_slice(rd, meth_ref_ext(ref, (long long)pos + i0 - 2, ref_last), ga, call, v1, v2);
   out[0] = s.out[0]; out[1] = s.out[1]; out[2] = s.out[2]; out[3] = s.out[3];
   meth += s.meth; unmeth += s.unmeth;
+  cm = s.cm; cu = s.cu;
+}
+WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
+                             uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
+                             unsigned long long before, unsigned long long after, uint32_t out[4],
+                             unsigned long long& meth, unsigned long long& unmeth) {
+  uint32_t cm, cu;
+  meth_read_slice(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu);
 }
 // Stores the slice's characters that belong to the read; cb + i0 is 16-byte aligned.  A whole slice is one 16-byte
 // store.  A read's tail [0, kb) goes out as naturally aligned pieces of 8, 4, 2 and 1 bytes by the bits of kb, its

@@ -1,0 +1,292 @@
+// pileup.hip -- per-cytosine methylation pile-up (include/walt_amd.h, "methylation pile-up"): the counters, and the
+// deterministic two-pass extraction of the covered positions as walt_meth_site records.  The adds are a variant of the
+// calling kernel (meth.hip k_meth_pile).  The reference has no such mode; the contract is the header's.
+#include <algorithm>
+
+#include <hip/hip_runtime.h>
+
+#include "map_common.h"
+#include "pileup_core.h"
+
+namespace walt {
+
+constexpr uint32_t kRefPadWords = 16;          // as meth.hip: zero words behind a packed reference
+constexpr uint32_t kPileMaxBlocks = 65536;     // blocks of an extraction at most
+constexpr uint64_t kPileTableBytes = 1u << 20; // block offsets [kPileMaxBlocks + 1], the totals in the last words
+constexpr uint32_t kPileTotals = (uint32_t)(kPileTableBytes / 8) - 8;  // n_sites, off-reference meth, unmeth
+constexpr uint32_t kPileTile = 4096;           // positions per block the default grid aims at
+static_assert(kPileMaxBlocks + 1 <= kPileTotals, "the table holds the offsets in front of the totals");
+static_assert(sizeof(walt_meth_site) == 16, "walt_meth_site is 16 bytes");
+
+struct PileArgs {
+  const uint32_t* plane[2];
+  const uint32_t* ref;         // the '+' reference
+  uint32_t ref_last;
+  const uint32_t* start_index;
+  uint32_t n_chrom;
+  uint32_t pos_lo, pos_hi;     // [pos_lo, pos_hi), pos_hi <= genome_len
+  uint64_t chunk;              // positions per block
+  unsigned long long* table;
+  walt_meth_site* sites;
+  unsigned long long cap;
+  unsigned long long* n_sites_out;  // device pointers of the device form (null: the host reads the table)
+  unsigned long long* offref_out;
+};
+
+// block b's positions [lo, hi)
+__device__ __forceinline__ void pile_block_range(const PileArgs& a, uint64_t& lo, uint64_t& hi) {
+  lo = (uint64_t)a.pos_lo + (uint64_t)blockIdx.x * a.chunk;
+  hi = lo + a.chunk;
+  lo = lo < a.pos_hi ? lo : a.pos_hi;
+  hi = hi < a.pos_hi ? hi : a.pos_hi;
+}
+// 0: uncovered, 1: a site, 2: covered but R[f] is A or T (only the base itself is looked at)
+__device__ __forceinline__ uint32_t pile_kind(const PileArgs& a, uint32_t f, uint32_t m, uint32_t u) {
+  if (!(m | u)) return 0u;
+  const uint32_t code = (a.ref[f >> 4] >> (2u * (f & 15u))) & 3u;
+  return code == 1u || code == 2u ? 1u : 2u;
+}
+
+// pass 1: sites per block; the off-reference calls summed per block, then one atomic per block and total
+__global__ __launch_bounds__(kBlock) void k_pile_count(const PileArgs a) {
+  __shared__ unsigned long long s_red[kBlock / 64][3];
+  uint64_t lo, hi;
+  pile_block_range(a, lo, hi);
+  unsigned long long v[3] = {0, 0, 0};
+  for (uint64_t f = lo + threadIdx.x; f < hi; f += kBlock) {
+    const uint32_t m = a.plane[0][f], u = a.plane[1][f];
+    const uint32_t kind = pile_kind(a, (uint32_t)f, m, u);
+    v[0] += kind == 1u;
+    v[1] += kind == 2u ? m : 0u;
+    v[2] += kind == 2u ? u : 0u;
+  }
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (uint32_t i = 0; i < 3; ++i) {
+    for (int d = 32; d > 0; d >>= 1) v[i] += __shfl_down(v[i], d);
+    if (lane == 0) s_red[wave][i] = v[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long t = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_red[w][threadIdx.x];
+    if (threadIdx.x == 0) a.table[blockIdx.x] = t;
+    else if (t) atomicAdd(&a.table[kPileTotals + threadIdx.x], t);
+  }
+}
+
+// exclusive scan of the block counts in place (one block); table[n_blocks] and the totals' first word = the sum
+__global__ __launch_bounds__(1024) void k_pile_scan(const PileArgs a, uint32_t n_blocks) {
+  __shared__ unsigned long long s_sum[1024];
+  const uint32_t per = (n_blocks + 1023u) / 1024u;
+  const uint32_t b0 = threadIdx.x * per, b1 = b0 + per < n_blocks ? b0 + per : n_blocks;
+  unsigned long long mine = 0;
+  for (uint32_t b = b0; b < b1; ++b) mine += a.table[b];
+  s_sum[threadIdx.x] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long run = 0;
+    for (uint32_t t = 0; t < 1024; ++t) { const unsigned long long x = s_sum[t]; s_sum[t] = run; run += x; }
+    a.table[n_blocks] = run;
+    a.table[kPileTotals] = run;
+    if (a.n_sites_out) *a.n_sites_out = run;
+    if (a.offref_out) { a.offref_out[0] = a.table[kPileTotals + 1]; a.offref_out[1] = a.table[kPileTotals + 2]; }
+  }
+  __syncthreads();
+  unsigned long long run = s_sum[threadIdx.x];
+  for (uint32_t b = b0; b < b1; ++b) { const unsigned long long x = a.table[b]; a.table[b] = run; run += x; }
+}
+
+// pass 2: the records, ascending by position: a block walks its positions kBlock at a time and ranks the sites of a
+// step by ballot within the wavefront and a prefix over the block's wavefronts
+__global__ __launch_bounds__(kBlock) void k_pile_write(const PileArgs a, uint32_t n_blocks) {
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  __shared__ uint32_t s_wave[kBlock / 64];
+  if (a.table[n_blocks] > a.cap) return;  // (uniform) too many for the caller's array: nothing is written
+  const ChromTab tab = chrom_tab_of(a.n_chrom);
+  chrom_tab_stage(s_start, a.start_index, tab);
+  __syncthreads();
+  uint64_t lo, hi;
+  pile_block_range(a, lo, hi);
+  unsigned long long at = a.table[blockIdx.x];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (uint64_t f0 = lo; f0 < hi; f0 += kBlock) {  // (uniform trip count)
+    const uint64_t f = f0 + threadIdx.x;
+    uint32_t m = 0, u = 0, kind = 0;
+    if (f < hi) {
+      m = a.plane[0][f]; u = a.plane[1][f];
+      kind = pile_kind(a, (uint32_t)f, m, u);
+    }
+    const unsigned long long vote = __ballot(kind == 1u);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(vote);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBlock / 64; ++w) {
+      before += w < wave ? s_wave[w] : 0u;
+      total += s_wave[w];
+    }
+    if (kind == 1u) {
+      const unsigned long long slot = at + before + (uint32_t)__popcll(vote & ((1ull << lane) - 1ull));
+      uint32_t c_lo, c_hi;
+      chrom_bounds(s_start, a.start_index, tab, (uint32_t)f, c_lo, c_hi);
+      uint8_t strand = 0, context = 0;
+      (void)pile_site(meth_ref_ext(a.ref, (long long)f - 2, a.ref_last), (uint32_t)f, c_lo, c_hi, strand, context);
+      // one 16-byte store: pos, meth, unmeth, strand | context << 8 | reserved 0
+      *reinterpret_cast<uint4*>(a.sites + slot) = make_uint4((uint32_t)f, m, u, (uint32_t)strand | ((uint32_t)context << 8));
+    }
+    at += total;
+    __syncthreads();  // s_wave is rewritten by the next step
+  }
+}
+
+static PileArgs pile_args(const walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint32_t& n_blocks) {
+  const walt_index* idx = p->idx;
+  PileArgs a;
+  a.plane[0] = p->plane[0]; a.plane[1] = p->plane[1];
+  a.ref = idx->ref[0];
+  a.ref_last = (idx->head.genome_len + 15) / 16 + kRefPadWords - 1;
+  a.start_index = idx->view.start_index;
+  a.n_chrom = idx->view.n_chrom;
+  a.pos_lo = pos_lo; a.pos_hi = pos_hi;
+  const uint64_t range = (uint64_t)pos_hi - pos_lo;
+  uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks
+                                               : std::min<uint64_t>((range + kPileTile - 1) / kPileTile, (uint64_t)idx->n_cu * 8);
+  want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, kPileMaxBlocks), std::max<uint64_t>(range, 1)));
+  n_blocks = (uint32_t)want;
+  a.chunk = (range + want - 1) / want;
+  a.table = p->table;
+  a.sites = nullptr; a.cap = 0; a.n_sites_out = nullptr; a.offref_out = nullptr;
+  return a;
+}
+
+static int pile_range_check(const walt_pileup* p, const char* who, uint32_t pos_lo, uint32_t pos_hi) {
+  if (!p) return fail(WALT_EINVAL, std::string(who) + ": bad argument (null pile-up)");
+  if (pos_lo > pos_hi || pos_hi > p->idx->head.genome_len)
+    return fail(WALT_EINVAL, std::string(who) + ": range [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) +
+                                 ") is not inside the genome's " + std::to_string(p->idx->head.genome_len) + " positions");
+  return WALT_OK;
+}
+
+// count and scan on `stream`
+static int pile_count_launch(const PileArgs& a, uint32_t n_blocks, hipStream_t stream) {
+  WALT_HIP(hipMemsetAsync(a.table + kPileTotals, 0, 3 * sizeof(unsigned long long), stream));
+  hipLaunchKernelGGL(k_pile_count, dim3(n_blocks), dim3(kBlock), 0, stream, a);
+  hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, stream, a, n_blocks);
+  WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+}  // namespace walt
+
+using namespace walt;
+
+extern "C" {
+
+int walt_pileup_create(walt_index* idx, walt_pileup** out) {
+  if (!idx || !out) return fail(WALT_EINVAL, "walt_pileup_create: bad argument");
+  *out = nullptr;
+  if (!idx->ref[0])
+    return fail(WALT_EINVAL, "walt_pileup_create: the index holds no reference (open it with WALT_WITH_REFERENCE or call "
+                             "walt_index_enable_reference)");
+  WALT_HIP(hipSetDevice(idx->device));
+  const uint64_t plane_bytes = 4ull * idx->head.genome_len, want = 2 * plane_bytes + kPileTableBytes;
+  walt_pileup* p = new walt_pileup;
+  p->idx = idx;
+  void* got[3] = {nullptr, nullptr, nullptr};
+  const uint64_t sizes[3] = {plane_bytes, plane_bytes, kPileTableBytes};
+  for (int i = 0; i < 3; ++i) {
+    const hipError_t e = hipMalloc(&got[i], sizes[i] ? sizes[i] : 4);
+    if (e != hipSuccess || hipMemset(got[i], 0, sizes[i]) != hipSuccess) {  // the index stays as it was
+      (void)hipGetLastError();
+      for (void* q : got) if (q) (void)hipFree(q);
+      delete p;
+      return fail(WALT_ENOMEM, "walt_pileup_create: the pile-up wants " + std::to_string(want) + " bytes of device memory (8 x genome_len + " +
+                                   std::to_string(kPileTableBytes) + "): " + hipGetErrorString(e));
+    }
+  }
+  WALT_HIP(hipDeviceSynchronize());
+  p->plane[0] = static_cast<uint32_t*>(got[0]);
+  p->plane[1] = static_cast<uint32_t*>(got[1]);
+  p->table = static_cast<unsigned long long*>(got[2]);
+  p->device_bytes = want;
+  *out = p;
+  return WALT_OK;
+}
+
+void walt_pileup_destroy(walt_pileup* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->idx->device);
+  (void)hipDeviceSynchronize();
+  (void)hipFree(p->plane[0]);
+  (void)hipFree(p->plane[1]);
+  (void)hipFree(p->table);
+  delete p;
+}
+
+int walt_pileup_clear(walt_pileup* p) {
+  if (!p) return fail(WALT_EINVAL, "walt_pileup_clear: bad argument (null pile-up)");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  for (int i = 0; i < 2; ++i) WALT_HIP(hipMemset(p->plane[i], 0, 4ull * p->idx->head.genome_len));
+  WALT_HIP(hipDeviceSynchronize());
+  return WALT_OK;
+}
+
+uint64_t walt_pileup_device_bytes(const walt_pileup* p) { return p ? p->device_bytes : 0; }
+
+int walt_pileup_extract_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_sites, uint64_t cap, void* d_n_sites,
+                               void* d_offref, void* stream) {
+  int rc = pile_range_check(p, "walt_pileup_extract_device", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (!d_n_sites || (cap && !d_sites)) return fail(WALT_EINVAL, "walt_pileup_extract_device: bad argument");
+  if (((uintptr_t)d_sites & 15u) || ((uintptr_t)d_n_sites & 7u) || ((uintptr_t)d_offref & 7u))
+    return fail(WALT_EINVAL, "walt_pileup_extract_device: sites must be 16-byte aligned, n_sites and offref 8-byte aligned");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  uint32_t n_blocks;
+  PileArgs a = pile_args(p, pos_lo, pos_hi, n_blocks);
+  a.sites = static_cast<walt_meth_site*>(d_sites);
+  a.cap = cap;
+  a.n_sites_out = static_cast<unsigned long long*>(d_n_sites);
+  a.offref_out = static_cast<unsigned long long*>(d_offref);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if ((rc = pile_count_launch(a, n_blocks, s))) return rc;
+  if (cap) hipLaunchKernelGGL(k_pile_write, dim3(n_blocks), dim3(kBlock), 0, s, a, n_blocks);
+  WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_meth_site* sites, uint64_t cap,
+                        uint64_t* n_sites, uint64_t* offref) {
+  int rc = pile_range_check(p, "walt_pileup_extract", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (!n_sites || (cap && !sites)) return fail(WALT_EINVAL, "walt_pileup_extract: bad argument");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  uint32_t n_blocks;
+  PileArgs a = pile_args(p, pos_lo, pos_hi, n_blocks);
+  if ((rc = pile_count_launch(a, n_blocks, nullptr))) return rc;
+  unsigned long long tot[3];
+  WALT_HIP(hipMemcpy(tot, p->table + kPileTotals, sizeof tot, hipMemcpyDeviceToHost));
+  *n_sites = tot[0];
+  if (offref) { offref[0] = tot[1]; offref[1] = tot[2]; }
+  if (tot[0] > cap)
+    return fail(WALT_EINVAL, "walt_pileup_extract: the range holds " + std::to_string(tot[0]) + " sites, the array has room for " +
+                                 std::to_string(cap));
+  if (!tot[0]) return WALT_OK;
+  void* d_sites = nullptr;
+  if (hipMalloc(&d_sites, tot[0] * sizeof(walt_meth_site)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(WALT_ENOMEM, "walt_pileup_extract: hipMalloc of " + std::to_string(tot[0] * sizeof(walt_meth_site)) + " bytes failed");
+  }
+  a.sites = static_cast<walt_meth_site*>(d_sites);
+  a.cap = tot[0];
+  hipLaunchKernelGGL(k_pile_write, dim3(n_blocks), dim3(kBlock), 0, nullptr, a, n_blocks);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(sites, d_sites, tot[0] * sizeof(walt_meth_site), hipMemcpyDeviceToHost);
+  (void)hipFree(d_sites);
+  if (e != hipSuccess) return fail(WALT_EHIP, std::string("walt_pileup_extract: ") + hipGetErrorString(e));
+  return WALT_OK;
+}
+
+}  // extern "C"

@@ -20,14 +20,16 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 
 
-def make_genome(rng, pattern):
-    n_chrom = rng.choice([3, 12, 60, 250, 900])
+def make_genome(rng, pattern, many=False):
+    """many: also draw sequence counts beyond what the kernels' table of chromosome starts holds whole (1,023) and
+    beyond its five-word path (4,092; walt_amd/csrc/chrom_core.h), with short sequences so that a genome costs the same"""
+    n_chrom = rng.choice([3, 12, 60, 250, 900, 1100, 2600, 4500, 9000] if many else [3, 12, 60, 250, 900])
     low = rng.random() < 0.4
     alphabet = rng.choice(["TTTTTCCAG", "TTCCCAAGG"]) if low else "ACGT"
     unit = "".join(rng.choice(alphabet) for _ in range(300))
     seqs = []
     for i in range(n_chrom):
-        L = rng.choice([36, 37, 38, 40, 52, 90, 150, 300, 700, 2000, 6000])
+        L = rng.choice([36, 37, 38, 40, 52, 90, 150] if n_chrom > 1000 else [36, 37, 38, 40, 52, 90, 150, 300, 700, 2000, 6000])
         s = [rng.choice(alphabet) for _ in range(L)]
         if L >= 150 and rng.random() < 0.6:
             p = rng.randrange(0, L - 60)
@@ -323,7 +325,7 @@ def run_soak_meth(seeds, pattern=3):
             rng = random.Random(seed * 15485863 + 7)  # a generator of its own: run_soak's draws for a seed stay as they are
             tmp = tempfile.mkdtemp(prefix="walt_soak_meth_", dir=base)
             try:
-                seqs = make_genome(rng, pattern)
+                seqs = make_genome(rng, pattern, many=True)
                 fa = os.path.join(tmp, "g.fa")
                 with open(fa, "w") as f:
                     for nm, sq in seqs:
@@ -389,7 +391,7 @@ def run_soak_pileup(seeds, pattern=3):
             rng = random.Random(seed * 32452843 + 11)
             tmp = tempfile.mkdtemp(prefix="walt_soak_pile_", dir=base)
             try:
-                seqs = make_genome(rng, pattern)
+                seqs = make_genome(rng, pattern, many=True)
                 fa = os.path.join(tmp, "g.fa")
                 with open(fa, "w") as f:
                     for nm, sq in seqs:

@@ -363,7 +363,7 @@ __device__ __forceinline__ void item_stream(const IndexView& iv, uint32_t strand
     if constexpr (FITS) {  // through the LDS array itself: through a pointer that may be either, the reads would be FLAT loads
       const uint32_t chr = chrom_id_steps(s_start, n_chrom, top_step, pos);
       c_lo = s_start[chr]; c_hi = s_start[chr + 1];
-    } else {  // more sequences than the LDS array holds: its samples, then the starts between two of them (map_common.h ChromTab)
+    } else {  // more sequences than the LDS array holds: its samples, then the starts between two of them (chrom_core.h ChromTab)
       walt::chrom_bounds(s_start, iv.start_index, chrom_tab_of(n_chrom), pos, c_lo, c_hi);
     }
   };

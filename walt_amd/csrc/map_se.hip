@@ -1916,7 +1916,7 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
 
         // One wavefront per SIMD fewer and no spilled registers (reads of up to 128 bases: 3 instead of 4; measured after
         // the read hand-out and the candidate list went in: 38.6 against 39.6 ms per 50 M reads) -- unless the genome has
-        // more sequences than the LDS table of chromosome starts holds (map_common.h ChromTab): then every look-up
+        // more sequences than the LDS table of chromosome starts holds (chrom_core.h ChromTab): then every look-up
         // bisects in HBM and the extra wavefront is worth more than the registers (3,000 contigs: 106.7 against 109.8 ms).
         // Option se_stage_occ chooses explicitly (A/B).
         else if (NW <= 10 && (opt.se_stage_occ ? opt.se_stage_occ == (NW <= 8 ? 3 : 2) : (NW <= 8 && view.n_chrom <= 1023u)))

@@ -5,11 +5,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/walt_amd.h"
+#include "batch_host.h"
 #include "host_common.h"
 #include "index_core.h"
 
@@ -18,6 +21,17 @@
     hipError_t e_ = (expr);                                                                  \
     if (e_ != hipSuccess)                                                                    \
       return walt::fail(WALT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+  } while (0)
+
+// WALT_HIP once work may be queued on the index's own streams: `unwind` -- a callable in scope that waits for those
+// streams -- runs before the error return, so that nothing still uses the caller's workspace when the call is back
+#define WALT_HIP_FORKED(expr)                                                                \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      unwind();                                                                              \
+      return walt::fail(WALT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+    }                                                                                        \
   } while (0)
 
 // Tuning values and test hooks of the mapping calls (walt_index_set_option; names in options.h).  The mapping calls
@@ -130,6 +144,91 @@ inline hipError_t host_api_buffer(walt_index* idx, int slot, size_t bytes, void*
   *out = idx->host_api_buf[slot];
   return hipSuccess;
 }
+
+// One call of a kind (single-end: se_busy, paired-end: pe_busy) at a time per index: its streams, events and host-call
+// buffers are the call's.  A second one is refused, never queued (include/walt_amd.h).  A host form takes the lock
+// after its argument checks and before its first host_api_buffer, and tells the device implementation it calls that
+// the lock is held; a public device form takes it itself.
+inline int take_busy(std::unique_lock<std::mutex>& busy, std::mutex& m, const char* entry, const char* kind) {
+  busy = std::unique_lock<std::mutex>(m, std::try_to_lock);
+  if (busy.owns_lock()) return WALT_OK;
+  return fail(WALT_EINVAL, std::string(entry) + ": another " + kind + " call is running on this index (an index is not re-entrant)");
+}
+
+// The device side of a host form's arguments: buffers from idx's grow-only slots and the copies into them (pageable
+// host memory: the copy is done when hipMemcpy returns).  The first failure sticks in `e` (alloc: it was an
+// allocation) and what follows does nothing, so a host form checks once, after its last upload.
+struct HostUpload {
+  walt_index* idx;
+  hipError_t e = hipSuccess;
+  bool alloc = false;
+  void* buffer(int slot, size_t bytes) {
+    void* p = nullptr;
+    if (e == hipSuccess && (e = host_api_buffer(idx, slot, bytes, &p)) != hipSuccess) alloc = true;
+    return p;
+  }
+  void* zeroed(int slot, size_t bytes) {
+    void* p = buffer(slot, bytes);
+    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
+    return p;
+  }
+  // one read set into the slots slot_bases / slot_off: its bases from the first read's on, its offsets relative to that read
+  void reads(int slot_bases, int slot_off, const char* bases, const uint64_t* offsets, uint32_t n, void** d_bases, void** d_off) {
+    const uint64_t nbytes = offsets[n] - offsets[0];
+    const size_t off_bytes = ((size_t)n + 1) * sizeof(uint64_t);
+    std::vector<uint64_t> rel;
+    const uint64_t* off_src = rebase_offsets(offsets, n, rel);
+    *d_bases = buffer(slot_bases, nbytes + 16);
+    *d_off = buffer(slot_off, off_bytes);
+    if (e == hipSuccess) e = hipMemcpy(*d_bases, bases + offsets[0], nbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(*d_off, off_src, off_bytes, hipMemcpyHostToDevice);
+  }
+};
+
+// map_se.hip: err[0] / err[1] / err[2] (non-ACGT words / over-long reads / dropped work items) at the start of a workspace
+int check_read_errors(const void* d_workspace, hipStream_t stream);
+
+// The end of a host form: what the kernels refused in the reads (check_read_errors waits for the null stream's work),
+// then the results -- records, conversion bytes, statistics; one whose host pointer is null is not asked for.
+struct HostDownload {
+  void* host;
+  const void* dev;
+  size_t bytes;
+};
+inline int host_api_finish(const void* d_workspace, std::initializer_list<HostDownload> results) {
+  if (const int rc = check_read_errors(d_workspace, nullptr)) return rc;
+  for (const HostDownload& r : results) {
+    if (!r.host) continue;
+    const hipError_t e = hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(WALT_EHIP, std::string("download failed: ") + hipGetErrorString(e));
+  }
+  return WALT_OK;
+}
+
+// A stream (non-blocking; *priority when given) and its events (timing disabled) for the index: made into locals,
+// destroyed again when one of them fails, and handed over only when all exist -- a member that is set says the whole
+// set is.
+inline hipError_t create_stream_set(hipStream_t* stream, const int* priority, std::initializer_list<hipEvent_t*> events) {
+  hipStream_t s = nullptr;
+  hipError_t e = priority ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, *priority)
+                          : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+  if (e != hipSuccess) return e;
+  std::vector<hipEvent_t> made;
+  while (made.size() < events.size()) {
+    hipEvent_t ev = nullptr;
+    if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) break;
+    made.push_back(ev);
+  }
+  if (e != hipSuccess) {
+    for (hipEvent_t ev : made) (void)hipEventDestroy(ev);
+    (void)hipStreamDestroy(s);
+    return e;
+  }
+  *stream = s;
+  size_t i = 0;
+  for (hipEvent_t* p : events) *p = made[i++];
+  return hipSuccess;
+}
 }  // namespace walt
 
 namespace walt {
@@ -149,6 +248,30 @@ inline int nw_for_len(uint32_t max_len) {
   if (max_len <= 512) return 32;
   if (max_len <= 1024) return 64;
   return 0;
+}
+
+// The kernel instance of a word count nw (nw_for_len): f(std::integral_constant<int, NW>()) with NW the instance, so
+// that f names it as a template argument.  Patterns 5 / 7 stop at kMaxReadLen = 148 / 152 bases: instances 7, 8, 10.
+// WALT_ONLY_NW (development: tools/kernel_resources.sh) builds that one instance only, for quick resource checks.
+template <class F>
+inline int dispatch_nw(int nw, F&& f) {
+#if defined(WALT_ONLY_NW)
+  (void)nw;
+  return f(std::integral_constant<int, WALT_ONLY_NW>());
+#else
+  switch (nw) {
+    case 7: return f(std::integral_constant<int, 7>());
+    case 8: return f(std::integral_constant<int, 8>());
+#if WALT_SEEDPATTERN == 3
+    case 10: return f(std::integral_constant<int, 10>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return f(std::integral_constant<int, 64>());
+#else
+    default: return f(std::integral_constant<int, 10>());
+#endif
+  }
+#endif
 }
 
 constexpr uint32_t kHashSpan = care_pos(kKeyWeight - 1) - care_pos(0);

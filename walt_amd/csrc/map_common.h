@@ -932,7 +932,5 @@ void launch_reduce_stats(unsigned long long* d_shards, unsigned long long* d_sta
 // as launch_reduce_stats, but too_short (counter 0) is cleared without being added (a second mapping of the same reads)
 void launch_reduce_stats_no_short(unsigned long long* d_shards, unsigned long long* d_stats, hipStream_t stream);
 
-int check_read_errors(const void* d_workspace, hipStream_t stream);
-
 }  // namespace walt
 #endif

@@ -1655,15 +1655,16 @@ static int launch_pe_topk(const walt_index* idx, const IndexView& view, const ui
 #endif
 }
 
+// the index's paired-end streams and events (first use): per slot, stream A with the slot's events (slot 0's set also
+// holds pe_start) and stream B
 static int pe_streams(walt_index* idx) {
-  if (idx->pe_start) return WALT_OK;
   for (int k = 0; k < 2; ++k) {
-    for (int j = 0; j < 2; ++j) WALT_HIP(hipStreamCreateWithFlags(&idx->pe_stream[k][j], hipStreamNonBlocking));
-    WALT_HIP(hipEventCreateWithFlags(&idx->pe_fork[k], hipEventDisableTiming));
-    WALT_HIP(hipEventCreateWithFlags(&idx->pe_join[k], hipEventDisableTiming));
-    WALT_HIP(hipEventCreateWithFlags(&idx->pe_done[k], hipEventDisableTiming));
+    if (!idx->pe_stream[k][0]) {
+      if (k == 0) WALT_HIP(create_stream_set(&idx->pe_stream[0][0], nullptr, {&idx->pe_fork[0], &idx->pe_join[0], &idx->pe_done[0], &idx->pe_start}));
+      else WALT_HIP(create_stream_set(&idx->pe_stream[1][0], nullptr, {&idx->pe_fork[1], &idx->pe_join[1], &idx->pe_done[1]}));
+    }
+    if (!idx->pe_stream[k][1]) WALT_HIP(create_stream_set(&idx->pe_stream[k][1], nullptr, {}));
   }
-  WALT_HIP(hipEventCreateWithFlags(&idx->pe_start, hipEventDisableTiming));
   return WALT_OK;
 }
 
@@ -1704,19 +1705,10 @@ static int pe_chunk(walt_index* idx, const uint8_t* d_bases1, const uint64_t* d_
     view.batch_cap_bytes = (uint64_t)w.cap_reads * max_read_len;
     uint32_t* const codes2 = run == kPeRpA ? w.codes2[1 - m] : w.codes2[m];
     if (run != kPeRpA) launch_ascii_to_2bit(bases[m], offs[m], n, codes2, view.batch_cap_bytes, pack_err, stream);
-    int rc;
-    switch (nw) {
-      case 7: rc = launch_pe_topk<7>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 8: rc = launch_pe_topk<8>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-#if WALT_SEEDPATTERN == 3  // patterns 5 / 7 stop at kMaxReadLen = 148 / 152 bases
-      case 10: rc = launch_pe_topk<10>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 16: rc = launch_pe_topk<16>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      case 32: rc = launch_pe_topk<32>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-      default: rc = launch_pe_topk<64>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-#else
-      default: rc = launch_pe_topk<10>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m], w.ranked[m], st, ctl, w.defer_list[m], w, m, stream); break;
-#endif
-    }
+    const int rc = dispatch_nw(nw, [&](auto NW) {
+      return launch_pe_topk<decltype(NW)::value>(idx, view, codes2, offs[m], pack_err, w.stride, n, sb, max_mm, b, top_k, w.heap_n[m],
+                                                 w.ranked[m], st, ctl, w.defer_list[m], w, m, stream);
+    });
     if (rc) return rc;
     if (count_short) launch_reduce_stats(w.shards[m], stats_of[m], stream);
     else launch_reduce_stats_no_short(w.shards[m], stats_of[m], stream);
@@ -1753,12 +1745,6 @@ static int pe_check_args(walt_index* idx, uint32_t top_k, uint32_t max_read_len,
   return WALT_OK;
 }
 
-}  // namespace walt
-
-using namespace walt;
-
-extern "C" {
-
 // bytes a call needs under geometry g: a call of several passes keeps two of them in flight (two workspaces)
 // (rp: the random-PBAT call's, whose slots also hold the mate-exchanged orientation's records)
 static size_t pe_bytes(const PeGeometry& g, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, bool serial, bool rp = false) {
@@ -1778,6 +1764,69 @@ static int pe_choose(const walt_options& opt, uint32_t n, int nw, uint32_t top_k
                                  (rp ? "walt_pe_rpbat_workspace_bytes_best)" : "walt_pe_workspace_bytes_best)"));
   return WALT_OK;
 }
+
+// The frame every paired-end call runs its passes in.  Passes of geo.chunk pairs alternate between two pipeline slots
+// (own workspace and streams) when `two`, so that the latency-bound list kernels and the merge of one pass run beside
+// the throughput-bound pass 1 of the next; else every pass takes slot 0 on the caller's stream.
+// pass(start, cnt, w, pack_err, slot, s) queues the pass of pairs [start, start + cnt): w is its slot's workspace,
+// pack_err the invalid-read counters of the whole call, s the stream of mate 1 and the merge.  rp: random-PBAT slots.
+template <class Pass>
+static int pe_drive(walt_index* idx, uint32_t n, const PeGeometry& geo, bool two, int nw, uint32_t top_k, uint32_t max_read_len,
+                    bool rp, void* d_workspace, hipStream_t stream, Pass&& pass) {
+  if (const int rc = pe_streams(idx)) return rc;
+  PeWorkspace w[2];
+  w[0] = carve_pe(d_workspace, geo, nw, top_k, max_read_len, rp);
+  w[1] = two ? carve_pe(static_cast<uint8_t*>(d_workspace) + w[0].total_bytes, geo, nw, top_k, max_read_len, rp) : w[0];
+  WALT_HIP(hipMemsetAsync(w[0].err, 0, 128 * sizeof(uint32_t), stream));
+  for (int k = 0; k < (two ? 2 : 1); ++k)
+    for (int m = 0; m < 2; ++m) WALT_HIP(hipMemsetAsync(w[k].shards[m], 0, kStatShardBytes, stream));
+  if (two) {
+    WALT_HIP(hipEventRecord(idx->pe_start, stream));
+    for (int k = 0; k < 2; ++k) WALT_HIP(hipStreamWaitEvent(idx->pe_stream[k][0], idx->pe_start, 0));
+  }
+  // work queued on the index's own streams must not outlive an error return (the caller frees its workspace)
+  auto unwind = [&]() {
+    for (int k = 0; k < 2; ++k)
+      for (int j = 0; j < 2; ++j)
+        if (idx->pe_stream[k][j]) (void)hipStreamSynchronize(idx->pe_stream[k][j]);
+  };
+  uint32_t p = 0;
+  for (uint32_t start = 0; start < n; start += geo.chunk, ++p) {
+    const uint32_t cnt = n - start < geo.chunk ? n - start : geo.chunk;
+    const int slot = two ? (int)(p & 1) : 0;
+    const int rc = pass(start, cnt, w[slot], w[0].err, slot, two ? idx->pe_stream[slot][0] : stream);
+    if (rc) {
+      unwind();
+      return rc;
+    }
+  }
+  if (two)
+    for (int k = 0; k < 2; ++k) {
+      WALT_HIP_FORKED(hipEventRecord(idx->pe_done[k], idx->pe_stream[k][0]));
+      WALT_HIP_FORKED(hipStreamWaitEvent(stream, idx->pe_done[k], 0));
+    }
+  return WALT_OK;
+}
+
+// A device form behind its argument checks: the index's paired-end lock (locked: the host form that calls already holds
+// it), the geometry its workspace allows, and the frame above.
+template <class Pass>
+static int pe_device_call(walt_index* idx, uint32_t n, int nw, uint32_t top_k, uint32_t max_read_len, bool rp, bool locked,
+                          void* d_workspace, size_t workspace_bytes, hipStream_t stream, Pass&& pass) {
+  std::unique_lock<std::mutex> busy;
+  if (!locked)
+    if (const int rc = take_busy(busy, idx->pe_busy, rp ? "walt_map_pe_rpbat_batch" : "walt_map_pe_batch", "paired-end")) return rc;
+  WALT_HIP(hipSetDevice(idx->device));
+  PeGeometry geo;
+  if (const int rc = pe_choose(idx->opt, n, nw, top_k, max_read_len, workspace_bytes, &geo, rp)) return rc;
+  return pe_drive(idx, n, geo, n > geo.chunk && idx->opt.pe_serial == 0, nw, top_k, max_read_len, rp, d_workspace, stream, pass);
+}
+
+}  // namespace walt
+
+using namespace walt;
+
+extern "C" {
 
 size_t walt_pe_workspace_bytes(uint32_t n, uint32_t max_read_len, uint32_t top_k) {
   int nw = nw_for_len(max_read_len);
@@ -1811,56 +1860,38 @@ int walt_map_pe_batch_device(walt_index* idx, const void* d_bases1, const void* 
                              uint32_t b, uint32_t top_k, int frag_range, void* d_out, void* d_stats,
                              void* d_workspace, size_t workspace_bytes, void* stream_) {
   int nw = 0;
-  int rc = pe_check_args(idx, top_k, max_read_len, &nw);
+  const int rc = pe_check_args(idx, top_k, max_read_len, &nw);
   if (rc) return rc;
   if (n == 0) return WALT_OK;
-  std::unique_lock<std::mutex> busy(idx->pe_busy, std::try_to_lock);
-  if (!busy.owns_lock()) return fail(WALT_EINVAL, "walt_map_pe_batch: another paired-end call is running on this index (an index is not re-entrant)");
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  WALT_HIP(hipSetDevice(idx->device));
-  PeGeometry geo;
-  if ((rc = pe_choose(idx->opt, n, nw, top_k, max_read_len, workspace_bytes, &geo))) return rc;
-  const uint32_t chunk = geo.chunk;
-  if ((rc = pe_streams(idx))) return rc;
-  // Passes alternate between two pipeline slots (own workspace and streams), so the latency-bound list
-  // kernels and the merge of one pass run beside the throughput-bound pass 1 of the next.
-  const bool serial = idx->opt.pe_serial != 0;
-  const bool two = n > chunk && !serial;
-  PeWorkspace w[2];
-  w[0] = carve_pe(d_workspace, geo, nw, top_k, max_read_len);
-  w[1] = two ? carve_pe(static_cast<uint8_t*>(d_workspace) + w[0].total_bytes, geo, nw, top_k, max_read_len) : w[0];
-  WALT_HIP(hipMemsetAsync(w[0].err, 0, 128 * sizeof(uint32_t), stream));
-  for (int k = 0; k < (two ? 2 : 1); ++k)
-    for (int m = 0; m < 2; ++m) WALT_HIP(hipMemsetAsync(w[k].shards[m], 0, kStatShardBytes, stream));
-  if (two) {
-    WALT_HIP(hipEventRecord(idx->pe_start, stream));
-    for (int k = 0; k < 2; ++k) WALT_HIP(hipStreamWaitEvent(idx->pe_stream[k][0], idx->pe_start, 0));
-  }
-  // work queued on the index's own streams must not outlive an error return (the caller frees its workspace)
-  auto unwind = [&]() {
-    for (int k = 0; k < 2; ++k)
-      for (int j = 0; j < 2; ++j)
-        if (idx->pe_stream[k][j]) (void)hipStreamSynchronize(idx->pe_stream[k][j]);
-  };
   unsigned long long* const stats_of[2] = {reinterpret_cast<unsigned long long*>(d_stats),
                                            reinterpret_cast<unsigned long long*>(d_stats) + 4};
-  uint32_t pass = 0;
-  for (uint32_t start = 0; start < n; start += chunk, ++pass) {
-    uint32_t cnt = n - start < chunk ? n - start : chunk;
-    const int slot = two ? (int)(pass & 1) : 0;
-    rc = pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases1), reinterpret_cast<const uint64_t*>(d_offsets1) + start,
-                  reinterpret_cast<const uint8_t*>(d_bases2), reinterpret_cast<const uint64_t*>(d_offsets2) + start, cnt,
-                  nw, max_read_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
-                  stats_of, true, w[slot], w[0].err, slot, two ? idx->pe_stream[slot][0] : stream);
-    if (rc) { unwind(); return rc; }
+  return pe_device_call(idx, n, nw, top_k, max_read_len, false, false, d_workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream_),
+                        [&](uint32_t start, uint32_t cnt, const PeWorkspace& w, uint32_t* pack_err, int slot, hipStream_t s) {
+    return pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases1), reinterpret_cast<const uint64_t*>(d_offsets1) + start,
+                    reinterpret_cast<const uint8_t*>(d_bases2), reinterpret_cast<const uint64_t*>(d_offsets2) + start, cnt,
+                    nw, max_read_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
+                    stats_of, true, w, pack_err, slot, s);
+  });
+}
+
+// What the two host forms share in front of their device work: the scan of both mates' offsets (bases_needed: a mate
+// with bases but no array is refused first), the argument checks, and -- pairs to map -- the index's paired-end lock
+// and both read sets in the host-call slots 0 / 2 and 1 / 3.  *nw stays 0 when n is 0: nothing to do.
+static int pe_host_begin(walt_index* idx, const char* entry, const char* const bases[2], const uint64_t* const offs[2], uint32_t n,
+                         uint32_t top_k, bool bases_needed, std::unique_lock<std::mutex>& busy, HostUpload& up, uint32_t* max_len,
+                         int* nw, void* d_bases[2], void* d_off[2]) {
+  for (int m = 0; m < 2; ++m) {
+    if (bases_needed && n && !bases[m] && offs[m][n] > offs[m][0]) return fail(WALT_EINVAL, std::string(entry) + ": bad argument");
+    if (const char* bad = scan_offsets(offs[m], n, max_len)) return fail(WALT_EINVAL, bad);
   }
-  if (two)
-    for (int k = 0; k < 2; ++k) {
-      if (hipEventRecord(idx->pe_done[k], idx->pe_stream[k][0]) != hipSuccess || hipStreamWaitEvent(stream, idx->pe_done[k], 0) != hipSuccess) {
-        unwind();
-        return fail(WALT_EHIP, "paired-end: joining the pipeline slots failed");
-      }
-    }
+  int nw_ = 0;
+  if (const int rc = pe_check_args(idx, top_k, *max_len, &nw_)) return rc;
+  if (n == 0) return WALT_OK;
+  if (const int rc = take_busy(busy, idx->pe_busy, entry, "paired-end")) return rc;
+  WALT_HIP(hipSetDevice(idx->device));
+  up.idx = idx;
+  for (int m = 0; m < 2; ++m) up.reads(m, 2 + m, bases[m], offs[m], n, &d_bases[m], &d_off[m]);
+  *nw = nw_;
   return WALT_OK;
 }
 
@@ -1870,39 +1901,17 @@ int walt_map_pe_batch(walt_index* idx, const char* bases1, const uint64_t* offse
                       walt_candidate* ranked2, uint32_t* ranked_n2, walt_batch_stats* stats) {
   if (!offsets1 || !offsets2 || (!out && n)) return fail(WALT_EINVAL, "walt_map_pe_batch: bad argument");
   if (stats) memset(stats, 0, 2 * sizeof(*stats));
+  const uint64_t* const offs[2] = {offsets1, offsets2};
+  const char* const bases[2] = {bases1, bases2};
+  std::unique_lock<std::mutex> busy;
+  HostUpload up{nullptr};
   uint32_t max_len = 0;
-  const uint64_t* offs[2] = {offsets1, offsets2};
-  for (int m = 0; m < 2; ++m)
-    for (uint32_t i = 0; i < n; ++i) {
-      if (offs[m][i + 1] < offs[m][i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
-      uint64_t l = offs[m][i + 1] - offs[m][i];
-      if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
-      if (l > max_len) max_len = (uint32_t)l;
-    }
   int nw = 0;
-  int rc = pe_check_args(idx, top_k, max_len, &nw);
-  if (rc) return rc;
-  if (n == 0) return WALT_OK;
-  WALT_HIP(hipSetDevice(idx->device));
-  const char* bases[2] = {bases1, bases2};
-  void *d_bases[2] = {nullptr, nullptr}, *d_off[2] = {nullptr, nullptr}, *d_out = nullptr, *d_stats = nullptr, *d_ws = nullptr;
-  hipError_t e = hipSuccess;
-  for (int m = 0; m < 2 && e == hipSuccess; ++m) {
-    const uint64_t nbytes = offs[m][n] - offs[m][0];
-    const uint64_t* off_src = offs[m];
-    std::vector<uint64_t> rel;
-    if (offs[m][0] != 0) {  // a slice of a larger batch (several devices share one)
-      rel.resize((size_t)n + 1);
-      for (uint32_t i = 0; i <= n; ++i) rel[i] = offs[m][i] - offs[m][0];
-      off_src = rel.data();
-    }
-    if ((e = host_api_buffer(idx, m, nbytes + 16, &d_bases[m])) != hipSuccess) break;
-    if ((e = host_api_buffer(idx, 2 + m, ((size_t)n + 1) * sizeof(uint64_t), &d_off[m])) != hipSuccess) break;
-    if ((e = hipMemcpy(d_bases[m], bases[m] + offs[m][0], nbytes, hipMemcpyHostToDevice)) != hipSuccess) break;
-    e = hipMemcpy(d_off[m], off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = host_api_buffer(idx, 4, (size_t)n * sizeof(walt_pair_result), &d_out);
-  if (e == hipSuccess) e = host_api_buffer(idx, 5, 2 * sizeof(walt_batch_stats), &d_stats);
+  void *d_bases[2] = {nullptr, nullptr}, *d_off[2] = {nullptr, nullptr};
+  int rc = pe_host_begin(idx, "walt_map_pe_batch", bases, offs, n, top_k, false, busy, up, &max_len, &nw, d_bases, d_off);
+  if (rc || !nw) return rc;
+  void* const d_out = up.buffer(4, (size_t)n * sizeof(walt_pair_result));
+  void* const d_stats = up.zeroed(5, 2 * sizeof(walt_batch_stats));
   // the same decision the device form's callers make (walt_pe_workspace_bytes_best): the larger passes when the device has
   // the room.  One pass at a time here (the ranked lists are copied out between passes): one workspace.
   walt_options one_slot = idx->opt;
@@ -1917,44 +1926,31 @@ int walt_map_pe_batch(walt_index* idx, const char* bases1, const uint64_t* offse
                                                                    free_b >= roomy_bytes + (2ull << 30)))))
       geo = g1;
   }
-  const uint32_t chunk = geo.chunk;
-  const size_t ws_bytes = carve_pe(nullptr, geo, nw, top_k, max_len).total_bytes;
-  if (e == hipSuccess) e = host_api_buffer(idx, 6, ws_bytes, &d_ws);
-  if (e == hipSuccess) e = hipMemset(d_stats, 0, 2 * sizeof(walt_batch_stats));
-  if (e != hipSuccess) return fail(WALT_EHIP, std::string("paired-end upload failed: ") + hipGetErrorString(e));
-  PeWorkspace w = carve_pe(d_ws, geo, nw, top_k, max_len);
-  if ((rc = pe_streams(idx))) return rc;
-  e = hipMemset(w.err, 0, 128 * sizeof(uint32_t));
-  for (int m = 0; m < 2 && e == hipSuccess; ++m) e = hipMemset(w.shards[m], 0, kStatShardBytes);
-  if (e != hipSuccess) return fail(WALT_EHIP, std::string("workspace setup failed: ") + hipGetErrorString(e));
+  void* const d_ws = up.buffer(6, carve_pe(nullptr, geo, nw, top_k, max_len).total_bytes);
+  if (up.e != hipSuccess) return fail(WALT_EHIP, std::string("paired-end upload failed: ") + hipGetErrorString(up.e));
   unsigned long long* const stats_of[2] = {reinterpret_cast<unsigned long long*>(d_stats),
                                            reinterpret_cast<unsigned long long*>(d_stats) + 4};
-  for (uint32_t start = 0; start < n && !rc; start += chunk) {
-    uint32_t cnt = n - start < chunk ? n - start : chunk;
-    rc = pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases[0]), reinterpret_cast<const uint64_t*>(d_off[0]) + start,
-                  reinterpret_cast<const uint8_t*>(d_bases[1]), reinterpret_cast<const uint64_t*>(d_off[1]) + start, cnt, nw,
-                  max_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
-                  stats_of, true, w, w.err, 0, nullptr);
-    if (rc) break;
-    if (hipDeviceSynchronize() != hipSuccess) { rc = fail(WALT_EHIP, "paired-end kernels failed"); break; }
-    walt_candidate* rk[2] = {ranked1, ranked2};
-    uint32_t* rn[2] = {ranked_n1, ranked_n2};
-    for (int m = 0; m < 2 && !rc; ++m) {
+  walt_candidate* const rk[2] = {ranked1, ranked2};
+  uint32_t* const rn[2] = {ranked_n1, ranked_n2};
+  rc = pe_drive(idx, n, geo, false, nw, top_k, max_len, false, d_ws, nullptr,
+                [&](uint32_t start, uint32_t cnt, const PeWorkspace& w, uint32_t* pack_err, int slot, hipStream_t s) {
+    const int rc_pass = pe_chunk(idx, reinterpret_cast<const uint8_t*>(d_bases[0]), reinterpret_cast<const uint64_t*>(d_off[0]) + start,
+                                 reinterpret_cast<const uint8_t*>(d_bases[1]), reinterpret_cast<const uint64_t*>(d_off[1]) + start, cnt, nw,
+                                 max_len, max_mismatches, b, top_k, frag_range, reinterpret_cast<PairResult*>(d_out) + start,
+                                 stats_of, true, w, pack_err, slot, s);
+    if (rc_pass) return rc_pass;
+    if (hipDeviceSynchronize() != hipSuccess) return fail(WALT_EHIP, "paired-end kernels failed");
+    for (int m = 0; m < 2; ++m) {
       if (rk[m] && hipMemcpy(rk[m] + (size_t)start * top_k, w.ranked[m], (size_t)cnt * top_k * sizeof(walt_candidate),
                              hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(WALT_EHIP, "download of the ranked lists failed");
-      if (!rc && rn[m] && hipMemcpy(rn[m] + start, w.heap_n[m], (size_t)cnt * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(WALT_EHIP, "download of the ranked-list lengths failed");
+        return fail(WALT_EHIP, "download of the ranked lists failed");
+      if (rn[m] && hipMemcpy(rn[m] + start, w.heap_n[m], (size_t)cnt * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(WALT_EHIP, "download of the ranked-list lengths failed");
     }
-  }
-  if (!rc) rc = check_read_errors(d_ws, nullptr);
-  if (!rc) {
-    if (hipMemcpy(out, d_out, (size_t)n * sizeof(walt_pair_result), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(WALT_EHIP, "download failed");
-    if (!rc && stats && hipMemcpy(stats, d_stats, 2 * sizeof(walt_batch_stats), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(WALT_EHIP, "download of the statistics failed");
-  }
-  return rc;
+    return (int)WALT_OK;
+  });
+  if (rc) return rc;
+  return host_api_finish(d_ws, {{out, d_out, (size_t)n * sizeof(walt_pair_result)}, {stats, d_stats, 2 * sizeof(walt_batch_stats)}});
 }
 
 // ---------------------------------------------------------------------------
@@ -1978,7 +1974,7 @@ static int map_pe_rpbat_device(walt_index* idx, const void* d_bases1, const void
                                uint32_t b, uint32_t top_k, int frag_range, void* d_out, void* d_conv, void* d_stats,
                                void* d_workspace, size_t workspace_bytes, hipStream_t stream, bool locked) {
   int nw = 0;
-  int rc = pe_check_args(idx, top_k, max_read_len, &nw);
+  const int rc = pe_check_args(idx, top_k, max_read_len, &nw);
   if (rc) return rc;
   if (n == 0) return WALT_OK;
   if (!d_bases1 || !d_offsets1 || !d_bases2 || !d_offsets2 || !d_out || !d_conv || !d_stats || !d_workspace ||
@@ -1986,31 +1982,6 @@ static int map_pe_rpbat_device(walt_index* idx, const void* d_bases1, const void
       (reinterpret_cast<uintptr_t>(d_conv) & 1))
     return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch_device: bad argument (null pointer, d_out / d_workspace not 16-byte "
                              "aligned, or d_conv not 2-byte aligned)");
-  std::unique_lock<std::mutex> busy(idx->pe_busy, std::defer_lock);
-  if (!locked && !busy.try_lock())
-    return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: another paired-end call is running on this index (an index is not re-entrant)");
-  WALT_HIP(hipSetDevice(idx->device));
-  PeGeometry geo;
-  if ((rc = pe_choose(idx->opt, n, nw, top_k, max_read_len, workspace_bytes, &geo, true))) return rc;
-  const uint32_t chunk = geo.chunk;
-  if ((rc = pe_streams(idx))) return rc;
-  const bool serial = idx->opt.pe_serial != 0;
-  const bool two = n > chunk && !serial;
-  PeWorkspace w[2];
-  w[0] = carve_pe(d_workspace, geo, nw, top_k, max_read_len, true);
-  w[1] = two ? carve_pe(static_cast<uint8_t*>(d_workspace) + w[0].total_bytes, geo, nw, top_k, max_read_len, true) : w[0];
-  WALT_HIP(hipMemsetAsync(w[0].err, 0, 128 * sizeof(uint32_t), stream));
-  for (int k = 0; k < (two ? 2 : 1); ++k)
-    for (int m = 0; m < 2; ++m) WALT_HIP(hipMemsetAsync(w[k].shards[m], 0, kStatShardBytes, stream));
-  if (two) {
-    WALT_HIP(hipEventRecord(idx->pe_start, stream));
-    for (int k = 0; k < 2; ++k) WALT_HIP(hipStreamWaitEvent(idx->pe_stream[k][0], idx->pe_start, 0));
-  }
-  auto unwind = [&]() {
-    for (int k = 0; k < 2; ++k)
-      for (int j = 0; j < 2; ++j)
-        if (idx->pe_stream[k][j]) (void)hipStreamSynchronize(idx->pe_stream[k][j]);
-  };
   const uint8_t* bases1 = reinterpret_cast<const uint8_t*>(d_bases1);
   const uint8_t* bases2 = reinterpret_cast<const uint8_t*>(d_bases2);
   const uint64_t* off1 = reinterpret_cast<const uint64_t*>(d_offsets1);
@@ -2021,35 +1992,25 @@ static int map_pe_rpbat_device(walt_index* idx, const void* d_bases1, const void
   unsigned long long* const stats_t[2] = {st, st + 4};
   unsigned long long* const stats_a[2] = {st + 4, st};
   const unsigned gm_cap = (unsigned)idx->n_cu * 4u;
-  uint32_t pass = 0;
-  for (uint32_t start = 0; start < n; start += chunk, ++pass) {
-    const uint32_t cnt = n - start < chunk ? n - start : chunk;
-    const int slot = two ? (int)(pass & 1) : 0;
-    hipStream_t s = two ? idx->pe_stream[slot][0] : stream;
+  return pe_device_call(idx, n, nw, top_k, max_read_len, true, locked, d_workspace, workspace_bytes, stream,
+                        [&](uint32_t start, uint32_t cnt, const PeWorkspace& w, uint32_t* pack_err, int slot, hipStream_t s) {
     PairResult* const out = reinterpret_cast<PairResult*>(d_out) + start;
     // 1. orientation T into the caller's records; 2. orientation A (mates exchanged, the codes of 1. reused) into the
     // slot's record array.  The second pass's kernels follow the first's merge on the slot's streams, so its ranked
     // lists are consumed before they are overwritten.
-    rc = pe_chunk(idx, bases1, off1 + start, bases2, off2 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
-                  frag_range, out, stats_t, true, w[slot], w[0].err, slot, s, kPeRpT);
-    if (!rc)
-      rc = pe_chunk(idx, bases2, off2 + start, bases1, off1 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
-                    frag_range, w[slot].arec, stats_a, false, w[slot], w[0].err, slot, s, kPeRpA);
-    if (rc) { unwind(); return rc; }
+    int rc_pass = pe_chunk(idx, bases1, off1 + start, bases2, off2 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
+                           frag_range, out, stats_t, true, w, pack_err, slot, s, kPeRpT);
+    if (!rc_pass)
+      rc_pass = pe_chunk(idx, bases2, off2 + start, bases1, off1 + start, cnt, nw, max_read_len, max_mismatches, b, top_k,
+                         frag_range, w.arec, stats_a, false, w, pack_err, slot, s, kPeRpA);
+    if (rc_pass) return rc_pass;
     // 3. the pair-level rule
     const unsigned gm = grid_for(cnt) < gm_cap ? grid_for(cnt) : gm_cap;
     hipLaunchKernelGGL(k_pe_rpbat_merge, dim3(gm), dim3(kBlock), 0, s, reinterpret_cast<uint4*>(out),
-                       reinterpret_cast<const uint4*>(w[slot].arec), reinterpret_cast<uint16_t*>(d_conv) + start, cnt);
-    if (hipGetLastError() != hipSuccess) { unwind(); return fail(WALT_EHIP, "k_pe_rpbat_merge launch failed"); }
-  }
-  if (two)
-    for (int k = 0; k < 2; ++k) {
-      if (hipEventRecord(idx->pe_done[k], idx->pe_stream[k][0]) != hipSuccess || hipStreamWaitEvent(stream, idx->pe_done[k], 0) != hipSuccess) {
-        unwind();
-        return fail(WALT_EHIP, "paired-end: joining the pipeline slots failed");
-      }
-    }
-  return WALT_OK;
+                       reinterpret_cast<const uint4*>(w.arec), reinterpret_cast<uint16_t*>(d_conv) + start, cnt);
+    if (hipGetLastError() != hipSuccess) return fail(WALT_EHIP, "k_pe_rpbat_merge launch failed");
+    return (int)WALT_OK;
+  });
 }
 
 int walt_map_pe_rpbat_batch_device(walt_index* idx, const void* d_bases1, const void* d_offsets1, const void* d_bases2,
@@ -2066,64 +2027,27 @@ int walt_map_pe_rpbat_batch(walt_index* idx, const char* bases1, const uint64_t*
                             int frag_range, walt_pair_result* out, uint8_t* conv, walt_batch_stats* stats) {
   if (!idx || !offsets1 || !offsets2 || (n && (!out || !conv))) return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: bad argument");
   if (stats) memset(stats, 0, 2 * sizeof(*stats));
-  const uint64_t* offs[2] = {offsets1, offsets2};
-  const char* bases[2] = {bases1, bases2};
+  const uint64_t* const offs[2] = {offsets1, offsets2};
+  const char* const bases[2] = {bases1, bases2};
+  std::unique_lock<std::mutex> busy;
+  HostUpload up{nullptr};
   uint32_t max_len = 0;
-  for (int m = 0; m < 2; ++m) {
-    if (n && !bases[m] && offs[m][n] > offs[m][0]) return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: bad argument");
-    for (uint32_t i = 0; i < n; ++i) {
-      if (offs[m][i + 1] < offs[m][i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
-      uint64_t l = offs[m][i + 1] - offs[m][i];
-      if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
-      if (l > max_len) max_len = (uint32_t)l;
-    }
-  }
   int nw = 0;
-  int rc = pe_check_args(idx, top_k, max_len, &nw);
-  if (rc) return rc;
-  if (n == 0) return WALT_OK;
-  // the index's paired-end lock before its host-call buffers are touched: a second call is refused, it cannot
-  // reallocate them under this one
-  std::unique_lock<std::mutex> busy(idx->pe_busy, std::try_to_lock);
-  if (!busy.owns_lock())
-    return fail(WALT_EINVAL, "walt_map_pe_rpbat_batch: another paired-end call is running on this index (an index is not re-entrant)");
-  WALT_HIP(hipSetDevice(idx->device));
-  void *d_bases[2] = {nullptr, nullptr}, *d_off[2] = {nullptr, nullptr}, *d_out = nullptr, *d_stats = nullptr,
-       *d_ws = nullptr, *d_conv = nullptr;
-  hipError_t e = hipSuccess;
-  for (int m = 0; m < 2 && e == hipSuccess; ++m) {
-    const uint64_t nbytes = offs[m][n] - offs[m][0];
-    const uint64_t* off_src = offs[m];
-    std::vector<uint64_t> rel;
-    if (offs[m][0] != 0) {  // a slice of a larger batch (several devices share one)
-      rel.resize((size_t)n + 1);
-      for (uint32_t i = 0; i <= n; ++i) rel[i] = offs[m][i] - offs[m][0];
-      off_src = rel.data();
-    }
-    if ((e = host_api_buffer(idx, m, nbytes + 16, &d_bases[m])) != hipSuccess) break;
-    if ((e = host_api_buffer(idx, 2 + m, ((size_t)n + 1) * sizeof(uint64_t), &d_off[m])) != hipSuccess) break;
-    if ((e = hipMemcpy(d_bases[m], bases[m] + offs[m][0], nbytes, hipMemcpyHostToDevice)) != hipSuccess) break;
-    e = hipMemcpy(d_off[m], off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice);
-  }
+  void *d_bases[2] = {nullptr, nullptr}, *d_off[2] = {nullptr, nullptr};
+  int rc = pe_host_begin(idx, "walt_map_pe_rpbat_batch", bases, offs, n, top_k, true, busy, up, &max_len, &nw, d_bases, d_off);
+  if (rc || !nw) return rc;
   const size_t ws_bytes = walt_pe_rpbat_workspace_bytes_best(idx, n, max_len, top_k);
-  if (e == hipSuccess) e = host_api_buffer(idx, 4, (size_t)n * sizeof(walt_pair_result), &d_out);
-  if (e == hipSuccess) e = host_api_buffer(idx, 5, 2 * sizeof(walt_batch_stats), &d_stats);
-  if (e == hipSuccess) e = host_api_buffer(idx, 6, ws_bytes, &d_ws);
-  if (e == hipSuccess) e = host_api_buffer(idx, 7, 2 * (size_t)n, &d_conv);
-  if (e == hipSuccess) e = hipMemset(d_stats, 0, 2 * sizeof(walt_batch_stats));
-  if (e != hipSuccess) return fail(WALT_EHIP, std::string("paired-end upload failed: ") + hipGetErrorString(e));
+  void* const d_out = up.buffer(4, (size_t)n * sizeof(walt_pair_result));
+  void* const d_stats = up.zeroed(5, 2 * sizeof(walt_batch_stats));
+  void* const d_ws = up.buffer(6, ws_bytes);
+  void* const d_conv = up.buffer(7, 2 * (size_t)n);
+  if (up.e != hipSuccess) return fail(WALT_EHIP, std::string("paired-end upload failed: ") + hipGetErrorString(up.e));
   rc = map_pe_rpbat_device(idx, d_bases[0], d_off[0], d_bases[1], d_off[1], n, max_len, max_mismatches, b, top_k,
                            frag_range, d_out, d_conv, d_stats, d_ws, ws_bytes, nullptr, true);
   if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(WALT_EHIP, "paired-end kernels failed");
-  if (!rc) rc = check_read_errors(d_ws, nullptr);
-  if (!rc) {
-    if (hipMemcpy(out, d_out, (size_t)n * sizeof(walt_pair_result), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(conv, d_conv, 2 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(WALT_EHIP, "download failed");
-    if (!rc && stats && hipMemcpy(stats, d_stats, 2 * sizeof(walt_batch_stats), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(WALT_EHIP, "download of the statistics failed");
-  }
-  return rc;
+  if (rc) return rc;
+  return host_api_finish(d_ws, {{out, d_out, (size_t)n * sizeof(walt_pair_result)}, {conv, d_conv, 2 * (size_t)n},
+                                {stats, d_stats, 2 * sizeof(walt_batch_stats)}});
 }
 
 }  // extern "C"

@@ -1794,14 +1794,6 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
     if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
     if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
   };
-#define WALT_HIP_FORKED(expr)                                                                \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      unwind();                                                                              \
-      return walt::fail(WALT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-    }                                                                                        \
-  } while (0)
   uint32_t* const rng = heavy_area + kHeavyCtlWords - 8;  // {first entry, end} of the deferred list the rest launch maps
   if (mono) {
     // the one-kernel heavy pass (large regions verified by the whole wavefront of their read's lane) instead of the
@@ -1868,14 +1860,10 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
     if (lit_side && !idx->se_side) {
       int lo_pri = 0, hi_pri = 0;
       WALT_HIP(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
-      WALT_HIP(hipStreamCreateWithPriority(&idx->se_side, hipStreamNonBlocking, lo_pri));
-      WALT_HIP(hipEventCreateWithFlags(&idx->se_fork, hipEventDisableTiming));
-      WALT_HIP(hipEventCreateWithFlags(&idx->se_join, hipEventDisableTiming));
+      WALT_HIP(create_stream_set(&idx->se_side, &lo_pri, {&idx->se_fork, &idx->se_join}));
     }
-    if (piped && !idx->se_pipe) {
-      WALT_HIP(hipStreamCreateWithFlags(&idx->se_pipe, hipStreamNonBlocking));
-      for (hipEvent_t& e : idx->se_pipe_ev) WALT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    if (piped && !idx->se_pipe)
+      WALT_HIP(create_stream_set(&idx->se_pipe, nullptr, {&idx->se_pipe_ev[0], &idx->se_pipe_ev[1], &idx->se_pipe_ev[2]}));
     // se_lit_side = 2 (default): the side launch starts HERE, on what pass 1 deferred (most of the list: pass 1 sees every
     // read, the staged rounds the heavy sixth), and runs beside the whole heavy pass -- a chain of dependent look-ups in
     // few wavefronts that fills a fraction of the device; what the staged rounds defer is mapped at the end.  The
@@ -1893,8 +1881,8 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
       WALT_HIP_FORKED(hipEventRecord(idx->se_join, idx->se_side));
     }
     if (piped) {  // (pass 1 done)
-      WALT_HIP(hipEventRecord(idx->se_pipe_ev[0], stream));
-      WALT_HIP(hipStreamWaitEvent(idx->se_pipe, idx->se_pipe_ev[0], 0));
+      WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[0], stream));
+      WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_pipe, idx->se_pipe_ev[0], 0));
     }
     // the rounds of one chunk: look-up stage, then the verifiers of its items, kPat times, and the final fold
     auto run_chunk = [&](hipStream_t cs, uint32_t* ctl_base, uint32_t* lists, bool lit, const uint32_t* count, const uint32_t* list,
@@ -2022,7 +2010,6 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
     mark(3);
     return WALT_OK;
   }
-#undef WALT_HIP_FORKED
   uint32_t* defer_sorted = defer_list + stride;
   if (n <= kDeferMask) launch_bin_deferred(defer_count, defer_list, defer_sorted, stream);
   else defer_sorted = defer_list;
@@ -2090,65 +2077,63 @@ static SeWorkspace se_workspace(void* d_workspace, uint32_t n, uint32_t max_read
 // strands _CT00/_CT01, 2: G->A strands _GA10/_GA11)
 static int se_map_pass(walt_index* idx, const IndexView& view, const SeWorkspace& w, const uint64_t* offsets, uint32_t n,
                        int nw, uint32_t sb, uint32_t max_mm, uint32_t b, BestMatch* out, hipStream_t stream) {
-  int rc;
-#define WALT_SE_CASE(NWV) rc = launch_map_se<NWV>(idx, view, w.codes2, offsets, w.err, n, sb, max_mm, b, out, w.shards, w.defer_count, w.defer_list, w.stride, w.heavy_area, w.carry_area, stream)
-#if defined(WALT_ONLY_NW)  // (development: one kernel instance, for quick resource checks -- tools/kernel_resources.sh)
-  WALT_SE_CASE(WALT_ONLY_NW);
-  (void)nw;
-#else
-  switch (nw) {
-    case 7: WALT_SE_CASE(7); break;
-    case 8: WALT_SE_CASE(8); break;
-#if WALT_SEEDPATTERN == 3  // patterns 5 / 7 stop at kMaxReadLen = 148 / 152 bases
-    case 10: WALT_SE_CASE(10); break;
-    case 16: WALT_SE_CASE(16); break;
-    case 32: WALT_SE_CASE(32); break;
-    default: WALT_SE_CASE(64); break;
-#else
-    default: WALT_SE_CASE(10); break;
+  return dispatch_nw(nw, [&](auto NW) {
+    return launch_map_se<decltype(NW)::value>(idx, view, w.codes2, offsets, w.err, n, sb, max_mm, b, out, w.shards, w.defer_count,
+                                              w.defer_list, w.stride, w.heavy_area, w.carry_area, stream);
+  });
+}
+
+// What map_se_device and map_se_rpbat_device (rp) share up to their first mapping pass: the batch-size and length
+// checks, the index's single-end lock (locked: the host form that calls already holds it), the workspace with its
+// control words cleared, this call's view of the index, and the reads packed (profile events around the pack).
+struct SeCall {
+  std::unique_lock<std::mutex> busy;
+  int nw = 0;
+  SeWorkspace w;
+  IndexView view;
+  const uint64_t* offsets = nullptr;
+};
+static int se_begin(walt_index* idx, bool rp, bool locked, const void* d_bases, const void* d_offsets, uint32_t n,
+                    uint32_t max_read_len, void* d_workspace, size_t workspace_bytes, hipStream_t stream, SeCall& c) {
+  const std::string entry = rp ? "walt_map_se_rpbat_batch" : "walt_map_se_batch";
+  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
+  if (!locked)
+    if (const int rc_busy = take_busy(c.busy, idx->se_busy, entry.c_str(), "single-end")) return rc_busy;
+#if defined(WALT_DIAG)
+  if (const int rc_diag = se_diag_setup()) return rc_diag;
 #endif
-  }
-#endif
-#undef WALT_SE_CASE
-  return rc;
+  if (const int rc_len = se_check_len(max_read_len, c.nw)) return rc_len;
+  const size_t need = rp ? walt_se_rpbat_workspace_bytes(n, max_read_len) : walt_se_workspace_bytes(n, max_read_len);
+  if (workspace_bytes < need)
+    return fail(WALT_EINVAL, entry + "_device: the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
+                                 std::to_string(need) + (rp ? " (walt_se_rpbat_workspace_bytes)" : " (walt_se_workspace_bytes)"));
+  WALT_HIP(hipSetDevice(idx->device));
+  c.w = se_workspace(d_workspace, n, max_read_len, c.nw);
+  WALT_HIP(hipMemsetAsync(c.w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
+  WALT_HIP(hipMemsetAsync(c.w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  c.offsets = reinterpret_cast<const uint64_t*>(d_offsets);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
+  c.view = idx->view;  // this launch's copy: the limits lane_load_read enforces
+  c.view.batch_max_len = max_read_len;
+  c.view.batch_cap_bytes = (uint64_t)n * max_read_len;
+  launch_ascii_to_2bit(reinterpret_cast<const uint8_t*>(d_bases), c.offsets, n, c.w.codes2, c.view.batch_cap_bytes, c.w.err, stream);
+  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
+  return WALT_OK;
 }
 
 int map_se_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, uint32_t max_read_len,
                   int ag, uint32_t max_mm, uint32_t b, void* d_out, void* d_stats, void* d_workspace,
-                  size_t workspace_bytes, hipStream_t stream) {
+                  size_t workspace_bytes, hipStream_t stream, bool locked) {
   if (!idx) return fail(WALT_EINVAL, "null index");
   const unsigned need = ag ? WALT_STRANDS_GA : WALT_STRANDS_CT;
   if ((idx->strand_mask & need) != need)
     return fail(WALT_EINVAL, ag ? "index opened without the _GA10/_GA11 strands" : "index opened without the _CT00/_CT01 strands");
   if (n == 0) return WALT_OK;
-  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
-  // One single-end call at a time per index: the call's side streams and events belong to the index (include/walt_amd.h)
-  std::unique_lock<std::mutex> busy(idx->se_busy, std::try_to_lock);
-  if (!busy.owns_lock()) return fail(WALT_EINVAL, "walt_map_se_batch: another single-end call is running on this index (an index is not re-entrant)");
-#if defined(WALT_DIAG)
-  if (const int rc_diag = se_diag_setup()) return rc_diag;
-#endif
-  int nw;
-  if (const int rc_len = se_check_len(max_read_len, nw)) return rc_len;
-  if (workspace_bytes < walt_se_workspace_bytes(n, max_read_len))
-    return fail(WALT_EINVAL, "walt_map_se_batch_device: the workspace holds " + std::to_string(workspace_bytes) + " bytes, the call needs " +
-                                 std::to_string(walt_se_workspace_bytes(n, max_read_len)) + " (walt_se_workspace_bytes)");
-  WALT_HIP(hipSetDevice(idx->device));
-  const SeWorkspace w = se_workspace(d_workspace, n, max_read_len, nw);
-  WALT_HIP(hipMemsetAsync(w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
-  WALT_HIP(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
-  const uint8_t* bases = reinterpret_cast<const uint8_t*>(d_bases);
-  const uint64_t* offsets = reinterpret_cast<const uint64_t*>(d_offsets);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
-  IndexView view = idx->view;  // this launch's copy: the limits lane_load_read enforces
-  view.batch_max_len = max_read_len;
-  view.batch_cap_bytes = (uint64_t)n * max_read_len;
-  launch_ascii_to_2bit(bases, offsets, n, w.codes2, view.batch_cap_bytes, w.err, stream);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
-  BestMatch* out = reinterpret_cast<BestMatch*>(d_out);
-  const int rc = se_map_pass(idx, view, w, offsets, n, nw, ag ? 2u : 0u, max_mm, b, out, stream);
+  SeCall c;
+  if (const int rc = se_begin(idx, false, locked, d_bases, d_offsets, n, max_read_len, d_workspace, workspace_bytes, stream, c)) return rc;
+  const int rc = se_map_pass(idx, c.view, c.w, c.offsets, n, c.nw, ag ? 2u : 0u, max_mm, b, reinterpret_cast<BestMatch*>(d_out), stream);
   if (rc) return rc;
-  launch_reduce_stats(w.shards, reinterpret_cast<unsigned long long*>(d_stats), stream);
+  launch_reduce_stats(c.w.shards, reinterpret_cast<unsigned long long*>(d_stats), stream);
   if (idx->profile) {
     WALT_HIP(hipEventRecord(idx->ev[2], stream));
     idx->ev_valid = true;
@@ -2194,7 +2179,6 @@ static uint64_t se_rpbat_ga_offset(uint32_t n, uint32_t max_read_len) {
   return align_up(walt_se_workspace_bytes(n, max_read_len), 16);
 }
 
-// locked: the caller (walt_map_se_rpbat_batch) already holds idx->se_busy
 int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, uint32_t max_read_len,
                         uint32_t max_mm, uint32_t b, void* d_out, void* d_conv, void* d_stats, void* d_workspace,
                         size_t workspace_bytes, hipStream_t stream, bool locked) {
@@ -2208,38 +2192,18 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
                                  " (random PBAT maps under both conversions: open it with WALT_STRANDS_ALL)");
   }
   if (n == 0) return WALT_OK;
-  if (n > kDeferMask + 1) return fail(WALT_EINVAL, "more than 2^28 reads in one batch (the reference's -N limit is 10^8, walt.cpp:236-239)");
   if (!d_out || !d_conv || !d_stats || !d_workspace || (reinterpret_cast<uintptr_t>(d_out) & 15) ||
       (reinterpret_cast<uintptr_t>(d_workspace) & 15))
     return fail(WALT_EINVAL, "walt_map_se_rpbat_batch_device: bad argument (null pointer, or d_out / d_workspace not 16-byte aligned)");
-  std::unique_lock<std::mutex> busy(idx->se_busy, std::defer_lock);
-  if (!locked && !busy.try_lock())
-    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: another single-end call is running on this index (an index is not re-entrant)");
-#if defined(WALT_DIAG)
-  if (const int rc_diag = se_diag_setup()) return rc_diag;
-#endif
-  int nw;
-  if (const int rc_len = se_check_len(max_read_len, nw)) return rc_len;
-  if (workspace_bytes < walt_se_rpbat_workspace_bytes(n, max_read_len))
-    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch_device: the workspace holds " + std::to_string(workspace_bytes) +
-                                 " bytes, the call needs " + std::to_string(walt_se_rpbat_workspace_bytes(n, max_read_len)) +
-                                 " (walt_se_rpbat_workspace_bytes)");
-  WALT_HIP(hipSetDevice(idx->device));
-  const SeWorkspace w = se_workspace(d_workspace, n, max_read_len, nw);
-  uint4* const ga = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(d_workspace) + se_rpbat_ga_offset(n, max_read_len));
-  WALT_HIP(hipMemsetAsync(w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
-  WALT_HIP(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
-  const uint64_t* offsets = reinterpret_cast<const uint64_t*>(d_offsets);
-  unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
-  IndexView view = idx->view;
-  view.batch_max_len = max_read_len;
-  view.batch_cap_bytes = (uint64_t)n * max_read_len;
   // the reads are packed once; both passes map the same 2-bit codes (the conversion is only the strand base)
-  launch_ascii_to_2bit(reinterpret_cast<const uint8_t*>(d_bases), offsets, n, w.codes2, view.batch_cap_bytes, w.err, stream);
-  if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[1], stream));
+  SeCall c;
+  int rc = se_begin(idx, true, locked, d_bases, d_offsets, n, max_read_len, d_workspace, workspace_bytes, stream, c);
+  if (rc) return rc;
+  const SeWorkspace& w = c.w;
+  uint4* const ga = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(d_workspace) + se_rpbat_ga_offset(n, max_read_len));
+  unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
   // C->T pass into the caller's records
-  int rc = se_map_pass(idx, view, w, offsets, n, nw, 0u, max_mm, b, reinterpret_cast<BestMatch*>(d_out), stream);
+  rc = se_map_pass(idx, c.view, w, c.offsets, n, c.nw, 0u, max_mm, b, reinterpret_cast<BestMatch*>(d_out), stream);
   if (rc) return rc;
   // From here the index's side streams may still run the first pass's work on this workspace: an error return waits
   // for them first.
@@ -2247,14 +2211,6 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
     if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
     if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
   };
-#define WALT_HIP_FORKED(expr)                                                                \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      unwind();                                                                              \
-      return walt::fail(WALT_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
-    }                                                                                        \
-  } while (0)
   // Statistics: the shards are reduced once per pass.  The first pass adds all four counters (and clears the shards);
   // the second adds probes / candidates / big_regions only, so too_short is counted once, as a single-conversion call
   // counts it (a read is short under both conversions).
@@ -2266,7 +2222,7 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
   WALT_HIP_FORKED(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
   // G->A pass into the workspace's record array; it starts from (0, 0, '+', max_mm) like the first, never from the
   // first pass's result (a cap taken from it would stop the seed loop before equally good hits are found)
-  rc = se_map_pass(idx, view, w, offsets, n, nw, 2u, max_mm, b, reinterpret_cast<BestMatch*>(ga), stream);
+  rc = se_map_pass(idx, c.view, w, c.offsets, n, c.nw, 2u, max_mm, b, reinterpret_cast<BestMatch*>(ga), stream);
   if (rc) {
     unwind();
     return rc;
@@ -2280,7 +2236,6 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
     idx->ev_valid = true;
   }
   WALT_HIP_FORKED(hipGetLastError());
-#undef WALT_HIP_FORKED
   return WALT_OK;
 }
 
@@ -2384,55 +2339,43 @@ int walt_map_se_batch_device(walt_index* idx, const void* d_bases, const void* d
                              uint32_t max_read_len, int ag_wildcard, uint32_t max_mismatches, uint32_t b,
                              void* d_out, void* d_stats, void* d_workspace, size_t workspace_bytes, void* stream) {
   return map_se_device(idx, d_bases, d_offsets, n, max_read_len, ag_wildcard, max_mismatches, b, d_out, d_stats,
-                       d_workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+                       d_workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false);
+}
+
+// The two host forms (conv: random PBAT, one conversion byte per read): arguments, the offset scan, the index's
+// single-end lock, the reads into the host-call slots 0 / 1 (records 2, statistics 3, workspace 4, conversions 5), the
+// device implementation on the null stream, and the results back.
+static int se_host_call(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, int ag, uint32_t max_mm,
+                        uint32_t b, walt_best_match* out, uint8_t* conv, bool rp, walt_batch_stats* stats) {
+  const std::string entry = rp ? "walt_map_se_rpbat_batch" : "walt_map_se_batch";
+  if (!idx || !offsets || (!bases && n && offsets[n] > 0) || (!out && n) || (rp && !conv && n)) return fail(WALT_EINVAL, entry + ": bad argument");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n == 0) return WALT_OK;
+  uint32_t max_len = 0;
+  if (const char* bad = scan_offsets(offsets, n, &max_len)) return fail(WALT_EINVAL, bad);
+  std::unique_lock<std::mutex> busy;
+  if (const int rc_busy = take_busy(busy, idx->se_busy, entry.c_str(), "single-end")) return rc_busy;
+  WALT_HIP(hipSetDevice(idx->device));
+  const size_t ws_bytes = rp ? walt_se_rpbat_workspace_bytes(n, max_len) : walt_se_workspace_bytes(n, max_len);
+  HostUpload up{idx};
+  void *d_bases = nullptr, *d_off = nullptr;
+  up.reads(0, 1, bases, offsets, n, &d_bases, &d_off);
+  void* const d_out = up.buffer(2, (size_t)n * sizeof(walt_best_match));
+  void* const d_stats = up.zeroed(3, sizeof(walt_batch_stats));
+  void* const d_ws = up.buffer(4, ws_bytes);
+  void* const d_conv = rp ? up.buffer(5, n) : nullptr;
+  if (up.e != hipSuccess)
+    return up.alloc ? fail(WALT_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(up.e))
+                    : fail(WALT_EHIP, std::string("upload failed: ") + hipGetErrorString(up.e));
+  const int rc = rp ? map_se_rpbat_device(idx, d_bases, d_off, n, max_len, max_mm, b, d_out, d_conv, d_stats, d_ws, ws_bytes, nullptr, true)
+                    : map_se_device(idx, d_bases, d_off, n, max_len, ag, max_mm, b, d_out, d_stats, d_ws, ws_bytes, nullptr, true);
+  if (rc) return rc;
+  return host_api_finish(d_ws, {{out, d_out, (size_t)n * sizeof(walt_best_match)}, {conv, d_conv, n}, {stats, d_stats, sizeof(walt_batch_stats)}});
 }
 
 int walt_map_se_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, int ag_wildcard,
                       uint32_t max_mismatches, uint32_t b, walt_best_match* out, walt_batch_stats* stats) {
-  if (!idx || !offsets || (!bases && n && offsets[n] > 0) || (!out && n)) return fail(WALT_EINVAL, "walt_map_se_batch: bad argument");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return WALT_OK;
-  WALT_HIP(hipSetDevice(idx->device));
-  uint32_t max_len = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
-    uint64_t l = offsets[i + 1] - offsets[i];
-    if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
-    if (l > max_len) max_len = (uint32_t)l;
-  }
-  const uint64_t nbytes = offsets[n] - offsets[0];
-  void *d_bases = nullptr, *d_off = nullptr, *d_out = nullptr, *d_stats = nullptr, *d_ws = nullptr;
-  int rc = WALT_OK;
-  hipError_t e;
-  // offsets as the kernels want them: relative to the first read of the batch (a caller that shards a batch
-  // over several devices passes a slice of its offsets array)
-  const uint64_t* off_src = offsets;
-  std::vector<uint64_t> rel;
-  if (offsets[0] != 0) {
-    rel.resize((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
-    off_src = rel.data();
-  }
-  if ((e = host_api_buffer(idx, 0, nbytes + 16, &d_bases)) != hipSuccess ||
-      (e = host_api_buffer(idx, 1, ((size_t)n + 1) * sizeof(uint64_t), &d_off)) != hipSuccess ||
-      (e = host_api_buffer(idx, 2, (size_t)n * sizeof(walt_best_match), &d_out)) != hipSuccess ||
-      (e = host_api_buffer(idx, 3, sizeof(walt_batch_stats), &d_stats)) != hipSuccess ||
-      (e = host_api_buffer(idx, 4, walt_se_workspace_bytes(n, max_len), &d_ws)) != hipSuccess)
-    return fail(WALT_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-  if ((e = hipMemcpyAsync(d_bases, bases + offsets[0], nbytes, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_off, off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-      (e = hipMemsetAsync(d_stats, 0, sizeof(walt_batch_stats), nullptr)) != hipSuccess)
-    return fail(WALT_EHIP, std::string("upload failed: ") + hipGetErrorString(e));
-  rc = map_se_device(idx, d_bases, d_off, n, max_len, ag_wildcard, max_mismatches, b, d_out, d_stats, d_ws,
-                     walt_se_workspace_bytes(n, max_len), nullptr);
-  if (!rc) rc = check_read_errors(d_ws, nullptr);
-  if (!rc) {
-    if ((e = hipMemcpy(out, d_out, (size_t)n * sizeof(walt_best_match), hipMemcpyDeviceToHost)) != hipSuccess)
-      rc = fail(WALT_EHIP, std::string("download failed: ") + hipGetErrorString(e));
-    walt_batch_stats st;
-    if (!rc && hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess && stats) *stats = st;
-  }
-  return rc;
+  return se_host_call(idx, bases, offsets, n, ag_wildcard, max_mismatches, b, out, nullptr, false, stats);
 }
 
 size_t walt_se_rpbat_workspace_bytes(uint32_t n, uint32_t max_read_len) {
@@ -2450,56 +2393,7 @@ int walt_map_se_rpbat_batch_device(walt_index* idx, const void* d_bases, const v
 int walt_map_se_rpbat_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n,
                             uint32_t max_mismatches, uint32_t b, walt_best_match* out, uint8_t* conv,
                             walt_batch_stats* stats) {
-  if (!idx || !offsets || (!bases && n && offsets[n] > 0) || (!out && n) || (!conv && n))
-    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: bad argument");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n == 0) return WALT_OK;
-  // the index's single-end lock before its host-call buffers are touched: a second call is refused, it cannot
-  // reallocate them under this one
-  std::unique_lock<std::mutex> busy(idx->se_busy, std::try_to_lock);
-  if (!busy.owns_lock())
-    return fail(WALT_EINVAL, "walt_map_se_rpbat_batch: another single-end call is running on this index (an index is not re-entrant)");
-  WALT_HIP(hipSetDevice(idx->device));
-  uint32_t max_len = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
-    uint64_t l = offsets[i + 1] - offsets[i];
-    if (l > 1024) return fail(WALT_EINVAL, "read length above 1024 is not supported");
-    if (l > max_len) max_len = (uint32_t)l;
-  }
-  const uint64_t nbytes = offsets[n] - offsets[0];
-  void *d_bases = nullptr, *d_off = nullptr, *d_out = nullptr, *d_conv = nullptr, *d_stats = nullptr, *d_ws = nullptr;
-  hipError_t e;
-  const uint64_t* off_src = offsets;  // relative to the first read of the batch (as walt_map_se_batch)
-  std::vector<uint64_t> rel;
-  if (offsets[0] != 0) {
-    rel.resize((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
-    off_src = rel.data();
-  }
-  const size_t ws_bytes = walt_se_rpbat_workspace_bytes(n, max_len);
-  if ((e = host_api_buffer(idx, 0, nbytes + 16, &d_bases)) != hipSuccess ||
-      (e = host_api_buffer(idx, 1, ((size_t)n + 1) * sizeof(uint64_t), &d_off)) != hipSuccess ||
-      (e = host_api_buffer(idx, 2, (size_t)n * sizeof(walt_best_match), &d_out)) != hipSuccess ||
-      (e = host_api_buffer(idx, 3, sizeof(walt_batch_stats), &d_stats)) != hipSuccess ||
-      (e = host_api_buffer(idx, 4, ws_bytes, &d_ws)) != hipSuccess ||
-      (e = host_api_buffer(idx, 5, n, &d_conv)) != hipSuccess)
-    return fail(WALT_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-  if ((e = hipMemcpyAsync(d_bases, bases + offsets[0], nbytes, hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_off, off_src, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, nullptr)) != hipSuccess ||
-      (e = hipMemsetAsync(d_stats, 0, sizeof(walt_batch_stats), nullptr)) != hipSuccess)
-    return fail(WALT_EHIP, std::string("upload failed: ") + hipGetErrorString(e));
-  int rc = map_se_rpbat_device(idx, d_bases, d_off, n, max_len, max_mismatches, b, d_out, d_conv, d_stats, d_ws,
-                               ws_bytes, nullptr, true);
-  if (!rc) rc = check_read_errors(d_ws, nullptr);
-  if (!rc) {
-    if ((e = hipMemcpy(out, d_out, (size_t)n * sizeof(walt_best_match), hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(conv, d_conv, n, hipMemcpyDeviceToHost)) != hipSuccess)
-      rc = fail(WALT_EHIP, std::string("download failed: ") + hipGetErrorString(e));
-    walt_batch_stats st;
-    if (!rc && hipMemcpy(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess && stats) *stats = st;
-  }
-  return rc;
+  return se_host_call(idx, bases, offsets, n, 0, max_mismatches, b, out, conv, true, stats);
 }
 
 }  // extern "C"

@@ -424,6 +424,84 @@ int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_m
 int walt_pileup_extract_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_sites, uint64_t cap,
                                void* d_n_sites, void* d_offref, void* stream);
 
+/* ---- duplicates: PCR duplicates marked from the mapped records, and kept out of the methylation counts ---------
+ * The reference has no such mode (its users sort the mapped records and run a second program, MethPipe's
+ * duplicate-remover, before they count; Bismark users run deduplicate_bismark); the contract is defined here.  It needs
+ * the records alone -- no bases, no reference, no index: a duplicate set (walt_dedup) belongs to a device, not to an index.
+ *
+ * Keys.  A set holds 64-bit keys; each remembers the ordinal of the first record that produced it.
+ *   key(kind, conv, strand, aux, pos): bit 63 conv == 'A', bit 62 strand == '-', bits 61:60 kind, bits 59:32 aux (28 bits),
+ *   bits 31:0 genome_pos.
+ * The all-ones word is the empty slot; it is no key, because a genome_pos of 0xFFFFFFFF makes a record ineligible.
+ *
+ * Which records have a key.
+ *   Single records (walt_dedup_batch; kind 0, 1 or 2 is the caller's: 0 for single-end reads): a walt_best_match is
+ *   eligible when times == 1, genome_pos != 0xFFFFFFFF and its conversion is 'T' or 'A'; its key has aux = 0.  genome_pos is
+ *   the 5' end of the read in its own strand's coordinates, so two reads are duplicates when 5' end, strand and conversion
+ *   agree, whatever their lengths (Bismark's single-end rule).
+ *   Pairs (walt_dedup_pairs_batch over walt_pair_result; conv[2n] as walt_map_pe_rpbat_batch writes it, or conv == NULL:
+ *   `conversion` for mate 1 and the other letter for mate 2).  best_times == 1: the pair has ONE key -- kind 3,
+ *   pos = m1.genome_pos, strand = m1.strand, conv = mate 1's, aux = (uint32_t)frag_len & 0x0FFFFFFF -- and both mates share
+ *   its verdict (eligible when m1.genome_pos != 0xFFFFFFFF and mate 1's conversion is 'T' or 'A').  best_times != 1: each
+ *   mate with times == 1 is a single record of kind 1 (mate 1) or 2 (mate 2) under its own conversion.  aux is the low 28
+ *   bits of the two's-complement length: lengths in [-2^27, 2^27) have distinct keys, lengths of 2^27 and more alias (2^27
+ *   with -2^27, 2^28 + x with x).  bin/walt -D refuses -L of 2^27 and more, so no two lengths it can report do.
+ *
+ * Verdict.  The set numbers every record it is fed 0, 1, 2, ... across calls (a pair takes one number; both of its mate
+ * keys use it).  An eligible record is a duplicate exactly when an eligible record with the same key and a smaller number
+ * was fed since the last clear: the first one fed wins, within a call the lowest index.  dup[i] (pairs: dup[2i + k] for
+ * mate k + 1) is 1 for a duplicate and 0 for everything else, ineligible records included.  The verdicts are a pure
+ * function of the sequence of records: they do not depend on how the sequence is cut into calls, on the table's capacity or
+ * growth, on the grid or on the hash.
+ *
+ * The table: open addressing, two planes of 8-byte words (16 bytes per slot), a power of two of slots, load at most 1/2 --
+ * 32 bytes of device memory per key at the limit.  walt_dedup_create: initial_slots is rounded up to a power of two, at
+ * least 64; 0 picks a default sized for about one batch of 10 M records (2^25 slots, 512 MiB); small values are the test
+ * hook for growth.  WALT_EHIP when there is no device.  walt_dedup_reserve(n_more) is synchronous: it waits for the
+ * device, reads the number of keys and doubles the table until keys + n_more <= slots / 2 (old and new table exist side
+ * by side meanwhile: 1.5 x the new size); WALT_ENOMEM names the bytes and leaves the set usable and unchanged.
+ * walt_dedup_count waits too: *keys = distinct keys held, *fed = records numbered since the last clear (either may be
+ * NULL).  walt_dedup_clear forgets everything and keeps the capacity.  walt_dedup_device_bytes = 16 x slots + 16.
+ *
+ * Batch calls.  Strides, conv == NULL and the alignment rules as in walt_meth_call_batch (a record stride of at least 16 and a
+ * multiple of 4; conv stride at least 1; `conversion` 'T' or 'A' when conv is NULL; WALT_EINVAL otherwise).  A conv BYTE
+ * that is neither letter makes its record ineligible, in both forms.  Host forms reserve for themselves (n keys; 2n for
+ * pairs) and wait for the result.  Device forms: pointers are HBM addresses on the set's device (d_records 4-byte,
+ * d_pairs 16-byte aligned), asynchronous on `stream` -- insert kernel, then mark kernel -- and unable to grow the table:
+ * when the keys at the last count plus everything enqueued since plus this call could exceed slots / 2 they return
+ * WALT_EINVAL telling the caller to reserve first, and enqueue nothing.  A probe that runs through the whole table (never
+ * under that limit) sets an error word that the next synchronous call returns as WALT_EHIP; the kernel ends, it never
+ * spins.  One call at a time per set: the ordinals and the mark-after-insert order are the set's.
+ *
+ * Skipping duplicates.  walt_meth_pileup_batch_skip[_device] are walt_meth_pileup_batch[_device] plus skip: a record whose
+ * byte skip[i * skip_stride] is non-zero adds nothing to the pile-up and nothing to stats (stats.reads included); its
+ * calls and counts are written as before.  skip == NULL: no record is skipped.  skip_stride 1 for walt_dedup_batch's dup;
+ * 2 with a base of dup or dup + 1 for one mate of walt_dedup_pairs_batch's.  Here the pile-up may be NULL: the calls are
+ * made and nothing is piled up. */
+typedef struct walt_dedup walt_dedup;
+int walt_dedup_create(int device, uint64_t initial_slots, walt_dedup** out);
+void walt_dedup_destroy(walt_dedup* dd);
+int walt_dedup_clear(walt_dedup* dd);
+int walt_dedup_reserve(walt_dedup* dd, uint64_t n_more);
+int walt_dedup_count(walt_dedup* dd, uint64_t* keys, uint64_t* fed);
+uint64_t walt_dedup_device_bytes(const walt_dedup* dd);
+int walt_dedup_batch(walt_dedup* dd, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                     int conversion, int kind, uint32_t n, uint8_t* dup);
+int walt_dedup_pairs_batch(walt_dedup* dd, const walt_pair_result* pairs, const uint8_t* conv, int conversion, uint32_t n,
+                           uint8_t* dup /*[2n]*/);
+int walt_dedup_batch_device(walt_dedup* dd, const void* d_records, size_t record_stride, const void* d_conv,
+                            size_t conv_stride, int conversion, int kind, uint32_t n, void* d_dup, void* stream);
+int walt_dedup_pairs_batch_device(walt_dedup* dd, const void* d_pairs, const void* d_conv, int conversion, uint32_t n,
+                                  void* d_dup /*[2n]*/, void* stream);
+int walt_meth_pileup_batch_skip(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride);
+int walt_meth_pileup_batch_skip_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -442,6 +442,114 @@ def run_soak_pileup(seeds, pattern=3):
         pattern, len(seeds), reads_total, sites_total)
 
 
+def run_soak_dedup(seeds, pattern=3):
+    """Duplicate marking (walt_dedup_*, walt_meth_pileup_batch_skip) on the genomes of `seeds`: single-end reads of either
+    conversion and pairs of either orientation, sampled WITH replacement so that about a third are copies of earlier
+    ones; mapped on the GPU (random-PBAT calls), fed to a set that starts at 64 slots in calls cut at random points, and
+    the verdicts compared with the restatement in tests/test_dedup_cpu.py; the pile-up of the records that are no
+    duplicates compared with the restatement in tests/test_gpu_pileup.py.  Returns the summary line, raises SoakMismatch
+    at the first difference (tests/test_gpu_dedup.py)."""
+    import refio
+    import walt_amd
+    import test_dedup_cpu as rule_of
+    import test_gpu_meth as meth_of
+    import test_gpu_pileup as pile_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 160)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    reads_total = dups_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 15485863 + 5)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_dedup_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                R = meth_of.reference_bases(db)
+                lengths = [lo + 2, 47, 60, 100, 100, min(150, hi)]
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                dd = pile = None
+                try:
+                    dd = walt_amd.Dedup(initial_slots=64, pattern=pattern)
+                    pile = idx.pileup()
+                    rule = rule_of.DupRule()
+                    acc = None
+                    # single-end: 400 distinct reads of either conversion, 600 drawn from them with replacement
+                    distinct = sample(rng, seqs, 200, "CT", lengths, refio) + sample(rng, seqs, 200, "GA", lengths, refio)
+                    reads = [rng.choice(distinct) for _ in range(600)]
+                    bases, offs = walt_amd.pack_reads(reads)
+                    recs, conv, _ = idx.map_se_rpbat_batch(bases, offs)
+                    got, at = [], 0
+                    while at < len(reads):
+                        n = rng.choice([1, 7, 64, 65, 300])
+                        got.append(dd.add_batch(recs[at:at + n], conv[at:at + n]))
+                        at += n
+                    got = np.concatenate(got)
+                    want = rule_of.expect_single(rule, recs, conv)
+                    if got.tolist() != want.tolist():
+                        raise SoakMismatch("MISMATCH dedup seed %d: single-end verdicts differ at %s" % (
+                            seed, np.nonzero(got != want)[0][:5].tolist()))
+                    pile.add_batch(bases, offs, recs, conv, skip=got, want_calls=False, want_counts=False, want_stats=False)
+                    kept = recs.copy()
+                    kept["times"][got != 0] = 0
+                    acc = pile_of.expected_counts(R, db.start_index, reads, kept, conv, into=acc)
+                    reads_total += len(reads)
+                    dups_total += int(got.sum())
+                    # pairs: the same set goes on (lone mates have kinds of their own)
+                    d1, d2 = sample_pairs(rng, seqs, 300, lengths, 400, refio)
+                    pick = [rng.randrange(len(d1)) for _ in range(450)]
+                    r1, r2 = [d1[i] for i in pick], [d2[i] for i in pick]
+                    b1, o1 = walt_amd.pack_reads(r1)
+                    b2, o2 = walt_amd.pack_reads(r2)
+                    res, pconv, _ = idx.map_pe_rpbat_batch(b1, o1, b2, o2, frag_range=400 + hi)
+                    gotp, at = [], 0
+                    while at < len(r1):
+                        n = rng.choice([1, 7, 64, 200])
+                        gotp.append(dd.add_pairs(res[at:at + n], pconv[at:at + n]))
+                        at += n
+                    gotp = np.concatenate(gotp)
+                    wantp = rule_of.expect_pairs(rule, res, pconv)
+                    if gotp.tolist() != wantp.tolist():
+                        raise SoakMismatch("MISMATCH dedup seed %d: paired-end verdicts differ at %s" % (
+                            seed, np.nonzero((gotp != wantp).any(axis=1))[0][:5].tolist()))
+                    if dd.count() != (len(rule.first), rule.fed):
+                        raise SoakMismatch("MISMATCH dedup seed %d: count %s against %s" % (seed, dd.count(), (len(rule.first), rule.fed)))
+                    for k, (rd, b, o) in enumerate(((r1, b1, o1), (r2, b2, o2))):
+                        m = res["m%d" % (k + 1)]
+                        pile.add_batch(b, o, m, pconv[:, k], skip=gotp[:, k], want_calls=False, want_counts=False, want_stats=False)
+                        kept = np.ascontiguousarray(m).copy()
+                        kept["times"][gotp[:, k] != 0] = 0
+                        acc = pile_of.expected_counts(R, db.start_index, rd, kept, pconv[:, k], into=acc)
+                    reads_total += 2 * len(r1)
+                    dups_total += int(gotp.sum())
+                    try:
+                        pile_of.assert_table(pile.extract(), R[0], db.start_index, acc[0], acc[1], "seed %d" % seed)
+                    except AssertionError as e:
+                        raise SoakMismatch("MISMATCH dedup seed %d: %s" % (seed, e))
+                finally:
+                    if pile is not None:
+                        pile.close()
+                    if dd is not None:
+                        dd.close()
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    if dups_total * 5 < reads_total:
+        raise SoakMismatch("soak too thin: %d duplicates among %d reads" % (dups_total, reads_total))
+    return "soak ok: duplicates, pattern %d, %d genomes, %d reads, %d duplicates identical to the restatement" % (
+        pattern, len(seeds), reads_total, dups_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

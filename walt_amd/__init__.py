@@ -214,6 +214,22 @@ def lib(pattern=None):
     L.walt_meth_pileup_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp]
     L.walt_pileup_extract.argtypes = [vp, u32, u32, vp, u64, c.POINTER(u64), vp]
     L.walt_pileup_extract_device.argtypes = [vp, u32, u32, vp, u64, vp, vp, vp]
+    L.walt_dedup_create.argtypes = [ci, u64, c.POINTER(vp)]
+    L.walt_dedup_destroy.argtypes = [vp]
+    L.walt_dedup_destroy.restype = None
+    L.walt_dedup_clear.argtypes = [vp]
+    L.walt_dedup_reserve.argtypes = [vp, u64]
+    L.walt_dedup_count.argtypes = [vp, c.POINTER(u64), c.POINTER(u64)]
+    L.walt_dedup_device_bytes.argtypes = [vp]
+    L.walt_dedup_device_bytes.restype = u64
+    L.walt_dedup_batch.argtypes = [vp, vp, c.c_size_t, vp, c.c_size_t, ci, ci, u32, vp]
+    L.walt_dedup_pairs_batch.argtypes = [vp, vp, vp, ci, u32, vp]
+    L.walt_dedup_batch_device.argtypes = [vp, vp, c.c_size_t, vp, c.c_size_t, ci, ci, u32, vp, vp]
+    L.walt_dedup_pairs_batch_device.argtypes = [vp, vp, vp, ci, u32, vp, vp]
+    L.walt_meth_pileup_batch_skip.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                              c.c_size_t]
+    L.walt_meth_pileup_batch_skip_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                     vp, c.c_size_t, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -518,21 +534,24 @@ class Index:
         self._ck(self._L.walt_index_enable_reference(self._h))
 
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                        stats=None, want_stats=True):
+                        stats=None, want_stats=True, skip=None):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
         strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
         meth_counts_dtype[n], stats meth_stats_dtype scalar array); an output that is not wanted is None.  stats: an
-        existing 1-element meth_stats_dtype array to accumulate into."""
-        return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats)
+        existing 1-element meth_stats_dtype array to accumulate into.  skip: a uint8 array with one element per read
+        (any stride, e.g. dup[:, 0] of Dedup.add_pairs): a read with a non-zero byte is called but left out of stats."""
+        return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
+                                skip)
 
     def pileup(self):
         """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True):
-        """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too."""
+                    stats=None, want_stats=True, skip=None):
+        """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
+        records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -565,7 +584,15 @@ class Index:
         bases_ptr = bases.ctypes.data
         tail = (bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
                 conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats))
-        if pile is None:
+        if skip is not None:
+            skip_arr = np.asarray(skip)
+            if skip_arr.dtype != np.uint8 or skip_arr.ndim != 1 or skip_arr.shape[0] != n:
+                raise ValueError("skip: a 1-d uint8 array with one element per read")
+            skip_stride = skip_arr.strides[0] if n > 1 else 1
+            if skip_stride <= 0:
+                skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+            self._ck(self._L.walt_meth_pileup_batch_skip(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride))
+        elif pile is None:
             self._ck(self._L.walt_meth_call_batch(self._h, *tail))
         else:
             self._ck(self._L.walt_meth_pileup_batch(self._h, pile, *tail))
@@ -673,14 +700,20 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True):
+                  want_stats=True, skip=None):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats)
+                                       want_stats, skip)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
-                         conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0):
+                         conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
+                         skip_stride=1):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous."""
+        if d_skip is not None:
+            self._index._ck(self._L.walt_meth_pileup_batch_skip_device(
+                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), stream))
+            return
         self._index._ck(self._L.walt_meth_pileup_batch_device(
             self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
             ord(conversion), d_call_len, d_calls, d_counts, d_stats, stream))
@@ -719,6 +752,103 @@ class Pileup:
     def close(self):
         if self._h:
             self._L.walt_pileup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Dedup:
+    """A duplicate set on one device (include/walt_amd.h, "duplicates"): PCR duplicates marked from mapped records alone.
+    The set numbers the records it is fed; a record is a duplicate when an earlier one had the same key."""
+
+    def __init__(self, device=0, initial_slots=0, pattern=None):
+        self._L = lib(pattern)
+        h = ctypes.c_void_p()
+        self._h = None
+        self._ck(self._L.walt_dedup_create(int(device), int(initial_slots), ctypes.byref(h)))
+        self._h = h
+
+    def _ck(self, rc):
+        if rc != WALT_OK:
+            raise WaltError(rc, self._L.walt_last_error().decode("utf-8", "replace"))
+
+    def add_batch(self, records, conv="T", kind=0):
+        """records: a best_match_dtype array or strided view (e.g. the m1 field of a pair_result_dtype array); conv: 'T' /
+        'A' for all, or a uint8 array per record (any stride).  Returns dup uint8[n]."""
+        records = np.asarray(records)
+        if records.dtype != best_match_dtype or records.ndim != 1:
+            raise ValueError("records: a 1-d best_match_dtype array (or view)")
+        n = records.shape[0]
+        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
+        if rec_stride < 0:
+            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
+        conv_arr, conv_stride, conversion = None, 0, 0
+        if isinstance(conv, (str, bytes)):
+            conversion = ord(conv)
+        else:
+            conv_arr = np.asarray(conv)
+            if conv_arr.dtype != np.uint8 or conv_arr.ndim != 1 or conv_arr.shape[0] != n:
+                raise ValueError("conv: 'T', 'A' or a 1-d uint8 array with one element per record")
+            conv_stride = conv_arr.strides[0] if n > 1 else 1
+            if conv_stride <= 0:
+                conv_arr, conv_stride = np.ascontiguousarray(conv_arr), 1
+        dup = np.zeros(n, dtype=np.uint8)
+        self._ck(self._L.walt_dedup_batch(self._h, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
+                                          conv_stride, conversion, int(kind), n, _ptr(dup)))
+        return dup
+
+    def add_pairs(self, pairs, conv="T"):
+        """pairs: a pair_result_dtype array; conv: mate 1's conversion for all ('T' / 'A'; mate 2 has the other), or a
+        uint8 array [n, 2] as map_pe_rpbat_batch returns it.  Returns dup uint8[n, 2]."""
+        pairs = np.ascontiguousarray(pairs, dtype=pair_result_dtype)
+        n = pairs.shape[0]
+        conv_arr, conversion = None, 0
+        if isinstance(conv, (str, bytes)):
+            conversion = ord(conv)
+        else:
+            conv_arr = np.ascontiguousarray(conv, dtype=np.uint8)
+            if conv_arr.shape != (n, 2):
+                raise ValueError("conv: 'T', 'A' or a uint8 array [n, 2]")
+        dup = np.zeros((n, 2), dtype=np.uint8)
+        self._ck(self._L.walt_dedup_pairs_batch(self._h, _ptr(pairs), _ptr(conv_arr), conversion, n, _ptr(dup)))
+        return dup
+
+    def add_batch_device(self, d_records, n, d_dup, record_stride=16, d_conv=None, conv_stride=1, conversion="T", kind=0,
+                         stream=0):
+        """Device-pointer form (ints are HBM addresses on the set's device); asynchronous; reserve() first."""
+        self._ck(self._L.walt_dedup_batch_device(self._h, d_records, int(record_stride), d_conv, int(conv_stride),
+                                                 ord(conversion), int(kind), int(n), d_dup, stream))
+
+    def add_pairs_device(self, d_pairs, n, d_dup, d_conv=None, conversion="T", stream=0):
+        self._ck(self._L.walt_dedup_pairs_batch_device(self._h, d_pairs, d_conv, ord(conversion), int(n), d_dup, stream))
+
+    def reserve(self, n_more):
+        self._ck(self._L.walt_dedup_reserve(self._h, int(n_more)))
+
+    def count(self):
+        """(distinct keys held, records numbered since the last clear)"""
+        keys, fed = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._L.walt_dedup_count(self._h, ctypes.byref(keys), ctypes.byref(fed)))
+        return keys.value, fed.value
+
+    def clear(self):
+        self._ck(self._L.walt_dedup_clear(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._L.walt_dedup_device_bytes(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.walt_dedup_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -52,6 +52,7 @@ struct Options {
   bool rpbat_pe = false;  // -RP: paired-end random PBAT, every pair in both orientations (walt_map_pe_rpbat_batch)
   bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
   bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
+  bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -91,6 +92,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "RP", "random-pbat-pe")) o.rpbat_pe = true;  // extension: pairs of either orientation
     else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
     else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
+    else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -118,6 +120,8 @@ static Options parse(int argc, const char** argv) {
   if (o.rpbat && o.ag) die("-R (random PBAT) maps every read under both conversions: it cannot be combined with -A");
   if (o.rpbat && o.pbat) die("-R (random PBAT) cannot be combined with -P");
   if (o.rpbat && (!o.pe1_csv.empty() || !o.pe2_csv.empty())) die("-R (random PBAT) is single-end only: it cannot be combined with -1 / -2 (use -RP)");
+  if (o.dedup && o.frag_range >= (1 << 27))
+    die("-D (duplicates) keys a pair by its fragment length in 28 bits: it cannot be combined with -L of 134217728 (2^27) or more");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -255,12 +259,13 @@ static void put_xm(Sink& f, View xm, bool flip) {
   if (flip) f.rev(xm); else f.put(xm);
 }
 static void out_single_sam(const walt_best_match& bm, View name, View seq, View score, const GenomeInfo& g,
-                           bool out_amb, bool out_unm, Sink& f, const char* tag = nullptr, View xm = View{nullptr, 0}) {
+                           bool out_amb, bool out_unm, Sink& f, const char* tag = nullptr, View xm = View{nullptr, 0},
+                           int flag_extra = 0 /* -D: 0x400 on a duplicate */) {
   uint32_t chr = chrom_id(g, bm.genome_pos);
   uint32_t start = bm.genome_pos - g.start[chr];
   if (bm.strand == '-') start = g.length[chr] - start - seq.len;
   const bool flip = bm.strand == '-';
-  int flag = (bm.times == 0 ? 0x4 : 0) + (bm.strand == '-' ? 0x10 : 0) + (bm.times >= 2 ? 0x100 : 0);
+  int flag = (bm.times == 0 ? 0x4 : 0) + (bm.strand == '-' ? 0x10 : 0) + (bm.times >= 2 ? 0x100 : 0) + flag_extra;
   if (bm.times == 0 && out_unm) {
     f.put(name); f.ch('\t'); f.i32(flag); f.lit("\t*\t0\t255\t*\t*\t0\t0\t");
     put_seq_qual(f, seq, score, flip);
@@ -374,6 +379,43 @@ static void write_methcounts(const string& out_file, PileSet& ps, const GenomeIn
             (unsigned long long)n_total, (unsigned long long)off[0], (unsigned long long)off[1]);
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
 }
+
+// ---------------------------------------------------------------- -D: PCR duplicates
+// One duplicate set per read file, on the first device of the run.  A batch is mapped by all devices first; then the
+// whole batch's records are fed to the set in input order (so the verdict depends neither on -N nor on -g); only then are
+// the methylation calls and the pile-up made, share by share, with the verdicts as their skip bytes.
+struct DupSet {
+  walt_dedup* dd = nullptr;
+  vector<uint8_t> dup;  // the current batch's verdicts: one per read, two per pair
+  uint64_t records = 0, duplicates = 0;  // eligible keys fed (reads, unique pairs, lone mates); those that were duplicates
+  void open(int device) { check(walt_dedup_create(device, 0, &dd)); }
+  void close() { if (dd) walt_dedup_destroy(dd); dd = nullptr; }
+  bool on() const { return dd != nullptr; }
+  void feed_se(const walt_best_match* res, const uint8_t* conv, int conversion, uint32_t n) {
+    dup.assign(n, 0);
+    check(walt_dedup_batch(dd, res, sizeof(walt_best_match), conv, 1, conversion, 0, n, dup.data()));
+    for (uint32_t j = 0; j < n; ++j) { records += res[j].times == 1; duplicates += dup[j]; }
+  }
+  void feed_pe(const walt_pair_result* pr, const uint8_t* conv, uint32_t n) {
+    dup.assign(2 * (size_t)n, 0);
+    check(walt_dedup_pairs_batch(dd, pr, conv, 'T', n, dup.data()));
+    for (uint32_t j = 0; j < n; ++j) {
+      if (pr[j].best_times == 1) { records += 1; duplicates += dup[2 * (size_t)j]; continue; }
+      records += (pr[j].m1.times == 1) + (pr[j].m2.times == 1);
+      duplicates += dup[2 * (size_t)j] + dup[2 * (size_t)j + 1];
+    }
+  }
+  void write_stats(const string& out_file) const {
+    char num[160];
+    if (records) snprintf(num, sizeof num, "records: %llu\nduplicates: %llu\nduplication rate: %.6f\n", (unsigned long long)records,
+                          (unsigned long long)duplicates, (double)duplicates / (double)records);
+    else snprintf(num, sizeof num, "records: 0\nduplicates: 0\nduplication rate: NA\n");
+    OutFile f;
+    if (!f.open_append(out_file + ".dupstats")) die("cannot open input file " + out_file + ".dupstats");
+    f.write(num, strlen(num));
+    f.close();
+  }
+};
 
 static double g_t_main = 0;  // start of main (timeline under -v)
 static int host_threads(const Options& o) { return o.threads > 0 ? o.threads : hostio::effective_cpus(); }
@@ -527,6 +569,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
   dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));
   PileSet pile;
   if (o.methcounts) pile.open(dev.idx);
+  DupSet dups;
+  if (o.dedup) dups.open(dev.ids[0]);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   OutFile fout;
@@ -578,21 +622,40 @@ static void process_se(const Options& o, const string& reads_file, const string&
     memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
     if (o.meth && o.sam && calls.size() < b.offsets[n]) calls.resize(b.offsets[n]);
     if ((o.meth || o.methcounts) && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
-    dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
+    auto map_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
-      int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
-                       : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
+      const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
+                             : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
       short_of[d] = bs.too_short;
-      if (rc == WALT_OK && o.methcounts)  // on the device that mapped the share; with -M both in one call
+      return rc;
+    };
+    auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
+      int rc = WALT_OK;
+      if (dups.on() && (o.meth || o.methcounts))  // -D: the same calls, duplicates neither piled up nor summed
+        rc = walt_meth_pileup_batch_skip(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+                                         sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
+                                         clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
+                                         o.meth ? &meth_of[d] : nullptr, dups.dup.data() + lo, 1);
+      else if (o.methcounts)  // on the device that mapped the share; with -M both in one call
         rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
                                     o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
                                     o.meth && o.sam ? calls.data() : nullptr, nullptr, o.meth ? &meth_of[d] : nullptr);
-      else if (rc == WALT_OK && o.meth)  // on the device that mapped the share
+      else if (o.meth)  // on the device that mapped the share
         rc = walt_meth_call_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
                                   o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
                                   o.sam ? calls.data() : nullptr, nullptr, &meth_of[d]);
       return rc;
-    });
+    };
+    if (!dups.on()) {
+      dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
+        const int rc = map_share(d, lo, hi);
+        return rc == WALT_OK ? meth_share(d, lo, hi) : rc;
+      });
+    } else {  // -D: every share mapped, then the whole batch through the set in input order, then the calls
+      dev.for_each_share(n, map_share);
+      dups.feed_se(res, o.rpbat ? conv.data() : nullptr, o.ag ? 'A' : 'T', n);
+      if (o.meth || o.methcounts) dev.for_each_share(n, meth_share);
+    }
     for (uint64_t v : short_of) st.too_short += (uint32_t)v;
     for (const walt_meth_stats& m : meth_of) add_meth(meth_total, m);
     t_map += now_s() - t0;
@@ -610,11 +673,12 @@ static void process_se(const Options& o, const string& reads_file, const string&
         c.update(res[j].times);
         // -R: a record of the G->A conversion is written as a -A run writes it (MR), or tagged (SAM)
         const bool ag = o.rpbat ? conv[j] == 'A' : o.ag;
-        if (!o.sam) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
-                                       s[kMain], s[kAmb1], s[kUnm1]);
+        const bool dup = dups.on() && dups.dup[j];  // (a duplicate has times == 1: its only line is the main file's)
+        if (!o.sam) { if (!dup) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
+                                                   s[kMain], s[kAmb1], s[kUnm1]); }
         else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain],
                             o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
-                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0});
+                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0}, dup ? 0x400 : 0);
       }
       acc[t] = c;
     }
@@ -653,6 +717,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     write_methstats(out_file, ms);
   }
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   const double t_c0 = now_s();
   dev.close();
   if (o.verbose)
@@ -804,6 +869,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   dev.open(o, WALT_STRANDS_ALL | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
   PileSet pile;  // -MC: both mates into the same pile-up
   if (o.methcounts) pile.open(dev.idx);
+  DupSet dups;
+  if (o.dedup) dups.open(dev.ids[0]);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   hostio::FastqReader rd[2];
@@ -870,15 +937,26 @@ static void process_pe(const Options& o, const string& file1, const string& file
       if (o.meth && o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
       if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
     }
-    dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
+    auto map_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs[2];
-      int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
+      const int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
                                                   hi - lo, o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo,
                                                   conv.data() + 2 * (size_t)lo, bs)
                         : walt_map_pe_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo, hi - lo,
                                             o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
       short1[d] = bs[0].too_short;
       short2[d] = bs[1].too_short;
+      return rc;
+    };
+    auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
+      int rc = WALT_OK;
+      for (int k = 0; k < 2 && rc == WALT_OK && dups.on() && (o.meth || o.methcounts); ++k)  // -D: duplicates neither piled up nor summed
+        rc = walt_meth_pileup_batch_skip(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
+                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
+                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
+                                         dups.dup.data() + 2 * (size_t)lo + k, 2);
+      if (dups.on()) return rc;
       for (int k = 0; k < 2 && rc == WALT_OK && o.methcounts; ++k)  // both mates into the device's pile-up; with -M in one call
         rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
                                     sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
@@ -890,7 +968,17 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                   clip[k].empty() ? nullptr : clip[k].data() + lo, o.sam ? calls[k].data() : nullptr, nullptr,
                                   &meth_of[2 * d + k]);
       return rc;
-    });
+    };
+    if (!dups.on()) {
+      dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
+        const int rc = map_share(d, lo, hi);
+        return rc == WALT_OK ? meth_share(d, lo, hi) : rc;
+      });
+    } else {  // -D: every share mapped, then the whole batch's pairs through the set in input order, then the calls
+      dev.for_each_share(n, map_share);
+      dups.feed_pe(pr, rp ? conv.data() : nullptr, n);
+      if (o.meth || o.methcounts) dev.for_each_share(n, meth_share);
+    }
     for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
     for (size_t d = 0; d < dev.size(); ++d) { st1.too_short += (uint32_t)short1[d]; st2.too_short += (uint32_t)short2[d]; }
     t_map += now_s() - t0;
@@ -910,14 +998,16 @@ static void process_pe(const Options& o, const string& file1, const string& file
         bool is_paired = false;
         int len = 0;
         const bool ag1 = rp && conv[2 * (size_t)j] == 'A', ag2 = !rp || conv[2 * (size_t)j + 1] == 'A';
+        // -D: a duplicate's MR line is not written (the one fragment line of a duplicate pair), its SAM lines get 0x400
+        const bool dup1 = dups.on() && dups.dup[2 * (size_t)j], dup2 = dups.on() && dups.dup[2 * (size_t)j + 1];
         if (p.best_times == 1) {
           a.unique_pairs++;
           walt_candidate r1 = {p.m1.genome_pos, p.m1.strand, {0, 0, 0}, p.m1.mismatch};
           walt_candidate r2 = {p.m2.genome_pos, p.m2.strand, {0, 0, 0}, p.m2.mismatch};
           if (ag1)  // -RP rule 3: the fragment of the mate-exchanged orientation, written from the T-rich mate 2 as -P writes it
-            len = put_fragment(r2, r1, o.frag_range, g, name, q2, k2, q1, k1, o.sam, s[kMain]);
+            len = put_fragment(r2, r1, o.frag_range, g, name, q2, k2, q1, k1, o.sam || dup1, s[kMain]);
           else
-            len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam, s[kMain]);
+            len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam || dup1, s[kMain]);
           a.frag_count[len]++;
           if (o.sam) { is_paired = true; bm1 = p.m1; bm2 = p.m2; }
         } else {
@@ -926,16 +1016,18 @@ static void process_pe(const Options& o, const string& file1, const string& file
           a.st1.update(bm1.times);
           a.st2.update(bm2.times);
           if (!o.sam && !pbat) {  // (-RP: each mate by the writer of its conversion)
-            out_single_results(bm1, name, q1, k1, g, ag1, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
-            out_single_results(bm2, name, q2, k2, g, ag2, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
+            if (!dup1) out_single_results(bm1, name, q1, k1, g, ag1, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
+            if (!dup2) out_single_results(bm2, name, q2, k2, g, ag2, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
           } else if (!o.sam) {  // the user's mate 1 sits in slot 1
-            out_single_results(bm2, name, q2, k2, g, true, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
-            out_single_results(bm1, name, q1, k1, g, false, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
+            if (!dup2) out_single_results(bm2, name, q2, k2, g, true, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
+            if (!dup1) out_single_results(bm1, name, q1, k1, g, false, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
           }
         }
         if (o.sam) {
           int fl1 = sam_flag(is_paired, bm1.times == 0, bm2.times == 0, bm1.strand == '-', bm2.strand == '-', !pbat, bm1.times >= 2);
           int fl2 = sam_flag(is_paired, bm2.times == 0, bm1.times == 0, bm2.strand == '-', bm1.strand == '-', pbat, bm2.times >= 2);
+          fl1 += dup1 ? 0x400 : 0;
+          fl2 += dup2 ? 0x400 : 0;
           out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain],
                          rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
                          o.meth ? View{calls[0].data() + bt[0].offsets[j], q1.len} : View{nullptr, 0},
@@ -997,6 +1089,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     write_methstats(out_file, ms);
   }
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   dev.close();
   if (o.verbose)
     fprintf(stderr, "[walt_amd: %d host threads, %zu GPU(s); index %.2f s, ingest not hidden behind the previous batch %.2f s, map %.2f s, "
@@ -1008,7 +1101,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1026,6 +1119,7 @@ int main(int argc, const char** argv) {
     for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
     if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
     if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
+    if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");
     size_t k = 0;

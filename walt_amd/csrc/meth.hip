@@ -164,6 +164,8 @@ struct MethArgs {
   unsigned long long* counts;  // null: not wanted (two words per read: walt_meth_counts)
   unsigned long long* shards;  // null: no batch totals
   uint32_t* pile[2];           // the pile-up's counters by forward position: methylated, unmethylated (k_meth_pile* only)
+  const uint8_t* skip;         // null: none; else a record with a non-zero byte at skip[r * skip_stride] is not counted
+  uint64_t skip_stride;
 };
 
 // One call of the pile-up: a 32-bit add whose result nobody reads (no value comes back from the memory side).
@@ -221,6 +223,8 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     // unmapped, made up (a position outside the genome, an unknown conversion) or empty: no call anywhere
     const bool valid = times != 0 && pos < a.genome_len && (cv == 'T' || cv == 'A');
     const bool mapped = valid && limit != 0;
+    // counted: piled up and summed into the batch totals (a duplicate, include/walt_amd.h "duplicates", is called but not counted)
+    const bool counted = times == 1 && !(a.skip && a.skip[r * a.skip_stride]);
     uint32_t c_lo = 0, c_hi = 0;
     if (mapped) chrom_bounds(s_start, a.start_index, tab, pos, c_lo, c_hi);
     const uint32_t ga = cv == 'A' ? 1u : 0u;
@@ -242,7 +246,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
                             batch_bytes - off - done, out, meth, unmeth, cm, cu);
             if (cb) meth_store_slice(cb + done, total, i0, out);
           }
-          if (times == 1) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
+          if (counted) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
         }
       }
     } else if (end > off && (mapped || a.calls)) {
@@ -260,7 +264,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
             uint32_t cm, cu;
             meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
                             batch_bytes - off - done, out, meth, unmeth, cm, cu);
-            if (times == 1)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
+            if (counted)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
               pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
                          [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
           } else {
@@ -279,7 +283,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     }
     if (sub == 0) {
       if (a.counts) { a.counts[2 * r] = meth; a.counts[2 * r + 1] = unmeth; }
-      if (times == 1 && valid) {
+      if (counted && valid) {
         tot[0] += 1;
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) {
@@ -344,7 +348,8 @@ static int pile_check(const walt_index* idx, const walt_pileup* p, const char* w
 
 static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, const void* d_records,
                        size_t rec_stride, const void* d_conv, size_t conv_stride, int conversion, const void* d_call_len,
-                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream, walt_pileup* pile = nullptr) {
+                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream, walt_pileup* pile = nullptr,
+                       const void* d_skip = nullptr, size_t skip_stride = 0) {
   if (n == 0 || (!d_calls && !d_counts && !d_stats && !pile)) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   MethArgs a;
@@ -367,6 +372,8 @@ static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offse
   a.shards = d_stats ? idx->meth_shards : nullptr;
   a.pile[0] = pile ? pile->plane[0] : nullptr;
   a.pile[1] = pile ? pile->plane[1] : nullptr;
+  a.skip = static_cast<const uint8_t*>(d_skip);
+  a.skip_stride = skip_stride;
   const uint64_t want = ((uint64_t)n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
   hipLaunchKernelGGL(!pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile, dim3(grid), dim3(kBlock), 0,
@@ -398,24 +405,26 @@ namespace walt {
 static int meth_batch_device(const char* who, walt_index* idx, walt_pileup* pile, const void* d_bases, const void* d_offsets,
                              uint32_t n, const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                              int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
-                             void* stream) {
+                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0) {
   int rc = meth_args_check(idx, who, record_stride, d_conv, conv_stride, conversion);
   if (rc) return rc;
+  if (d_skip && skip_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": skip stride 0 is smaller than its element (1)");
   if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
     return fail(WALT_EINVAL, std::string(who) + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
   return meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
-                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile);
+                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride);
 }
 
 // the two host forms (pile null: walt_meth_call_batch)
 static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile, const char* bases, const uint64_t* offsets,
                            uint32_t n, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
                            int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
-                           walt_meth_stats* stats) {
+                           walt_meth_stats* stats, const uint8_t* skip = nullptr, size_t skip_stride = 0) {
   const std::string who(who_c);
   int rc = meth_args_check(idx, who_c, record_stride, conv, conv_stride, conversion);
   if (rc) return rc;
+  if (skip && skip_stride < 1) return fail(WALT_EINVAL, who + ": skip stride 0 is smaller than its element (1)");
   if (n == 0) return WALT_OK;
   if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument");
   for (uint32_t i = 0; i < n; ++i) {
@@ -436,6 +445,11 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
     cv.resize(n);
     for (uint32_t i = 0; i < n; ++i) cv[i] = conv[(size_t)i * conv_stride];
   }
+  std::vector<uint8_t> sk;
+  if (skip) {
+    sk.resize(n);
+    for (uint32_t i = 0; i < n; ++i) sk[i] = skip[(size_t)i * skip_stride];
+  }
   std::vector<uint64_t> rel((size_t)n + 1);
   for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
   struct Scoped {
@@ -444,10 +458,11 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
     int get(size_t bytes) {
       return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (methylation calls)");
     }
-  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats;
+  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip;
   if ((rc = d_bases.get(nbytes + 16)) || (rc = d_off.get(((size_t)n + 1) * 8)) || (rc = d_rec.get((size_t)n * 16))) return rc;
   if (conv && (rc = d_conv.get(n))) return rc;
   if (call_len && (rc = d_len.get((size_t)n * 4))) return rc;
+  if (skip && (rc = d_skip.get(n))) return rc;
   if (calls && (rc = d_calls.get(nbytes + 16))) return rc;
   if (counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts)))) return rc;
   if (stats && (rc = d_stats.get(sizeof(walt_meth_stats)))) return rc;
@@ -456,9 +471,10 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
   WALT_HIP(hipMemcpy(d_rec.p, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
   if (conv) WALT_HIP(hipMemcpy(d_conv.p, cv.data(), n, hipMemcpyHostToDevice));
   if (call_len) WALT_HIP(hipMemcpy(d_len.p, call_len, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (skip) WALT_HIP(hipMemcpy(d_skip.p, sk.data(), n, hipMemcpyHostToDevice));
   if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
   rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
-                   d_stats.p, nullptr, pile);
+                   d_stats.p, nullptr, pile, d_skip.p, 1);
   if (rc) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
@@ -509,6 +525,27 @@ int walt_meth_pileup_batch(walt_index* idx, walt_pileup* p, const char* bases, c
   if (rc) return rc;
   return meth_batch_host("walt_meth_pileup_batch", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
                          conversion, call_len, calls, counts, stats);
+}
+
+// the pile-up forms plus skip (include/walt_amd.h, "duplicates"); here the pile-up may be null: calls only
+int walt_meth_pileup_batch_skip_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, void* stream) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_skip_device: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_skip_device");
+  return meth_batch_device("walt_meth_pileup_batch_skip_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
+                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride);
+}
+
+int walt_meth_pileup_batch_skip(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_skip: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_skip");
+  return meth_batch_host("walt_meth_pileup_batch_skip", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
+                         conversion, call_len, calls, counts, stats, skip, skip_stride);
 }
 
 }  // extern "C"

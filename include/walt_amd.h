@@ -362,7 +362,8 @@ int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void
  * record.  Only records with times == 1 are piled up: the set walt_meth_stats sums.  A record with times >= 2 adds
  * nothing (its calls string is still written), and neither does one that gets no call above: genome_pos outside the
  * genome, a conversion that is neither 'T' nor 'A', a read longer than 1024 bases.  call_len bounds the called
- * positions as there.  Overlapping mates of a pair are both counted, as walt_meth_stats counts them.
+ * positions as there.  Overlapping mates of a pair are both counted, as walt_meth_stats counts them, unless the caller
+ * passes the overlap interval (-NO; "overlap of a pair" below).
  *
  * Where a call lands.  With [lo, hi) the chromosome that holds genome_pos and q = genome_pos + i, the forward position
  * is f = q for a '+' record and f = lo + hi - 1 - q for a '-' record (both strands share the chromosome starts).  The
@@ -501,6 +502,56 @@ int walt_meth_pileup_batch_skip_device(walt_index* idx, walt_pileup* p, const vo
                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                        const void* d_skip, size_t skip_stride, void* stream);
+
+/* ---- overlap of a pair: a base that both mates of a unique proper pair cover is called once ------------------------
+ * The reference has no such mode.  When the fragment is shorter than the two reads together, both mates sequence the same
+ * bases of one molecule; counting them twice doubles that molecule's weight.  Here mate 1 keeps its calls and the part of
+ * mate 2 that lies on mate 1's called span gets none (Bismark's --no_overlap rule).  The contract is defined here.
+ *
+ * For one walt_pair_result, in forward positions as the pile-up defines them: with [lo, hi) the chromosome that holds
+ * genome_pos, strand position q has f(q) = q on a '+' record and f(q) = lo + hi - 1 - q on a '-' record.  len1, len2 are
+ * the mates' lengths (differences of their offsets), p1, p2 their genome_pos, call_len1 / call_len2 as in the
+ * methylation calls (NULL: the whole read).
+ *   Mate 1's called span  S1 = { f(p1 + j) : 0 <= j < min(len1, call_len1), p1 + j < hi }: a contiguous interval
+ *   [A1, B1) of forward positions.
+ *   The excluded interval: the read positions j of mate 2 with f(p2 + j) inside [A1, B1) form one interval
+ *   [ex_lo, ex_hi) in mate 2's read coordinates, clipped to [0, len2]: [A1 - p2, B1 - p2) for a '+' mate 2,
+ *   [lo + hi - p2 - B1, lo + hi - p2 - A1) for a '-' one.  When mate 1 lies strictly inside mate 2 (it is short or
+ *   clipped) the interval lies in the middle of mate 2.
+ *   Encoding: one uint32_t per pair, ex_lo | ex_hi << 16.  It is 0 when nothing is excluded: an empty interval,
+ *   best_times != 1, a mate with times != 1, a genome_pos outside the genome, mates on different chromosomes, a read
+ *   longer than 1024 bases.
+ * The definition is in forward coordinates alone and does not ask the mates' strands to differ: hand-made records with
+ * equal strands follow the same formula.  The conversions play no part.
+ *
+ * walt_pair_overlap_batch[_device] write excl[n] from pairs[n] and the two mates' offsets (n + 1 each; only their
+ * differences are used).  They need an index for the chromosome starts -- with any strands, with or without the
+ * reference.  totals (optional, uint64_t[2], ACCUMULATED into, not cleared): [0] pairs with a non-empty interval, [1] the
+ * read positions of those intervals below min(len2, call_len2) -- the positions at which mate 2 could have been called.
+ * Host form: offsets relative to offsets[0] or not, as the caller has them; waits for the result.  Device form: pointers
+ * are HBM addresses on idx's device, asynchronous on `stream`; d_pairs, d_call_len1 / 2 and d_excl 4-byte aligned,
+ * d_offsets1 / 2 and d_totals 8-byte aligned.  WALT_EINVAL for a null index, a null array with n > 0, or a misaligned one.
+ *
+ * Effect on calling.  walt_meth_pileup_batch_excl[_device] are walt_meth_pileup_batch_skip[_device] plus excl
+ * (uint32_t[n], one word per record of the batch in the encoding above, 4-byte aligned; NULL: none).  A read position
+ * inside its record's interval is treated exactly like a position at or beyond call_len: letter '.', no count, no
+ * total, no add to the pile-up.  `reads` of walt_meth_stats is unchanged.  The pile-up may be NULL and skip may be NULL.
+ * For a pair: call mate 1 as before and mate 2 with walt_pair_overlap_batch's excl.  Every older entry point is the same
+ * call with excl == NULL and gives what it always gave. */
+int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
+                            uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl,
+                            uint64_t* totals /*[2]: pairs, bases*/);
+int walt_pair_overlap_batch_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
+                                   uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
+                                   void* stream);
+int walt_meth_pileup_batch_excl(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl);
+int walt_meth_pileup_batch_excl_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, void* stream);
 
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment

@@ -550,6 +550,95 @@ def run_soak_dedup(seeds, pattern=3):
         pattern, len(seeds), reads_total, dups_total)
 
 
+def sample_fragments(rng, seqs, n, lo, hi, refio):
+    """n bisulfite pairs cut from fragments of lo + 2 bases (shorter than one read: the mates are the whole fragment) up
+    to 2 hi + 120 (longer than two reads: no overlap): mate 1 the fragment's C->T converted start, mate 2 the reverse
+    complement of its end, about half of the C kept; a tenth of the pairs two unrelated reads."""
+    out1, out2 = [], []
+    while len(out1) < n:
+        _, g = seqs[rng.randrange(len(seqs))]
+        f_len = rng.choice([lo + 2, rng.randrange(lo + 2, hi + 1), rng.randrange(hi, 2 * hi + 1), rng.randrange(2 * hi, 2 * hi + 121)])
+        if rng.random() < 0.1:
+            out1.append(sample(rng, seqs, 1, "CT", [lo + 2, 60, 100], refio)[0])
+            out2.append(sample(rng, seqs, 1, "GA", [lo + 2, 60, 100], refio)[0])
+            continue
+        if len(g) < f_len:
+            continue
+        p = rng.randrange(0, len(g) - f_len + 1)
+        if rng.random() < 0.3:
+            p = rng.choice([0, len(g) - f_len])
+        f = g[p:p + f_len]
+        if rng.random() < 0.5:
+            f = refio.revcomp(f)
+        f = "".join("T" if (c == "C" and rng.random() < 0.5) else c for c in f)
+        l1, l2 = (min(f_len, rng.choice([lo + 2, 60, 100, hi])) for _ in range(2))
+        out1.append(f[:l1])
+        out2.append(refio.revcomp(f[-l2:]))
+    return out1, out2
+
+
+def run_soak_overlap(seeds, pattern=3):
+    """The overlap of a pair (walt_pair_overlap_batch, walt_meth_pileup_batch_excl) on the genomes of `seeds` (many of
+    them with hundreds of short chromosomes): pairs cut from fragments shorter than one read up to longer than two, some
+    with call_len on either mate, mapped on the GPU; the interval words, the totals, both mates' calls, counts and batch
+    totals and the WHOLE table of the one pile-up both mates go into compared with the brute-force restatement in
+    tests/test_gpu_overlap.py, under either shape of the adds.  Returns the summary line, raises SoakMismatch at the
+    first difference (tests/test_gpu_overlap.py)."""
+    import refio
+    import walt_amd
+    import test_gpu_meth as meth_of
+    import test_gpu_overlap as rule_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 150)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    pairs_total = overlap_total = bases_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 49979687 + 13)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_overlap_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern, many=True)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                R = meth_of.reference_bases(db)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                try:
+                    idx.set_option("pile_rows", rng.choice([0, 1]))
+                    r1, r2 = sample_fragments(rng, seqs, 400, lo, hi, refio)
+                    b1, o1 = walt_amd.pack_reads(r1)
+                    b2, o2 = walt_amd.pack_reads(r2)
+                    res, _ = idx.map_pe_batch(b1, o1, b2, o2, frag_range=2 * hi + 200)
+                    cl1 = cl2 = None
+                    if rng.random() < 0.5:
+                        cl1 = [rng.choice([len(r), len(r), len(r) // 2, 0, 1, len(r) + 3]) for r in r1]
+                    if rng.random() < 0.5:
+                        cl2 = [rng.choice([len(r), len(r), len(r) // 2, 0, 1, len(r) + 3]) for r in r2]
+                    try:
+                        want, _ = rule_of.run_pairs(idx, R, db.start_index, r1, r2, res, "T", "A", cl1, cl2, what="seed %d" % seed)
+                    except AssertionError as e:
+                        raise SoakMismatch("MISMATCH overlap seed %d: %s" % (seed, e))
+                    pairs_total += len(r1)
+                    overlap_total += want["totals"][0]
+                    bases_total += want["totals"][1]
+                finally:
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    if overlap_total * 10 < pairs_total:
+        raise SoakMismatch("soak too thin: %d overlapping pairs among %d" % (overlap_total, pairs_total))
+    return "soak ok: overlap, pattern %d, %d genomes, %d pairs, %d with an overlap (%d mate-2 bases) identical to the restatement" % (
+        pattern, len(seeds), pairs_total, overlap_total, bases_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

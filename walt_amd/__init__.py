@@ -230,6 +230,12 @@ def lib(pattern=None):
                                               c.c_size_t]
     L.walt_meth_pileup_batch_skip_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                      vp, c.c_size_t, vp]
+    L.walt_pair_overlap_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.walt_pair_overlap_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.walt_meth_pileup_batch_excl.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                              c.c_size_t, vp]
+    L.walt_meth_pileup_batch_excl_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                     vp, c.c_size_t, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -534,24 +540,59 @@ class Index:
         self._ck(self._L.walt_index_enable_reference(self._h))
 
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                        stats=None, want_stats=True, skip=None):
+                        stats=None, want_stats=True, skip=None, excl=None):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
         strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
         meth_counts_dtype[n], stats meth_stats_dtype scalar array); an output that is not wanted is None.  stats: an
         existing 1-element meth_stats_dtype array to accumulate into.  skip: a uint8 array with one element per read
-        (any stride, e.g. dup[:, 0] of Dedup.add_pairs): a read with a non-zero byte is called but left out of stats."""
+        (any stride, e.g. dup[:, 0] of Dedup.add_pairs): a read with a non-zero byte is called but left out of stats.
+        excl: a uint32 array with one word per read, as Index.pair_overlap returns it: the read positions
+        [excl & 0xFFFF, excl >> 16) get no call (walt_meth_pileup_batch_excl; only when given)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
-                                skip)
+                                skip, excl)
+
+    # -- overlap of a pair (include/walt_amd.h states the rules) --------------------------------------------------
+    def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None):
+        """Host-buffer form of walt_pair_overlap_batch.  pairs: a pair_result_dtype array; offsets1 / offsets2: the two
+        mates' offsets (n + 1 each).  Returns (excl uint32[n]: per pair the read positions of mate 2 that mate 1 already
+        calls, ex_lo | ex_hi << 16, 0 for none; totals uint64[2]: pairs with a non-empty interval, mate-2 bases
+        excluded)."""
+        pairs = np.ascontiguousarray(pairs, dtype=pair_result_dtype)
+        offsets1 = np.ascontiguousarray(offsets1, dtype=np.uint64)
+        offsets2 = np.ascontiguousarray(offsets2, dtype=np.uint64)
+        n = pairs.size
+        if pairs.ndim != 1 or offsets1.size != n + 1 or offsets2.size != n + 1:
+            raise ValueError("pairs: a 1-d pair_result_dtype array; offsets1 and offsets2: one more element than pairs")
+        cl = []
+        for a in (call_len1, call_len2):
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+            if a is not None and a.size != n:
+                raise ValueError("call_len: one element per pair")
+            cl.append(a)
+        excl = np.zeros(n, dtype=np.uint32)
+        totals = np.zeros(2, dtype=np.uint64)
+        self._ck(self._L.walt_pair_overlap_batch(self._h, _ptr(pairs) if n else None, _ptr(offsets1), _ptr(offsets2), n,
+                                                 _ptr(cl[0]) if n else None, _ptr(cl[1]) if n else None,
+                                                 _ptr(excl) if n else None, _ptr(totals)))
+        return excl, totals
+
+    def pair_overlap_device(self, d_pairs, d_offsets1, d_offsets2, n, d_excl, d_call_len1=None, d_call_len2=None,
+                            d_totals=None, stream=0):
+        """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  d_totals
+        (uint64[2]) is accumulated into, not cleared."""
+        self._ck(self._L.walt_pair_overlap_batch_device(self._h, d_pairs, d_offsets1, d_offsets2, int(n), d_call_len1,
+                                                        d_call_len2, d_excl, d_totals, stream))
 
     def pileup(self):
         """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True, skip=None):
+                    stats=None, want_stats=True, skip=None, excl=None):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
-        records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up)."""
+        records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
+        positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -584,6 +625,7 @@ class Index:
         bases_ptr = bases.ctypes.data
         tail = (bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
                 conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats))
+        skip_arr, skip_stride = None, 1
         if skip is not None:
             skip_arr = np.asarray(skip)
             if skip_arr.dtype != np.uint8 or skip_arr.ndim != 1 or skip_arr.shape[0] != n:
@@ -591,6 +633,13 @@ class Index:
             skip_stride = skip_arr.strides[0] if n > 1 else 1
             if skip_stride <= 0:
                 skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+        if excl is not None:
+            excl_arr = np.ascontiguousarray(excl, dtype=np.uint32)
+            if excl_arr.ndim != 1 or excl_arr.shape[0] != n:
+                raise ValueError("excl: a 1-d uint32 array with one word per read")
+            self._ck(self._L.walt_meth_pileup_batch_excl(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride,
+                                                         _ptr(excl_arr) if n else None))
+        elif skip is not None:
             self._ck(self._L.walt_meth_pileup_batch_skip(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride))
         elif pile is None:
             self._ck(self._L.walt_meth_call_batch(self._h, *tail))
@@ -700,15 +749,21 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True, skip=None):
+                  want_stats=True, skip=None, excl=None):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip)
+                                       want_stats, skip, excl)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
-                         skip_stride=1):
-        """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous."""
+                         skip_stride=1, d_excl=None):
+        """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
+        record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's)."""
+        if d_excl is not None:
+            self._index._ck(self._L.walt_meth_pileup_batch_excl_device(
+                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, stream))
+            return
         if d_skip is not None:
             self._index._ck(self._L.walt_meth_pileup_batch_skip_device(
                 self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),

@@ -53,6 +53,7 @@ struct Options {
   bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
   bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
+  bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -93,6 +94,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
     else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
+    else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -122,6 +124,10 @@ static Options parse(int argc, const char** argv) {
   if (o.rpbat && (!o.pe1_csv.empty() || !o.pe2_csv.empty())) die("-R (random PBAT) is single-end only: it cannot be combined with -1 / -2 (use -RP)");
   if (o.dedup && o.frag_range >= (1 << 27))
     die("-D (duplicates) keys a pair by its fragment length in 28 bits: it cannot be combined with -L of 134217728 (2^27) or more");
+  if (o.no_overlap && !o.se_csv.empty())
+    die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
+  if (o.no_overlap && !o.meth && !o.methcounts)
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC there is nothing for it to do");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -895,6 +901,11 @@ static void process_pe(const Options& o, const string& file1, const string& file
   vector<uint8_t> conv;  // -RP: the conversion of each mate's record ('T' / 'A'), two per pair
   vector<char> calls[2];     // -M -sam: the methylation calls of each slot's batch, at the offsets of its bases
   vector<uint32_t> clip[2];  // -M -C: the clip points
+  // -NO: per pair, the read positions of the user's mate 2 that its mate 1 already calls (include/walt_amd.h, "overlap of
+  // a pair"); the user's mate 1 sits in slot 1 under -P.  The totals: pairs with an overlap, mate-2 bases left uncalled
+  vector<uint32_t> excl;
+  const int over_slot = pbat ? 0 : 1;  // the slot whose calls take the interval
+  uint64_t overlap_total[2] = {0, 0};
   walt_meth_stats meth_total[2];  // per slot
   memset(meth_total, 0, sizeof meth_total);
   vector<Sink> sinks((size_t)T * kSinks);
@@ -948,8 +959,36 @@ static void process_pe(const Options& o, const string& file1, const string& file
       short2[d] = bs[1].too_short;
       return rc;
     };
+    vector<uint64_t> overlap_of;  // -NO: the totals of each device's share
+    if (o.no_overlap) {
+      overlap_of.assign(2 * dev.size(), 0);
+      if (excl.size() < n) excl.resize(n);
+    }
+    // -NO: the share's intervals from the records in user order, then both slots through the form that takes them (with
+    // no interval for the user's mate 1: the call it always got); -D's verdicts go along as skip bytes
+    auto no_overlap_share = [&](size_t d, uint32_t lo, uint32_t hi) {
+      const int u1 = 1 - over_slot;
+      vector<walt_pair_result> user;  // -P: mate 1 of the records is the user's mate 2
+      if (pbat) {
+        user.assign(pr + lo, pr + hi);
+        for (walt_pair_result& p : user) std::swap(p.m1, p.m2);
+      }
+      int rc = walt_pair_overlap_batch(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
+                                       clip[u1].empty() ? nullptr : clip[u1].data() + lo,
+                                       clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
+                                       &overlap_of[2 * d]);
+      for (int k = 0; k < 2 && rc == WALT_OK; ++k)
+        rc = walt_meth_pileup_batch_excl(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
+                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
+                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
+                                         dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
+                                         k == over_slot ? excl.data() + lo : nullptr);
+      return rc;
+    };
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       int rc = WALT_OK;
+      if (o.no_overlap) return no_overlap_share(d, lo, hi);
       for (int k = 0; k < 2 && rc == WALT_OK && dups.on() && (o.meth || o.methcounts); ++k)  // -D: duplicates neither piled up nor summed
         rc = walt_meth_pileup_batch_skip(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
@@ -980,6 +1019,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
       if (o.meth || o.methcounts) dev.for_each_share(n, meth_share);
     }
     for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
+    for (size_t d = 0; 2 * d < overlap_of.size(); ++d) { overlap_total[0] += overlap_of[2 * d]; overlap_total[1] += overlap_of[2 * d + 1]; }
     for (size_t d = 0; d < dev.size(); ++d) { st1.too_short += (uint32_t)short1[d]; st2.too_short += (uint32_t)short2[d]; }
     t_map += now_s() - t0;
     if (!more) unlock_idle.start([&, cur]() { bts[cur ^ 1][0].release(); bts[cur ^ 1][1].release(); });
@@ -1086,8 +1126,15 @@ static void process_pe(const Options& o, const string& file1, const string& file
     Sink ms;
     ms.lit("mate1\n"); put_meth_block(ms, meth_total[pbat ? 1 : 0]);
     ms.lit("mate2\n"); put_meth_block(ms, meth_total[pbat ? 0 : 1]);
+    if (o.no_overlap) {  // over all unique proper pairs, duplicates (-D) included
+      char num[96];
+      snprintf(num, sizeof num, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
+      ms.lit(num);
+    }
     write_methstats(out_file, ms);
   }
+  if (o.no_overlap && o.verbose)
+    fprintf(stderr, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   dev.close();
@@ -1101,7 +1148,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

@@ -166,6 +166,7 @@ struct MethArgs {
   uint32_t* pile[2];           // the pile-up's counters by forward position: methylated, unmethylated (k_meth_pile* only)
   const uint8_t* skip;         // null: none; else a record with a non-zero byte at skip[r * skip_stride] is not counted
   uint64_t skip_stride;
+  const uint32_t* excl;        // null: none; else excl[r] = ex_lo | ex_hi << 16, read positions of record r that get no call
 };
 
 // One call of the pile-up: a 32-bit add whose result nobody reads (no value comes back from the memory side).
@@ -199,7 +200,10 @@ __device__ __forceinline__ void pile_rows(uint32_t cm, uint32_t cu, long long q0
 // kPile: 0 the calling alone (k_meth_call), 1 / 2 the same with every call of a record with times == 1 added to the
 // pile-up (include/walt_amd.h, "methylation pile-up"), the batch read once.  1: every lane adds its own slice's calls
 // (pile_slice); 2: pile_rows.
-template <int kPile>
+// kExcl: the batch comes with excluded intervals (a.excl).  An instance of its own: the calls without them run the
+// code they always ran (the word's load and the mask's arithmetic per slice cost the calling kernel 3 % when both
+// lived in one instance).
+template <int kPile, bool kExcl>
 __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   __shared__ uint32_t s_start[kLdsChroms + 1];
   __shared__ unsigned long long s_red[kBlock / 64][kMethTotals];
@@ -227,6 +231,9 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     const bool counted = times == 1 && !(a.skip && a.skip[r * a.skip_stride]);
     uint32_t c_lo = 0, c_hi = 0;
     if (mapped) chrom_bounds(s_start, a.start_index, tab, pos, c_lo, c_hi);
+    // the other mate of the pair calls these read positions (include/walt_amd.h, "overlap of a pair"); 0: none
+    const uint32_t ex = kExcl ? a.excl[r] : 0u;
+    const uint32_t ex_lo = ex & 0xFFFFu, ex_hi = ex >> 16;
     const uint32_t ga = cv == 'A' ? 1u : 0u;
     const uint32_t* __restrict__ ref = a.ref[strand == '-' ? 1 : 0];
     unsigned long long meth = 0, unmeth = 0;
@@ -243,7 +250,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
           if (i0 < total) {
             uint32_t out[4];
             meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                            batch_bytes - off - done, out, meth, unmeth, cm, cu);
+                            batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi);
             if (cb) meth_store_slice(cb + done, total, i0, out);
           }
           if (counted) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
@@ -259,18 +266,12 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
         const int total = (int)(end - off - done < (1u << 30) ? end - off - done : (1u << 30));
         const int h = done ? 0 : head;
         for (int i0 = -h + 16 * (int)sub; i0 < total; i0 += 16 * (int)kMethGroup) {
-          uint32_t out[4];
-          if (kPile == 1) {
-            uint32_t cm, cu;
-            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                            batch_bytes - off - done, out, meth, unmeth, cm, cu);
-            if (counted)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
-              pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
-                         [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
-          } else {
-            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                            batch_bytes - off - done, out, meth, unmeth);
-          }
+          uint32_t out[4], cm, cu;
+          meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                          batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi);
+          if (kPile == 1 && counted)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
+            pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
+                       [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
           if (cb) meth_store_slice(cb + done, total, i0, out);
         }
       }
@@ -310,9 +311,12 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) { meth_call_body<0>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile(const MethArgs a) { meth_call_body<1>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile_rows(const MethArgs a) { meth_call_body<2>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) { meth_call_body<0, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile(const MethArgs a) { meth_call_body<1, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows(const MethArgs a) { meth_call_body<2, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call_excl(const MethArgs a) { meth_call_body<0, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_excl(const MethArgs a) { meth_call_body<1, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_excl(const MethArgs a) { meth_call_body<2, true>(a); }
 
 // folds the shards into walt_meth_stats (accumulating) and clears them
 __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
@@ -349,7 +353,7 @@ static int pile_check(const walt_index* idx, const walt_pileup* p, const char* w
 static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, const void* d_records,
                        size_t rec_stride, const void* d_conv, size_t conv_stride, int conversion, const void* d_call_len,
                        void* d_calls, void* d_counts, void* d_stats, hipStream_t stream, walt_pileup* pile = nullptr,
-                       const void* d_skip = nullptr, size_t skip_stride = 0) {
+                       const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr) {
   if (n == 0 || (!d_calls && !d_counts && !d_stats && !pile)) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   MethArgs a;
@@ -374,10 +378,12 @@ static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offse
   a.pile[1] = pile ? pile->plane[1] : nullptr;
   a.skip = static_cast<const uint8_t*>(d_skip);
   a.skip_stride = skip_stride;
+  a.excl = static_cast<const uint32_t*>(d_excl);
   const uint64_t want = ((uint64_t)n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
-  hipLaunchKernelGGL(!pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile, dim3(grid), dim3(kBlock), 0,
-                     stream, a);
+  const auto kernel = a.excl ? (!pile ? k_meth_call_excl : idx->opt.pile_rows ? k_meth_pile_rows_excl : k_meth_pile_excl)
+                             : (!pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   if (d_stats)
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
                        static_cast<unsigned long long*>(d_stats));
@@ -405,22 +411,24 @@ namespace walt {
 static int meth_batch_device(const char* who, walt_index* idx, walt_pileup* pile, const void* d_bases, const void* d_offsets,
                              uint32_t n, const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                              int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
-                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0) {
+                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr) {
   int rc = meth_args_check(idx, who, record_stride, d_conv, conv_stride, conversion);
   if (rc) return rc;
   if (d_skip && skip_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": skip stride 0 is smaller than its element (1)");
   if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
     return fail(WALT_EINVAL, std::string(who) + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
+  if ((uintptr_t)d_excl & 3u) return fail(WALT_EINVAL, std::string(who) + ": excl must be 4-byte aligned");
   return meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
-                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride);
+                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride, d_excl);
 }
 
 // the two host forms (pile null: walt_meth_call_batch)
 static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile, const char* bases, const uint64_t* offsets,
                            uint32_t n, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
                            int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
-                           walt_meth_stats* stats, const uint8_t* skip = nullptr, size_t skip_stride = 0) {
+                           walt_meth_stats* stats, const uint8_t* skip = nullptr, size_t skip_stride = 0,
+                           const uint32_t* excl = nullptr) {
   const std::string who(who_c);
   int rc = meth_args_check(idx, who_c, record_stride, conv, conv_stride, conversion);
   if (rc) return rc;
@@ -458,11 +466,12 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
     int get(size_t bytes) {
       return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (methylation calls)");
     }
-  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip;
+  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl;
   if ((rc = d_bases.get(nbytes + 16)) || (rc = d_off.get(((size_t)n + 1) * 8)) || (rc = d_rec.get((size_t)n * 16))) return rc;
   if (conv && (rc = d_conv.get(n))) return rc;
   if (call_len && (rc = d_len.get((size_t)n * 4))) return rc;
   if (skip && (rc = d_skip.get(n))) return rc;
+  if (excl && (rc = d_excl.get((size_t)n * 4))) return rc;
   if (calls && (rc = d_calls.get(nbytes + 16))) return rc;
   if (counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts)))) return rc;
   if (stats && (rc = d_stats.get(sizeof(walt_meth_stats)))) return rc;
@@ -472,9 +481,10 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
   if (conv) WALT_HIP(hipMemcpy(d_conv.p, cv.data(), n, hipMemcpyHostToDevice));
   if (call_len) WALT_HIP(hipMemcpy(d_len.p, call_len, (size_t)n * 4, hipMemcpyHostToDevice));
   if (skip) WALT_HIP(hipMemcpy(d_skip.p, sk.data(), n, hipMemcpyHostToDevice));
+  if (excl) WALT_HIP(hipMemcpy(d_excl.p, excl, (size_t)n * 4, hipMemcpyHostToDevice));
   if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
   rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
-                   d_stats.p, nullptr, pile, d_skip.p, 1);
+                   d_stats.p, nullptr, pile, d_skip.p, 1, d_excl.p);
   if (rc) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
@@ -546,6 +556,27 @@ int walt_meth_pileup_batch_skip(walt_index* idx, walt_pileup* p, const char* bas
   if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_skip");
   return meth_batch_host("walt_meth_pileup_batch_skip", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
                          conversion, call_len, calls, counts, stats, skip, skip_stride);
+}
+
+// the skip forms plus excl (include/walt_amd.h, "overlap of a pair"); the pile-up and skip may be null
+int walt_meth_pileup_batch_excl_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, void* stream) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_excl_device: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_excl_device");
+  return meth_batch_device("walt_meth_pileup_batch_excl_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
+                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl);
+}
+
+int walt_meth_pileup_batch_excl(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_excl: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_excl");
+  return meth_batch_host("walt_meth_pileup_batch_excl", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
+                         conversion, call_len, calls, counts, stats, skip, skip_stride, excl);
 }
 
 }  // extern "C"

@@ -91,10 +91,12 @@ WALT_HD MethSlice meth_slice(const uint32_t rd[4], unsigned long long ext, uint3
 
 // The three flag sets of meth_slice for a slice that starts at read position i0 (negative in a read's first slice),
 // of a read at genome position p in the chromosome [lo, hi), with `limit` = min(read length, call_len).
+// [ex_lo, ex_hi): read positions that get no call although they could (include/walt_amd.h, "overlap of a pair": the
+// other mate of the pair calls them); empty when ex_lo >= ex_hi.
 WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long hi, long long limit, uint32_t ga,
-                              uint32_t& call, uint32_t& v1, uint32_t& v2) {
+                              uint32_t& call, uint32_t& v1, uint32_t& v2, long long ex_lo, long long ex_hi) {
   const long long room = hi - p;  // read positions below it lie inside the chromosome
-  call = meth_range(-i0, (limit < room ? limit : room) - i0);
+  call = meth_range(-i0, (limit < room ? limit : room) - i0) & ~meth_range(ex_lo - i0, ex_hi - i0);
   if (ga) {  // context at q - 1, q - 2 >= lo  <=>  k >= lo + 1 - p - i0, lo + 2 - p - i0
     v1 = meth_range(lo + 1 - p - i0, 16);
     v2 = meth_range(lo + 2 - p - i0, 16);
@@ -102,6 +104,10 @@ WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long
     v1 = meth_range(0, room - i0 - 1);
     v2 = meth_range(0, room - i0 - 2);
   }
+}
+WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long hi, long long limit, uint32_t ga,
+                              uint32_t& call, uint32_t& v1, uint32_t& v2) {
+  meth_slice_flags(i0, p, lo, hi, limit, ga, call, v1, v2, 0, 0);
 }
 
 // ext of meth_slice from the packed reference: positions qs = q0 - 2 .. qs + 31 (qs may be negative at the genome's
@@ -125,16 +131,17 @@ WALT_HD unsigned long long meth_ref_ext(const uint32_t* ref, long long qs, uint3
 // bases in front of rb and from rb on: a partial slice (a read's head or tail) is loaded whole where the 16 bytes lie
 // inside the batch (the neighbouring read's bases are masked out by the flags), byte by byte at the batch's two ends.
 // cm / cu = the slice's positions called methylated / unmethylated (field masks; 0 where nothing is called): what a
-// per-cytosine pile-up adds (pileup_core.h).
+// per-cytosine pile-up adds (pileup_core.h).  [ex_lo, ex_hi): the read positions excluded from calling (meth_slice_flags).
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
                              uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
                              unsigned long long before, unsigned long long after, uint32_t out[4],
-                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu) {
+                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
+                             uint32_t ex_lo, uint32_t ex_hi) {
   out[0] = out[1] = out[2] = out[3] = 0x2E2E2E2Eu;
   cm = cu = 0;
   if (!mapped || i0 >= (int)limit) return;
   uint32_t call, v1, v2;
-  meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2);
+  meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2, ex_lo, ex_hi);
   if (!call) return;
   uint32_t rd[4] = {0, 0, 0, 0};
   if ((i0 >= 0 || (unsigned long long)(-i0) <= before) && (unsigned long long)(i0 + 16) <= after) {
@@ -150,12 +157,19 @@ WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool 
   meth += s.meth; unmeth += s.unmeth;
   cm = s.cm; cu = s.cu;
 }
+// the forms without an excluded interval: what they always gave
+WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
+                             uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
+                             unsigned long long before, unsigned long long after, uint32_t out[4],
+                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu) {
+  meth_read_slice(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu, 0u, 0u);
+}
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
                              uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
                              unsigned long long before, unsigned long long after, uint32_t out[4],
                              unsigned long long& meth, unsigned long long& unmeth) {
   uint32_t cm, cu;
-  meth_read_slice(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu);
+  meth_read_slice(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu, 0u, 0u);
 }
 // Stores the slice's characters that belong to the read; cb + i0 is 16-byte aligned.  A whole slice is one 16-byte
 // store.  A read's tail [0, kb) goes out as naturally aligned pieces of 8, 4, 2 and 1 bytes by the bits of kb, its

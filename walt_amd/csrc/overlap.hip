@@ -1,0 +1,151 @@
+// overlap.hip -- the overlap of a proper pair on the device (include/walt_amd.h, "overlap of a pair"): one kernel that
+// turns every walt_pair_result of a batch into the interval of mate 2's read positions whose forward positions mate 1
+// already calls.  The per-lane logic is overlap_core.h's.  The reference has no such mode; the contract is the header's.
+#include <string.h>
+
+#include <hip/hip_runtime.h>
+
+#include "map_common.h"
+#include "overlap_core.h"
+
+namespace walt {
+
+constexpr uint32_t kOverlapTotals = 2;  // pairs with a non-empty interval, mate-2 bases excluded
+static_assert(sizeof(walt_pair_result) == 64 && offsetof(walt_pair_result, m2) == 16 && offsetof(walt_pair_result, best_times) == 32,
+              "k_pair_overlap reads a walt_pair_result by word");
+
+struct OverlapArgs {
+  const uint32_t* start_index;
+  uint32_t n_chrom;
+  uint32_t genome_len;
+  const uint32_t* pairs;       // walt_pair_result[n], sixteen words each
+  const uint64_t* offsets1;    // n + 1 each: only the differences are used
+  const uint64_t* offsets2;
+  const uint32_t* call_len1;   // null: the whole read
+  const uint32_t* call_len2;
+  uint32_t n;
+  uint32_t* excl;
+  unsigned long long* totals;  // null: not wanted
+};
+
+// One pair per lane: 64 bytes of record, two offsets per mate, the optional clip points, one look-up over the staged
+// chromosome starts, one word out.
+__global__ __launch_bounds__(kBlock) void k_pair_overlap(const OverlapArgs a) {
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  __shared__ unsigned long long s_red[kBlock / 64][kOverlapTotals];
+  const ChromTab tab = chrom_tab_of(a.n_chrom);
+  chrom_tab_stage(s_start, a.start_index, tab);
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  uint32_t word = 0, bases = 0;
+  if (i < a.n) {
+    const uint32_t* rec = a.pairs + i * 16;
+    const uint32_t p1 = rec[0], t1 = rec[1], s1 = rec[2] & 0xFFu;
+    const uint32_t p2 = rec[4], t2 = rec[5], s2 = rec[6] & 0xFFu;
+    const uint32_t best_times = rec[8];
+    const uint64_t b1 = a.offsets1[i], e1 = a.offsets1[i + 1], b2 = a.offsets2[i], e2 = a.offsets2[i + 1];
+    const uint64_t len1 = e1 > b1 ? e1 - b1 : 0, len2 = e2 > b2 ? e2 - b2 : 0;
+    word = overlap_pair(s_start, a.start_index, tab, a.genome_len, p1, t1, s1 == '-', p2, t2, s2 == '-', best_times, len1, len2,
+                        a.call_len1 ? a.call_len1[i] : ~0u, a.call_len2 ? a.call_len2[i] : ~0u, bases);
+    a.excl[i] = word;
+  }
+  if (!a.totals) return;  // (uniform)
+  // wavefront, block, then one add per block and total
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long v[kOverlapTotals] = {word ? 1ull : 0ull, bases};
+#pragma unroll
+  for (uint32_t k = 0; k < kOverlapTotals; ++k) {
+    for (int d = 32; d > 0; d >>= 1) v[k] += __shfl_down(v[k], d);
+    if (lane == 0) s_red[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < kOverlapTotals) {
+    unsigned long long t = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_red[w][threadIdx.x];
+    if (t) atomicAdd(&a.totals[threadIdx.x], t);
+  }
+}
+
+static int overlap_launch(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2, uint32_t n,
+                          const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals, hipStream_t stream) {
+  if (n == 0) return WALT_OK;
+  WALT_HIP(hipSetDevice(idx->device));
+  OverlapArgs a;
+  a.start_index = idx->view.start_index;
+  a.n_chrom = idx->view.n_chrom;
+  a.genome_len = idx->head.genome_len;
+  a.pairs = static_cast<const uint32_t*>(d_pairs);
+  a.offsets1 = static_cast<const uint64_t*>(d_offsets1);
+  a.offsets2 = static_cast<const uint64_t*>(d_offsets2);
+  a.call_len1 = static_cast<const uint32_t*>(d_call_len1);
+  a.call_len2 = static_cast<const uint32_t*>(d_call_len2);
+  a.n = n;
+  a.excl = static_cast<uint32_t*>(d_excl);
+  a.totals = static_cast<unsigned long long*>(d_totals);
+  hipLaunchKernelGGL(k_pair_overlap, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+  WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+}  // namespace walt
+
+using namespace walt;
+
+extern "C" {
+
+int walt_pair_overlap_batch_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
+                                   uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
+                                   void* stream) {
+  const std::string who = "walt_pair_overlap_batch_device";
+  if (!idx) return fail(WALT_EINVAL, who + ": bad argument (null index)");
+  if (n && (!d_pairs || !d_offsets1 || !d_offsets2 || !d_excl)) return fail(WALT_EINVAL, who + ": bad argument");
+  if (((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_call_len1 & 3u) || ((uintptr_t)d_call_len2 & 3u) || ((uintptr_t)d_excl & 3u) ||
+      ((uintptr_t)d_offsets1 & 7u) || ((uintptr_t)d_offsets2 & 7u) || ((uintptr_t)d_totals & 7u))
+    return fail(WALT_EINVAL, who + ": pairs, call_len and excl must be 4-byte aligned, offsets and totals 8-byte aligned");
+  return overlap_launch(idx, d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2, d_excl, d_totals,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
+                            uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl, uint64_t* totals) {
+  const std::string who = "walt_pair_overlap_batch";
+  if (!idx) return fail(WALT_EINVAL, who + ": bad argument (null index)");
+  if (n == 0) return WALT_OK;
+  if (!pairs || !offsets1 || !offsets2 || !excl) return fail(WALT_EINVAL, who + ": bad argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (offsets1[i + 1] < offsets1[i] || offsets2[i + 1] < offsets2[i]) return fail(WALT_EINVAL, who + ": offsets not non-decreasing");
+  WALT_HIP(hipSetDevice(idx->device));
+  struct Scoped {
+    void* p = nullptr;
+    ~Scoped() { if (p) (void)hipFree(p); }
+    int get(size_t bytes) {
+      return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (overlap of a pair)");
+    }
+  } d_pairs, d_off1, d_off2, d_len1, d_len2, d_excl, d_totals;
+  int rc;
+  const size_t off_bytes = ((size_t)n + 1) * 8;
+  if ((rc = d_pairs.get((size_t)n * 64)) || (rc = d_off1.get(off_bytes)) || (rc = d_off2.get(off_bytes)) ||
+      (rc = d_excl.get((size_t)n * 4)))
+    return rc;
+  if (call_len1 && (rc = d_len1.get((size_t)n * 4))) return rc;
+  if (call_len2 && (rc = d_len2.get((size_t)n * 4))) return rc;
+  if (totals && (rc = d_totals.get(kOverlapTotals * 8))) return rc;
+  // (only the differences of the offsets are used: relative to offsets[0] or not is the same)
+  WALT_HIP(hipMemcpy(d_pairs.p, pairs, (size_t)n * 64, hipMemcpyHostToDevice));
+  WALT_HIP(hipMemcpy(d_off1.p, offsets1, off_bytes, hipMemcpyHostToDevice));
+  WALT_HIP(hipMemcpy(d_off2.p, offsets2, off_bytes, hipMemcpyHostToDevice));
+  if (call_len1) WALT_HIP(hipMemcpy(d_len1.p, call_len1, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (call_len2) WALT_HIP(hipMemcpy(d_len2.p, call_len2, (size_t)n * 4, hipMemcpyHostToDevice));
+  if (totals) WALT_HIP(hipMemset(d_totals.p, 0, kOverlapTotals * 8));
+  if ((rc = overlap_launch(idx, d_pairs.p, d_off1.p, d_off2.p, n, d_len1.p, d_len2.p, d_excl.p, d_totals.p, nullptr))) return rc;
+  WALT_HIP(hipStreamSynchronize(nullptr));
+  WALT_HIP(hipMemcpy(excl, d_excl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (totals) {
+    uint64_t t[kOverlapTotals];
+    WALT_HIP(hipMemcpy(t, d_totals.p, sizeof t, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < kOverlapTotals; ++k) totals[k] += t[k];
+  }
+  return WALT_OK;
+}
+
+}  // extern "C"

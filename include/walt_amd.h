@@ -553,6 +553,72 @@ int walt_meth_pileup_batch_excl_device(walt_index* idx, walt_pileup* p, const vo
                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                        const void* d_skip, size_t skip_stride, const void* d_excl, void* stream);
 
+/* ---- methylation bias by read position: calls per position of the read as sequenced, context and state ------------
+ * The reference has no such mode (its users run a second program over the mapped reads: Bismark's M-bias.txt, MethPipe's
+ * per-position bsrate); the contract is defined here.  The table shows end-repair bias at the 5' end of mate 2, adaptor and
+ * low-quality bias at the 3' end, and -- in its CHG / CHH rows -- the conversion rate per sequencing cycle.  It needs the
+ * calls, their offsets, the records and the skip bytes alone: a set (walt_mbias) belongs to a device, like walt_dedup, not
+ * to an index.
+ *
+ * The set holds n_tables tables, 1 to 8; a caller uses one table per mate.  A table is
+ *   uint64_t count[4][2][1024]   (WALT_MBIAS_POSITIONS = 1024, WALT_MBIAS_WORDS = 8192)
+ * first index the context (0 CpG, 1 CHG, 2 CHH, 3 unknown), second index 0 methylated / 1 unmethylated, third index the
+ * read position.  Counts are exact 64-bit.
+ *
+ * What counts.  For record r of a batch, read position i in [0, offsets[r + 1] - offsets[r]) adds 1 to count[c][m][i] when
+ * calls[offsets[r] + i] is one of the eight letters: z / Z CpG, x / X CHG, h / H CHH, u / U unknown context; upper case is
+ * methylated (m = 0), lower case unmethylated (m = 1).  Every other byte adds nothing -- '.', and so the positions that
+ * call_len clips and that an excluded interval ("overlap of a pair") blanks.  A record adds only when times == 1 and its
+ * skip byte, if given, is zero: the records that walt_meth_stats and the pile-up count.  A read longer than 1024 bases adds
+ * nothing (the kernel tests the length before it forms an index).  Consequently, for the same records and calls,
+ *   sum over i of count[c][0][i] = walt_meth_stats.meth[c]   and   sum over i of count[c][1][i] = walt_meth_stats.unmeth[c].
+ *
+ * Life cycle.  walt_mbias_create: WALT_EINVAL when n_tables is outside 1..8 or the device does not exist, WALT_EHIP when
+ * there is no device at all; the tables start at zero.  walt_mbias_clear zeroes every table.  walt_mbias_read waits for the
+ * device and writes table `table` to out[4][2][1024], folding the replicas the set keeps on the device (8 per table, so
+ * that the blocks of a batch do not all add to one line).  walt_mbias_device_bytes = n_tables x 8 x 65536.
+ *
+ * Batch calls.  walt_mbias_batch[_device] add the calls of one batch to one table.  Strides and alignment as in
+ * walt_meth_call_batch: a record stride of at least 16 and a multiple of 4 (64 with a base of &pairs->m1 or &pairs->m2 for
+ * one mate of a walt_pair_result array), a skip stride of at least 1 (skip == NULL: none); d_records 4-byte aligned,
+ * d_offsets 8-byte aligned, d_calls at any address.  Host form: offsets relative to offsets[0] or not, as the caller has
+ * them (calls + offsets[0] is the first byte read); a read longer than 1024 bases is rejected as the calling host form
+ * rejects it; it waits for the result.  Device form: pointers are HBM addresses on the set's device, asynchronous on
+ * `stream`.  Adds are ordered by their stream, and two streams may feed one set at the same time.  WALT_EINVAL, with a
+ * message naming the cause, for a null set, a table index >= n_tables, a null array with n > 0, a bad stride, a
+ * misaligned pointer.
+ *
+ * With the calling.  walt_meth_pileup_batch_mbias[_device] are walt_meth_pileup_batch_excl[_device] plus mb and table:
+ * the calls of the batch are added to that table of mb as walt_mbias_batch would add them, under the same skip.  mb == NULL
+ * gives exactly the excl form.  The host form keeps its device copy of the calls and counts it before freeing it, also when
+ * the caller's `calls` is NULL (it then allocates the device array for itself).  The device form launches the bias kernel
+ * behind the calling kernel on the same stream; WALT_EINVAL when mb is given and d_calls is NULL (the table is counted from
+ * the calls).  WALT_EINVAL when the set lives on another device than the index, or for a table index >= n_tables.  The
+ * pile-up, skip and excl may each be NULL as before.  Every older entry point is this call with mb == NULL and gives what
+ * it always gave. */
+#define WALT_MBIAS_POSITIONS 1024
+#define WALT_MBIAS_WORDS 8192
+typedef struct walt_mbias walt_mbias;
+int walt_mbias_create(int device, uint32_t n_tables, walt_mbias** out);
+void walt_mbias_destroy(walt_mbias* mb);
+int walt_mbias_clear(walt_mbias* mb);
+uint64_t walt_mbias_device_bytes(const walt_mbias* mb);
+int walt_mbias_read(walt_mbias* mb, uint32_t table, uint64_t* out /*[4][2][1024]*/);
+int walt_mbias_batch(walt_mbias* mb, uint32_t table, const char* calls, const uint64_t* offsets, uint32_t n,
+                     const void* records, size_t record_stride, const uint8_t* skip, size_t skip_stride);
+int walt_mbias_batch_device(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
+                            const void* d_records, size_t record_stride, const void* d_skip, size_t skip_stride, void* stream);
+int walt_meth_pileup_batch_mbias(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                 const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                 int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                 walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                 walt_mbias* mb, uint32_t table);
+int walt_meth_pileup_batch_mbias_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                        const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                        uint32_t table, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

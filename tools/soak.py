@@ -639,6 +639,72 @@ def run_soak_overlap(seeds, pattern=3):
         pattern, len(seeds), pairs_total, overlap_total, bases_total)
 
 
+def run_soak_mbias(seeds, pattern=3):
+    """Methylation bias by read position (walt_mbias_*, walt_meth_pileup_batch_mbias) on the genomes of `seeds`: pairs cut
+    from fragments of every length, some with call_len, skip bytes and the excluded intervals of their overlap, mapped
+    and called on the GPU with one table per mate; each table compared with the restatement in tests/test_gpu_mbias.py
+    over the calls that came back, its column sums with the batch totals, and the same calls fed again through
+    walt_mbias_batch double every count.  Returns the summary line, raises SoakMismatch at the first difference."""
+    import refio
+    import walt_amd
+    import test_gpu_mbias as rule_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 150)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    pairs_total = calls_total = 0
+    mb = walt_amd.MBias(0, 2, pattern=pattern)
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 86028121 + 19)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_mbias_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern, many=rng.random() < 0.3)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                try:
+                    r1, r2 = sample_fragments(rng, seqs, 300, lo, hi, refio)
+                    b1, o1 = walt_amd.pack_reads(r1)
+                    b2, o2 = walt_amd.pack_reads(r2)
+                    res, _ = idx.map_pe_batch(b1, o1, b2, o2, frag_range=2 * hi + 200)
+                    excl, _ = idx.pair_overlap(res, o1, o2)
+                    mb.clear()
+                    for k, (b, o, reads, mate, cv) in enumerate(((b1, o1, r1, "m1", "T"), (b2, o2, r2, "m2", "A"))):
+                        cl = [rng.choice([len(r), len(r), len(r) // 2, 0, len(r) + 3]) for r in reads] if rng.random() < 0.5 else None
+                        skip = np.array([rng.random() < 0.2 for _ in reads], dtype=np.uint8) if rng.random() < 0.5 else None
+                        ex = excl if k == 1 and rng.random() < 0.7 else None
+                        calls, _, stats = idx.meth_call_batch(b, o, res[mate], cv, call_len=cl, skip=skip, excl=ex, mbias=mb, mbias_table=k)
+                        want = rule_of.expected_table(calls, o, res[mate]["times"], skip)
+                        got = mb.read(k)
+                        if not np.array_equal(got, want):
+                            raise SoakMismatch("MISMATCH mbias seed %d mate %d: table differs at %s" % (seed, k + 1, np.argwhere(got != want)[:4].tolist()))
+                        m, u = rule_of.column_sums(got)
+                        if not (np.array_equal(m, stats["meth"][0]) and np.array_equal(u, stats["unmeth"][0])):
+                            raise SoakMismatch("MISMATCH mbias seed %d mate %d: column sums %s %s, totals %s" % (seed, k + 1, m, u, stats))
+                        mb.add(calls, o, res[mate], skip=skip, table=k)
+                        if not np.array_equal(mb.read(k), want * np.uint64(2)):
+                            raise SoakMismatch("MISMATCH mbias seed %d mate %d: the same calls fed again do not double the table" % (seed, k + 1))
+                        calls_total += int(want.sum())
+                    pairs_total += len(r1)
+                finally:
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        mb.close()
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    if calls_total < 10 * pairs_total:
+        raise SoakMismatch("soak too thin: %d calls counted over %d pairs" % (calls_total, pairs_total))
+    return "soak ok: mbias, pattern %d, %d genomes, %d pairs, %d calls counted by read position identical to the restatement" % (
+        pattern, len(seeds), pairs_total, calls_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

@@ -236,6 +236,19 @@ def lib(pattern=None):
                                               c.c_size_t, vp]
     L.walt_meth_pileup_batch_excl_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                      vp, c.c_size_t, vp, vp]
+    L.walt_mbias_create.argtypes = [ci, u32, c.POINTER(vp)]
+    L.walt_mbias_destroy.argtypes = [vp]
+    L.walt_mbias_destroy.restype = None
+    L.walt_mbias_clear.argtypes = [vp]
+    L.walt_mbias_device_bytes.argtypes = [vp]
+    L.walt_mbias_device_bytes.restype = u64
+    L.walt_mbias_read.argtypes = [vp, u32, vp]
+    L.walt_mbias_batch.argtypes = [vp, u32, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t]
+    L.walt_mbias_batch_device.argtypes = [vp, u32, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, vp]
+    L.walt_meth_pileup_batch_mbias.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                               c.c_size_t, vp, vp, u32]
+    L.walt_meth_pileup_batch_mbias_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                      vp, c.c_size_t, vp, vp, u32, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -540,7 +553,7 @@ class Index:
         self._ck(self._L.walt_index_enable_reference(self._h))
 
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                        stats=None, want_stats=True, skip=None, excl=None):
+                        stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
         strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
@@ -548,9 +561,11 @@ class Index:
         existing 1-element meth_stats_dtype array to accumulate into.  skip: a uint8 array with one element per read
         (any stride, e.g. dup[:, 0] of Dedup.add_pairs): a read with a non-zero byte is called but left out of stats.
         excl: a uint32 array with one word per read, as Index.pair_overlap returns it: the read positions
-        [excl & 0xFFFF, excl >> 16) get no call (walt_meth_pileup_batch_excl; only when given)."""
+        [excl & 0xFFFF, excl >> 16) get no call (walt_meth_pileup_batch_excl; only when given).  mbias: an MBias set on
+        this index's device; the calls of the batch are added to its table mbias_table under the same skip
+        (walt_meth_pileup_batch_mbias; only when given; want_calls may be False)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
-                                skip, excl)
+                                skip, excl, mbias, mbias_table)
 
     # -- overlap of a pair (include/walt_amd.h states the rules) --------------------------------------------------
     def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None):
@@ -589,7 +604,7 @@ class Index:
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True, skip=None, excl=None):
+                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
         records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
         positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
@@ -633,10 +648,15 @@ class Index:
             skip_stride = skip_arr.strides[0] if n > 1 else 1
             if skip_stride <= 0:
                 skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+        excl_arr = None
         if excl is not None:
             excl_arr = np.ascontiguousarray(excl, dtype=np.uint32)
             if excl_arr.ndim != 1 or excl_arr.shape[0] != n:
                 raise ValueError("excl: a 1-d uint32 array with one word per read")
+        if mbias is not None:
+            self._ck(self._L.walt_meth_pileup_batch_mbias(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride,
+                                                          _ptr(excl_arr) if n else None, mbias.handle, int(mbias_table)))
+        elif excl is not None:
             self._ck(self._L.walt_meth_pileup_batch_excl(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride,
                                                          _ptr(excl_arr) if n else None))
         elif skip is not None:
@@ -648,8 +668,23 @@ class Index:
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
-                               conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0):
-        """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous."""
+                               conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0,
+                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0):
+        """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  mbias: an MBias set
+        whose table mbias_table takes the calls too (walt_meth_pileup_batch_mbias_device with a null pile-up; d_calls
+        must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
+        pile-up)."""
+        if mbias is not None:
+            self._ck(self._L.walt_meth_pileup_batch_mbias_device(
+                self._h, None, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, mbias.handle,
+                int(mbias_table), stream))
+            return
+        if d_skip is not None or d_excl is not None:
+            self._ck(self._L.walt_meth_pileup_batch_excl_device(
+                self._h, None, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, stream))
+            return
         self._ck(self._L.walt_meth_call_batch_device(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride),
                                                      d_conv, int(conv_stride), ord(conversion), d_call_len, d_calls,
                                                      d_counts, d_stats, stream))
@@ -749,16 +784,23 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True, skip=None, excl=None):
+                  want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip, excl)
+                                       want_stats, skip, excl, mbias, mbias_table)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
-                         skip_stride=1, d_excl=None):
+                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
-        record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's)."""
+        record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
+        MBias set whose table mbias_table takes the calls too (d_calls must be given)."""
+        if mbias is not None:
+            self._index._ck(self._L.walt_meth_pileup_batch_mbias_device(
+                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, mbias.handle,
+                int(mbias_table), stream))
+            return
         if d_excl is not None:
             self._index._ck(self._L.walt_meth_pileup_batch_excl_device(
                 self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
@@ -904,6 +946,84 @@ class Dedup:
     def close(self):
         if self._h:
             self._L.walt_dedup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MBias:
+    """Methylation bias by read position on one device (include/walt_amd.h, "methylation bias by read position"):
+    `tables` tables (1 to 8; one per mate) of exact 64-bit counts [context 4][methylated, unmethylated][position 1024],
+    summed from the calls of uniquely mapped, unskipped records."""
+
+    SHAPE = (4, 2, 1024)
+
+    def __init__(self, device=0, tables=1, pattern=None):
+        self._L = lib(pattern)
+        h = ctypes.c_void_p()
+        self._h = None
+        self._ck(self._L.walt_mbias_create(int(device), int(tables), ctypes.byref(h)))
+        self._h = h
+        self.tables = int(tables)
+
+    def _ck(self, rc):
+        if rc != WALT_OK:
+            raise WaltError(rc, self._L.walt_last_error().decode("utf-8", "replace"))
+
+    def add(self, calls, offsets, records, skip=None, table=0):
+        """calls: the uint8 array Index.meth_call_batch returned (indexed from offsets[0]); offsets: n + 1; records: a
+        best_match_dtype array or strided view (e.g. the m2 field of a pair_result_dtype array); skip: a uint8 array per
+        record, any stride.  Waits for the result."""
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        records = np.asarray(records)
+        if records.dtype != best_match_dtype or records.ndim != 1 or records.shape[0] != n:
+            raise ValueError("records: a 1-d best_match_dtype array (or view) with one element per read")
+        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
+        if rec_stride < 0:
+            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
+        skip_arr, skip_stride = None, 1
+        if skip is not None:
+            skip_arr = np.asarray(skip)
+            if skip_arr.dtype != np.uint8 or skip_arr.ndim != 1 or skip_arr.shape[0] != n:
+                raise ValueError("skip: a 1-d uint8 array with one element per read")
+            skip_stride = skip_arr.strides[0] if n > 1 else 1
+            if skip_stride <= 0:
+                skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+        calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
+        self._ck(self._L.walt_mbias_batch(self._h, int(table), calls_ptr, _ptr(offsets), n, records.ctypes.data if n else None,
+                                          rec_stride, _ptr(skip_arr) if n else None, skip_stride))
+
+    def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, table=0, stream=0):
+        """Device-pointer form (ints are HBM addresses on the set's device, stream a hipStream_t value); asynchronous."""
+        self._ck(self._L.walt_mbias_batch_device(self._h, int(table), d_calls, d_offsets, int(n), d_records, int(record_stride),
+                                                 d_skip, int(skip_stride), stream))
+
+    def read(self, table=0):
+        """The table as a uint64 array [4, 2, 1024]: context (CpG, CHG, CHH, unknown), methylated / unmethylated, position."""
+        out = np.zeros(self.SHAPE, dtype=np.uint64)
+        self._ck(self._L.walt_mbias_read(self._h, int(table), _ptr(out)))
+        return out
+
+    def clear(self):
+        self._ck(self._L.walt_mbias_clear(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._L.walt_mbias_device_bytes(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.walt_mbias_destroy(self._h)
             self._h = None
 
     def __del__(self):

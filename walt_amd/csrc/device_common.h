@@ -129,7 +129,22 @@ struct walt_pileup {
   uint64_t device_bytes = 0;
 };
 
+// Methylation bias by read position (mbias.hip): n_tables x kMbiasReplicas replica tables of 64-bit counters,
+// count[4][2][1024] each; a block of the bias kernel flushes into replica blockIdx % kMbiasReplicas of its table.
+struct walt_mbias {
+  int device = 0;
+  int n_cu = 256;
+  uint32_t n_tables = 0;
+  unsigned long long* tabs = nullptr;
+};
+
 namespace walt {
+// mbias.hip: the argument checks of walt_mbias_batch_device (who: the entry point the message names), and the kernel on `stream`
+int mbias_check(const walt_mbias* mb, const char* who, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
+                const void* d_records, size_t rec_stride, const void* d_skip, size_t skip_stride);
+int mbias_launch(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
+                 size_t rec_stride, const void* d_skip, size_t skip_stride, hipStream_t stream);
+
 // grow-only device buffer `slot` of idx (freed by walt_index_close)
 inline hipError_t host_api_buffer(walt_index* idx, int slot, size_t bytes, void** out) {
   if (idx->host_api_cap[slot] < bytes) {

@@ -447,5 +447,28 @@ struct FastqReader {
   }
 };
 
+// ---------------------------------------------------------------- <out>.mbias (bin/walt -MB)
+// One block of the methylation bias table (include/walt_amd.h, "methylation bias by read position"): count[4][2][1024]
+// as walt_mbias_read returns it.  For each context in the order CpG, CHG, CHH, unknown, one line per position 1 .. L:
+//   context <TAB> position (1-based) <TAB> methylated <TAB> unmethylated <TAB> level
+// L = the highest position with a non-zero count in any context of the block (no line when there is none); the level is
+// %.6f, or NA where both counts are 0, as <out>.methstats prints it.
+static const uint32_t kMbiasPositions = 1024;
+inline void put_mbias_block(Sink& out, const uint64_t* count) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  uint32_t L = 0;
+  for (uint32_t cell = 0; cell < 8; ++cell)
+    for (uint32_t i = L; i < kMbiasPositions; ++i)
+      if (count[(size_t)cell * kMbiasPositions + i]) L = i + 1;
+  char num[128];
+  for (uint32_t c = 0; c < 4; ++c)
+    for (uint32_t i = 0; i < L; ++i) {
+      const unsigned long long m = count[(size_t)(2 * c) * kMbiasPositions + i], u = count[(size_t)(2 * c + 1) * kMbiasPositions + i];
+      if (m + u) snprintf(num, sizeof num, "%s\t%u\t%llu\t%llu\t%.6f\n", ctx[c], i + 1, m, u, (double)m / ((double)m + (double)u));
+      else snprintf(num, sizeof num, "%s\t%u\t%llu\t%llu\tNA\n", ctx[c], i + 1, m, u);
+      out.lit(num);
+    }
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

@@ -54,6 +54,7 @@ struct Options {
   bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
+  bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -95,6 +96,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
+    else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -126,8 +128,8 @@ static Options parse(int argc, const char** argv) {
     die("-D (duplicates) keys a pair by its fragment length in 28 bits: it cannot be combined with -L of 134217728 (2^27) or more");
   if (o.no_overlap && !o.se_csv.empty())
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
-  if (o.no_overlap && !o.meth && !o.methcounts)
-    die("-NO (no overlap) changes methylation calls only: without -M or -MC there is nothing for it to do");
+  if (o.no_overlap && !o.meth && !o.methcounts && !o.mbias)
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB) there is nothing for it to do");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -386,6 +388,41 @@ static void write_methcounts(const string& out_file, PileSet& ps, const GenomeIn
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
 }
 
+// ---------------------------------------------------------------- -MB: methylation bias by read position
+// One set per device of the run, one table per mate; a share's calls are counted on the device that made them.  At the
+// end of a read file the host adds the devices' tables, writes the blocks and clears the sets.
+struct MbiasSet {
+  vector<walt_mbias*> p;
+  uint32_t n_tables = 0;
+  void open(const vector<int>& ids, uint32_t tables) {
+    p.assign(ids.size(), nullptr);
+    n_tables = tables;
+    for (size_t d = 0; d < ids.size(); ++d)
+      if (walt_mbias_create(ids[d], tables, &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+  }
+  void close() {
+    for (walt_mbias*& q : p) { if (q) walt_mbias_destroy(q); q = nullptr; }
+    p.clear();
+  }
+  bool on() const { return !p.empty(); }
+  walt_mbias* of(size_t d) const { return on() ? p[d] : nullptr; }
+  void block(Sink& out, uint32_t table) const {  // the table summed over the devices
+    vector<uint64_t> sum(WALT_MBIAS_WORDS, 0), one(WALT_MBIAS_WORDS);
+    for (walt_mbias* q : p) {
+      check(walt_mbias_read(q, table, one.data()));
+      for (size_t w = 0; w < sum.size(); ++w) sum[w] += one[w];
+    }
+    hostio::put_mbias_block(out, sum.data());
+  }
+  void write(const string& out_file, const Sink& ms) {
+    OutFile mf;
+    if (!mf.open_append(out_file + ".mbias")) die("cannot open input file " + out_file + ".mbias");
+    mf.write(ms.p, ms.n);
+    mf.close();
+    for (walt_mbias* q : p) check(walt_mbias_clear(q));
+  }
+};
+
 // ---------------------------------------------------------------- -D: PCR duplicates
 // One duplicate set per read file, on the first device of the run.  A batch is mapped by all devices first; then the
 // whole batch's records are fed to the set in input order (so the verdict depends neither on -N nor on -g); only then are
@@ -572,9 +609,12 @@ static void process_se(const Options& o, const string& reads_file, const string&
     rd.load(o.batch_size, o.adaptor, bt[0]);
   });
   DeviceSet dev;
-  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));
+  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth || o.methcounts || o.mbias ? WALT_WITH_REFERENCE : 0u));
+  const bool calling = o.meth || o.methcounts || o.mbias;
   PileSet pile;
   if (o.methcounts) pile.open(dev.idx);
+  MbiasSet mbs;
+  if (o.mbias) mbs.open(dev.ids, 1);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
@@ -627,7 +667,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     vector<walt_meth_stats> meth_of(dev.size());
     memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
     if (o.meth && o.sam && calls.size() < b.offsets[n]) calls.resize(b.offsets[n]);
-    if ((o.meth || o.methcounts) && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
+    if (calling && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
     auto map_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
       const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
@@ -635,22 +675,16 @@ static void process_se(const Options& o, const string& reads_file, const string&
       short_of[d] = bs.too_short;
       return rc;
     };
+    // the calls of a share, on the device that mapped it: one call takes whatever the options give it -- the pile-up (-MC),
+    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB) -- each null without its
+    // option (all null: walt_meth_call_batch)
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
-      int rc = WALT_OK;
-      if (dups.on() && (o.meth || o.methcounts))  // -D: the same calls, duplicates neither piled up nor summed
-        rc = walt_meth_pileup_batch_skip(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
-                                         sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
-                                         clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
-                                         o.meth ? &meth_of[d] : nullptr, dups.dup.data() + lo, 1);
-      else if (o.methcounts)  // on the device that mapped the share; with -M both in one call
-        rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
-                                    o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
-                                    o.meth && o.sam ? calls.data() : nullptr, nullptr, o.meth ? &meth_of[d] : nullptr);
-      else if (o.meth)  // on the device that mapped the share
-        rc = walt_meth_call_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
-                                  o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T', clip.empty() ? nullptr : clip.data() + lo,
-                                  o.sam ? calls.data() : nullptr, nullptr, &meth_of[d]);
-      return rc;
+      if (!calling) return (int)WALT_OK;
+      return walt_meth_pileup_batch_mbias(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
+                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
+                                          o.meth ? &meth_of[d] : nullptr, dups.on() ? dups.dup.data() + lo : nullptr, 1, nullptr,
+                                          mbs.of(d), 0);
     };
     if (!dups.on()) {
       dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
@@ -660,7 +694,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     } else {  // -D: every share mapped, then the whole batch through the set in input order, then the calls
       dev.for_each_share(n, map_share);
       dups.feed_se(res, o.rpbat ? conv.data() : nullptr, o.ag ? 'A' : 'T', n);
-      if (o.meth || o.methcounts) dev.for_each_share(n, meth_share);
+      if (calling) dev.for_each_share(n, meth_share);
     }
     for (uint64_t v : short_of) st.too_short += (uint32_t)v;
     for (const walt_meth_stats& m : meth_of) add_meth(meth_total, m);
@@ -723,6 +757,12 @@ static void process_se(const Options& o, const string& reads_file, const string&
     write_methstats(out_file, ms);
   }
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (mbs.on()) {
+    Sink ms;
+    mbs.block(ms, 0);
+    mbs.write(out_file, ms);
+    mbs.close();
+  }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   const double t_c0 = now_s();
   dev.close();
@@ -872,9 +912,12 @@ static void process_pe(const Options& o, const string& file1, const string& file
   const int T_bg = std::max(1, T / 4);
   double t0 = now_s();
   DeviceSet dev;
-  dev.open(o, WALT_STRANDS_ALL | (o.meth || o.methcounts ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
+  dev.open(o, WALT_STRANDS_ALL | (o.meth || o.methcounts || o.mbias ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
+  const bool calling = o.meth || o.methcounts || o.mbias;
   PileSet pile;  // -MC: both mates into the same pile-up
   if (o.methcounts) pile.open(dev.idx);
+  MbiasSet mbs;  // -MB: table k takes slot k
+  if (o.mbias) mbs.open(dev.ids, 2);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
@@ -944,7 +987,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     if (rp && conv.size() < 2 * (size_t)n) conv.resize(2 * (size_t)n);
     vector<walt_meth_stats> meth_of(2 * dev.size());
     memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
-    for (int k = 0; k < 2 && (o.meth || o.methcounts); ++k) {
+    for (int k = 0; k < 2 && calling; ++k) {
       if (o.meth && o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
       if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
     }
@@ -964,48 +1007,33 @@ static void process_pe(const Options& o, const string& file1, const string& file
       overlap_of.assign(2 * dev.size(), 0);
       if (excl.size() < n) excl.resize(n);
     }
-    // -NO: the share's intervals from the records in user order, then both slots through the form that takes them (with
-    // no interval for the user's mate 1: the call it always got); -D's verdicts go along as skip bytes
-    auto no_overlap_share = [&](size_t d, uint32_t lo, uint32_t hi) {
-      const int u1 = 1 - over_slot;
-      vector<walt_pair_result> user;  // -P: mate 1 of the records is the user's mate 2
-      if (pbat) {
-        user.assign(pr + lo, pr + hi);
-        for (walt_pair_result& p : user) std::swap(p.m1, p.m2);
-      }
-      int rc = walt_pair_overlap_batch(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
-                                       clip[u1].empty() ? nullptr : clip[u1].data() + lo,
-                                       clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
-                                       &overlap_of[2 * d]);
-      for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_excl(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
-                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
-                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
-                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
-                                         dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
-                                         k == over_slot ? excl.data() + lo : nullptr);
-      return rc;
-    };
+    // The calls of a share, on the device that mapped it.  -NO: first the share's intervals from the records in user order.
+    // Then both slots through one call that takes whatever the options give it -- the pile-up (-MC: both mates into the
+    // device's), the verdicts as skip bytes (-D), the interval words for the user's mate 2 (-NO; none for mate 1: the call
+    // it always got), the bias set (-MB: table k takes slot k) -- each null without its option.  Slot 0 was mapped C->T,
+    // slot 1 G->A (-RP: as conv says).
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       int rc = WALT_OK;
-      if (o.no_overlap) return no_overlap_share(d, lo, hi);
-      for (int k = 0; k < 2 && rc == WALT_OK && dups.on() && (o.meth || o.methcounts); ++k)  // -D: duplicates neither piled up nor summed
-        rc = walt_meth_pileup_batch_skip(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
-                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
-                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
-                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
-                                         dups.dup.data() + 2 * (size_t)lo + k, 2);
-      if (dups.on()) return rc;
-      for (int k = 0; k < 2 && rc == WALT_OK && o.methcounts; ++k)  // both mates into the device's pile-up; with -M in one call
-        rc = walt_meth_pileup_batch(dev.idx[d], pile.p[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
-                                    sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
-                                    clip[k].empty() ? nullptr : clip[k].data() + lo, o.meth && o.sam ? calls[k].data() : nullptr,
-                                    nullptr, o.meth ? &meth_of[2 * d + k] : nullptr);
-      for (int k = 0; k < 2 && rc == WALT_OK && o.meth && !o.methcounts; ++k)  // slot 0 was mapped C->T, slot 1 G->A (-RP: as conv says)
-        rc = walt_meth_call_batch(dev.idx[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
-                                  sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
-                                  clip[k].empty() ? nullptr : clip[k].data() + lo, o.sam ? calls[k].data() : nullptr, nullptr,
-                                  &meth_of[2 * d + k]);
+      if (!calling) return rc;
+      if (o.no_overlap) {
+        const int u1 = 1 - over_slot;
+        vector<walt_pair_result> user;  // -P: mate 1 of the records is the user's mate 2
+        if (pbat) {
+          user.assign(pr + lo, pr + hi);
+          for (walt_pair_result& p : user) std::swap(p.m1, p.m2);
+        }
+        rc = walt_pair_overlap_batch(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
+                                     clip[u1].empty() ? nullptr : clip[u1].data() + lo,
+                                     clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
+                                     &overlap_of[2 * d]);
+      }
+      for (int k = 0; k < 2 && rc == WALT_OK; ++k)
+        rc = walt_meth_pileup_batch_mbias(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
+                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
+                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
+                                          dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
+                                          o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k);
       return rc;
     };
     if (!dups.on()) {
@@ -1016,7 +1044,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     } else {  // -D: every share mapped, then the whole batch's pairs through the set in input order, then the calls
       dev.for_each_share(n, map_share);
       dups.feed_pe(pr, rp ? conv.data() : nullptr, n);
-      if (o.meth || o.methcounts) dev.for_each_share(n, meth_share);
+      if (calling) dev.for_each_share(n, meth_share);
     }
     for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
     for (size_t d = 0; 2 * d < overlap_of.size(); ++d) { overlap_total[0] += overlap_of[2 * d]; overlap_total[1] += overlap_of[2 * d + 1]; }
@@ -1136,6 +1164,13 @@ static void process_pe(const Options& o, const string& file1, const string& file
   if (o.no_overlap && o.verbose)
     fprintf(stderr, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (mbs.on()) {  // in the user's order, as <out>.methstats
+    Sink ms;
+    ms.lit("mate1\n"); mbs.block(ms, pbat ? 1 : 0);
+    ms.lit("mate2\n"); mbs.block(ms, pbat ? 0 : 1);
+    mbs.write(out_file, ms);
+    mbs.close();
+  }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   dev.close();
   if (o.verbose)
@@ -1148,7 +1183,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1166,6 +1201,7 @@ int main(int argc, const char** argv) {
     for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
     if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
     if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
+    if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");

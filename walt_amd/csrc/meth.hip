@@ -407,20 +407,39 @@ int walt_index_has_reference(const walt_index* idx) { return idx && idx->ref[0] 
 }  // extern "C"
 
 namespace walt {
+// a bias set beside the calling (include/walt_amd.h, "methylation bias by read position"): same device, a table it has,
+// and calls to count
+static int mbias_with_calls_check(const walt_index* idx, const char* who, const walt_mbias* mb, uint32_t table, bool has_calls) {
+  if (mb->device != idx->device)
+    return fail(WALT_EINVAL, std::string(who) + ": the bias set lives on device " + std::to_string(mb->device) +
+                                 ", the index on device " + std::to_string(idx->device));
+  if (table >= mb->n_tables)
+    return fail(WALT_EINVAL, std::string(who) + ": table " + std::to_string(table) + " of a bias set with " + std::to_string(mb->n_tables));
+  if (!has_calls)
+    return fail(WALT_EINVAL, std::string(who) + ": the bias table is counted from the calls: d_calls must not be NULL when a bias set is given");
+  return WALT_OK;
+}
+
 // the two device forms (pile null: walt_meth_call_batch_device)
 static int meth_batch_device(const char* who, walt_index* idx, walt_pileup* pile, const void* d_bases, const void* d_offsets,
                              uint32_t n, const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                              int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
-                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr) {
+                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr,
+                             walt_mbias* mb = nullptr, uint32_t table = 0) {
   int rc = meth_args_check(idx, who, record_stride, d_conv, conv_stride, conversion);
   if (rc) return rc;
+  if (mb && (rc = mbias_with_calls_check(idx, who, mb, table, d_calls != nullptr))) return rc;
   if (d_skip && skip_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": skip stride 0 is smaller than its element (1)");
   if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
     return fail(WALT_EINVAL, std::string(who) + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
   if ((uintptr_t)d_excl & 3u) return fail(WALT_EINVAL, std::string(who) + ": excl must be 4-byte aligned");
-  return meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
-                     d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride, d_excl);
+  rc = meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
+                   d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride, d_excl);
+  if (rc || !mb) return rc;
+  // the bias table, from the calls just written: behind the calling kernel on the same stream
+  return mbias_launch(mb, table, d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride,
+                      reinterpret_cast<hipStream_t>(stream));
 }
 
 // the two host forms (pile null: walt_meth_call_batch)
@@ -428,10 +447,11 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
                            uint32_t n, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
                            int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
                            walt_meth_stats* stats, const uint8_t* skip = nullptr, size_t skip_stride = 0,
-                           const uint32_t* excl = nullptr) {
+                           const uint32_t* excl = nullptr, walt_mbias* mb = nullptr, uint32_t table = 0) {
   const std::string who(who_c);
   int rc = meth_args_check(idx, who_c, record_stride, conv, conv_stride, conversion);
   if (rc) return rc;
+  if (mb && (rc = mbias_with_calls_check(idx, who_c, mb, table, true))) return rc;
   if (skip && skip_stride < 1) return fail(WALT_EINVAL, who + ": skip stride 0 is smaller than its element (1)");
   if (n == 0) return WALT_OK;
   if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument");
@@ -442,7 +462,7 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
       return fail(WALT_EINVAL, who + ": conversion " + std::to_string((int)conv[(size_t)i * conv_stride]) +
                                    " of read " + std::to_string(i) + " is neither 'T' nor 'A'");
   }
-  if (!calls && !counts && !stats && !pile) return WALT_OK;
+  if (!calls && !counts && !stats && !pile && !mb) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   // the records and conversions as the kernel reads them: packed (the caller's strides stay on the host)
@@ -472,7 +492,7 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
   if (call_len && (rc = d_len.get((size_t)n * 4))) return rc;
   if (skip && (rc = d_skip.get(n))) return rc;
   if (excl && (rc = d_excl.get((size_t)n * 4))) return rc;
-  if (calls && (rc = d_calls.get(nbytes + 16))) return rc;
+  if ((calls || mb) && (rc = d_calls.get(nbytes + 16))) return rc;  // (the bias table is counted from the device copy)
   if (counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts)))) return rc;
   if (stats && (rc = d_stats.get(sizeof(walt_meth_stats)))) return rc;
   WALT_HIP(hipMemcpy(d_bases.p, bases + offsets[0], nbytes, hipMemcpyHostToDevice));
@@ -486,6 +506,7 @@ static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile
   rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
                    d_stats.p, nullptr, pile, d_skip.p, 1, d_excl.p);
   if (rc) return rc;
+  if (mb && (rc = mbias_launch(mb, table, d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1, nullptr))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
   if (counts) WALT_HIP(hipMemcpy(counts, d_counts.p, (size_t)n * sizeof(walt_meth_counts), hipMemcpyDeviceToHost));
@@ -577,6 +598,30 @@ int walt_meth_pileup_batch_excl(walt_index* idx, walt_pileup* p, const char* bas
   if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_excl");
   return meth_batch_host("walt_meth_pileup_batch_excl", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
                          conversion, call_len, calls, counts, stats, skip, skip_stride, excl);
+}
+
+// the excl forms plus a bias set (include/walt_amd.h, "methylation bias by read position"); mb null: the excl form
+int walt_meth_pileup_batch_mbias_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                        const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                        uint32_t table, void* stream) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_mbias_device: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_mbias_device");
+  return meth_batch_device("walt_meth_pileup_batch_mbias_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
+                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl,
+                           mb, table);
+}
+
+int walt_meth_pileup_batch_mbias(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                 const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                 int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                 walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                 walt_mbias* mb, uint32_t table) {
+  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_mbias: bad argument");
+  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_mbias");
+  return meth_batch_host("walt_meth_pileup_batch_mbias", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
+                         conversion, call_len, calls, counts, stats, skip, skip_stride, excl, mb, table);
 }
 
 }  // extern "C"

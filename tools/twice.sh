@@ -1,6 +1,9 @@
 #!/bin/bash
 # Diagnostic library on a GPU box: what parts of k_se_stage cost -- the run's gain when a part runs twice.
 #   bash tools/twice.sh <tag> [bench args...]   (bits: 1 fence search, 2 position fetch, 4 candidate list, 8 entry loads)
+# Since the first fence round's A pivot keys come with the slot's entries (map_common.h probe_entries_first) they are part
+# of bit 8 -- the slot's four loads per strand, entries or pivot keys -- and bit 1 repeats the rounds from the first B
+# sub-round on: figures of bit 1 from before that change (4.5 of 11.9 ms) included the first A sub-round.
 set -u
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"

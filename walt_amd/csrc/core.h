@@ -991,12 +991,12 @@ struct FencePlan {
   uint32_t sh, first, m;  // level, fence number of pivot 0, pivots (0: the search is finished)
 };
 WALT_HD uint32_t fence_ceil(uint32_t x, uint32_t sh) { return x ? ((x - 1u) >> sh) + 1u : 0u; }  // ceil(x / 2^sh), no overflow
-WALT_HD FencePlan fence_plan(const StrandView& sv, uint32_t x, uint32_t y) {
+WALT_HD FencePlan fence_plan(bool fences, uint32_t x, uint32_t y) {  // fences: the strand has fence keys (StrandView::fen)
   FencePlan p;
   p.sh = 0; p.first = x; p.m = 0;
   if (y <= x) return p;
   uint32_t sh = 0;
-  if (sv.fen[0] != nullptr) {
+  if (fences) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -1011,17 +1011,25 @@ WALT_HD FencePlan fence_plan(const StrandView& sv, uint32_t x, uint32_t y) {
   p.m = cnt < 16u ? cnt : 16u;                       // (more than 16 only without fences, or beyond 16 x 65536 entries)
   return p;
 }
-// where pivot i's key lies (i clamped to the plan's pivots; a finished search reads entry `safe`)
-WALT_HD const uint32_t* fence_ptr(const StrandView& sv, const FencePlan& p, uint32_t i, uint32_t safe) {
+WALT_HD FencePlan fence_plan(const StrandView& sv, uint32_t x, uint32_t y) { return fence_plan(sv.fen[0] != nullptr, x, y); }
+// where pivot i's key lies (i clamped to the plan's pivots; a finished search reads entry `safe`).  The five arrays come
+// as VALUES -- the entries, 12 bytes each, and fence levels 1 .. 4, 8 bytes a key: the heavy kernels hold them pinned in
+// scalar registers (map_common.h fence_round_dual), because the choice among the fields of a StrandView in memory is
+// compiled into a LOAD of the chosen field, a dependent memory access in front of the key loads.
+WALT_HD const uint32_t* fence_ptr_at(const uint32_t* e, const uint32_t* f1, const uint32_t* f2, const uint32_t* f3, const uint32_t* f4,
+                                     const FencePlan& p, uint32_t i, uint32_t safe) {
   const uint32_t ii = i < p.m ? i : (p.m ? p.m - 1u : 0u);
   const uint32_t sh = p.m ? p.sh : 0u;
   const uint64_t f = p.m ? (uint64_t)p.first + ii : (uint64_t)safe;
-  const uint32_t* base = reinterpret_cast<const uint32_t*>(sv.ent);
-  base = sh == 4 ? sv.fen[0] : base;
-  base = sh == 8 ? sv.fen[1] : base;
-  base = sh == 12 ? sv.fen[2] : base;
-  base = sh == 16 ? sv.fen[3] : base;
+  const uint32_t* base = e;
+  base = sh == 4 ? f1 : base;
+  base = sh == 8 ? f2 : base;
+  base = sh == 12 ? f3 : base;
+  base = sh == 16 ? f4 : base;
   return base + f * (sh ? 2u : 3u);
+}
+WALT_HD const uint32_t* fence_ptr(const StrandView& sv, const FencePlan& p, uint32_t i, uint32_t safe) {
+  return fence_ptr_at(reinterpret_cast<const uint32_t*>(sv.ent), sv.fen[0], sv.fen[1], sv.fen[2], sv.fen[3], p, i, safe);
 }
 WALT_HD uint64_t fence_load(const uint32_t* p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1032,6 +1040,24 @@ WALT_HD uint64_t fence_load(const uint32_t* p) {
 #else
   return ((uint64_t)p[0] << 32) | p[1];
 #endif
+}
+// Where the keys of the A pivots (3, 7, 11, 15) of a slot's FIRST fence round lie.  That round's plan is
+// fence_plan(lo, lo + ne), a pure function of the directory pair, so a caller that knows the pair can fetch these
+// keys together with whatever it loads next instead of waiting for them in the round (map_common.h
+// probe_entries_first).  key[j] is fence_ptr of pivot 4j + 3 (clamped to the plan's pivots as fence_ptr clamps it):
+// the two key words of an entry at level 0, of a fence key above; ne == 0 names entry 0 four times.
+// (the five arrays as values: see fence_ptr_at)
+WALT_HD FencePlan fence_first_keys(const uint32_t* e, const uint32_t* f1, const uint32_t* f2, const uint32_t* f3, const uint32_t* f4,
+                                   uint32_t lo, uint32_t ne, const uint32_t* key[4]) {
+  const FencePlan p = fence_plan(f1 != nullptr, lo, lo + ne);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (uint32_t j = 0; j < 4; ++j) key[j] = fence_ptr_at(e, f1, f2, f3, f4, p, 4 * j + 3, 0u);
+  return p;
+}
+WALT_HD FencePlan fence_first_keys(const StrandView& sv, uint32_t lo, uint32_t ne, const uint32_t* key[4]) {
+  return fence_first_keys(reinterpret_cast<const uint32_t*>(sv.ent), sv.fen[0], sv.fen[1], sv.fen[2], sv.fen[3], lo, ne, key);
 }
 WALT_HD void fence_narrow(const FencePlan& p, uint32_t c, uint32_t& x, uint32_t& y) {
   if (!p.m) return;

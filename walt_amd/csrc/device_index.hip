@@ -393,7 +393,7 @@ int finish_strand_device(walt_index* idx, int strand, uint32_t* g2, const uint32
       const uint64_t bytes_before = idx->device_bytes;
       for (uint32_t k = 0; k < kFenceLevels && have; ++k) {
         const uint64_t n_k = (((uint64_t)index_size - 1) >> (4 * (k + 1))) + 1;
-        have = dev_alloc(idx, &fen[k], 2 * n_k + 32) == WALT_OK;  // (+ slack: a clamped pivot never reads beyond, a whole line may)
+        have = dev_alloc(idx, &fen[k], 2 * n_k + 32) == WALT_OK;  // (+ slack: a clamped pivot never reads beyond, a whole line may; map_common.h probe_entries_first reads 12 bytes at a key of 8)
       }
       if (have) {
         hipLaunchKernelGGL(k_make_fences, dim3(grid_for(((uint64_t)index_size + 15) / 16)), dim3(kBlock), 0, stream, ent, index_size,

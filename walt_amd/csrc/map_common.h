@@ -367,6 +367,51 @@ __device__ __forceinline__ void probe_entries(const StrandView& sv, SlotProbe& p
     if (j < p.ne) p.e[j] = sv.ent[p.lo + j];
   }
 }
+// The heavy and staged kernels' form (the probes that probe_resolve_dual resolves).  There a slot of more than kScan
+// entries is searched by fence rounds and never looks at its first entries, and the first round's plan is a function of
+// the directory pair alone.  So such a lane spends its four loads on the keys of that round's A pivots (core.h
+// fence_first_keys) -- into the same registers, e[j] = pivot 4j + 3 -- and fence_round_dual<true> starts from them: the
+// search waits once less.  The loads are unconditional and the ADDRESS is selected (a load under a per-lane branch is
+// waited for at the end of the branch): a lane that wants no entry j reads entry 0, one broadcast access.  Twelve bytes
+// are read at a fence key of eight; the fence arrays end in slack that covers the last key (device_index.hip).
+// `fences`: dual_fences() of the two strands -- without fences the long slots keep their entries (kary_round).
+__device__ __forceinline__ bool dual_fences(const StrandView& svp, const StrandView& svm) {
+  return svp.fen[0] != nullptr && svm.fen[0] != nullptr;
+}
+template <typename T>
+__device__ __forceinline__ const T* sgpr_pin(const T* p) {  // a wave-uniform pointer, held in scalar registers from here on
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  asm volatile("" : "+s"(lo), "+s"(hi));
+  return reinterpret_cast<const T*>(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ void probe_entries_first(const StrandView& sv, SlotProbe& p, bool fences) {
+  static_assert(kScan == 4, "e[] holds the four A pivots of a fence round");
+  typedef uint32_t __attribute__((address_space(1))) gword;  // global loads, not FLAT ones (map_items.h load_global)
+  const bool lng = fences && p.ne > kScan;
+  // The five arrays' addresses are pinned in scalar registers first.  Left to itself hipcc turns the choice among
+  // them into ONE load of the pointer from the selected field of the kernel's argument block -- a per-lane load that
+  // the key loads depend on, and whose wait (vmcnt counts in order) also waits for the other strand's keys.
+  const uint32_t* const be = sgpr_pin(reinterpret_cast<const uint32_t*>(sv.ent));
+  const uint32_t* const b1 = fences ? sgpr_pin(sv.fen[0]) : nullptr;  // (no fences: the plan's level is 0, the entries)
+  const uint32_t *const b2 = sgpr_pin(sv.fen[1]), *const b3 = sgpr_pin(sv.fen[2]), *const b4 = sgpr_pin(sv.fen[3]);
+  const uint32_t* key[4];
+  fence_first_keys(be, b1, b2, b3, b4, p.lo, lng ? p.ne : 0u, key);
+#pragma unroll
+  for (uint32_t j = 0; j < kScan; ++j) {
+    const bool own = j < p.ne && !(j == 0 && p.inl);  // the slot's entry j is wanted
+    const uint32_t* at = lng ? key[j] : be + 3ull * (own ? p.lo + j : 0u);
+    const gword* q = reinterpret_cast<const gword*>(reinterpret_cast<uintptr_t>(at));
+    Ent e;
+    e.key_hi = q[0]; e.key_lo = q[1]; e.pos = q[2];
+    Ent z;  // what a lane that wants no entry j holds: e[0] as probe_issue left it (the inline entry of a one-entry slot), else zeros
+    z.key_hi = z.key_lo = z.pos = 0;
+    if (j == 0) z = p.e[0];
+    p.e[j].key_hi = (lng || own) ? e.key_hi : z.key_hi;
+    p.e[j].key_lo = (lng || own) ? e.key_lo : z.key_lo;
+    p.e[j].pos = (lng || own) ? e.pos : z.pos;
+  }
+}
 // kernel instances for reads of up to 16 NW bases: can a seed exceed the 44 care characters of hash + key?
 // (pattern 3: NW > 8, reads above 134 bases; pattern 5: NW >= 8, from 119 bases; pattern 7: every instance, from 90)
 template <int NW>
@@ -446,8 +491,13 @@ __device__ __forceinline__ void probe_resolve(const StrandView& sv, const SlotPr
 // lock-step: the A pivots of all of them are loaded together, then the B pivots.  While the two searches of a strand
 // still share their range (and quarter) the second one needs no loads of its own; the wavefront skips them when that
 // holds for all of its lanes (a uniform branch: the loads in it are the last before the values are needed anyway).
+// FIRST: the first round of a search whose probes came from probe_entries_first.  Its plans are those of the whole slots,
+// the keys of its A pivots are pp.e[] / pm.e[] already, and the two searches of a strand share their range: the A
+// sub-round issues no load and waits for nothing, and there is no A2 branch.  Everything else is the round as it is.
+template <bool FIRST = false>
 __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const StrandView& svm, KaryState* ks, uint64_t T,
-                                                 uint64_t M, uint32_t safe_p, uint32_t safe_m) {
+                                                 uint64_t M, uint32_t safe_p, uint32_t safe_m, const SlotProbe* pp = nullptr,
+                                                 const SlotProbe* pm = nullptr) {
   // Round 4: (1) at most ONE set of pivot keys is live at a time -- while the two searches of a strand share their
   // range the second one's counts are taken from the first one's keys (the words it would load are the same), and its
   // own loads are issued only inside the wave-uniform branch that needs them; (2) a search that is finished (or never
@@ -456,7 +506,19 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
   // a lane whose slot is EMPTY some other slot's entry, i.e. a random HBM line fetched for nothing.  The loads stay
   // unconditional: a load under a per-lane branch is waited for at the end of that branch, and eight of them in a row
   // made a sub-round eight round trips (tried: 12.1 -> 15.4 ms).  Same pivots, same counts, same ranges.
+  // The rounds' pivot addresses are computed from the strands' five arrays held as scalar values (core.h fence_ptr_at).
+  // fence_ptr's choice among the FIELDS of a StrandView was compiled into a per-lane load of the chosen field from the
+  // kernel's argument block: every sub-round first waited for a pointer, and as vmcnt counts in order the second
+  // strand's pointer also waited for the first strand's keys -- three dependent waits where the sub-round needs one.
   (void)safe_p; (void)safe_m;
+  const uint32_t *ae[2], *f1[2], *f2[2], *f3[2], *f4[2];  // entries and fence levels 1 .. 4 of the two strands
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const StrandView& sv = f ? svm : svp;
+    ae[f] = sgpr_pin(reinterpret_cast<const uint32_t*>(sv.ent));
+    f1[f] = sgpr_pin(sv.fen[0]); f2[f] = sgpr_pin(sv.fen[1]); f3[f] = sgpr_pin(sv.fen[2]); f4[f] = sgpr_pin(sv.fen[3]);
+  }
+  auto pivot_at = [&](int f, const FencePlan& pl, uint32_t i) { return fence_ptr_at(ae[f], f1[f], f2[f], f3[f], f4[f], pl, i, 0u); };
   FencePlan p1[2], p2[2];
   bool same[2];
 #pragma unroll
@@ -473,7 +535,8 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (uint32_t j = 0; j < 4; ++j) {
-        a1[f][j] = fence_load(fence_ptr(f ? svm : svp, p1[f], 4 * j + 3, 0u));
+        if constexpr (FIRST) a1[f][j] = ent_key((f ? pm : pp)->e[j]);
+        else a1[f][j] = fence_load(pivot_at(f, p1[f], 4 * j + 3));
       }
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -481,7 +544,7 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
       q2[f] = fence_count4(p2[f], a1[f], 3, 4, 4, T, M, false);  // (right when same[f]: p2 == p1 and the keys are these)
     }
   }
-  if (__ballot((!same[0] && p2[0].m) || (!same[1] && p2[1].m))) {
+  if (!FIRST && __ballot((!same[0] && p2[0].m) || (!same[1] && p2[1].m))) {
     uint64_t a2[2][4];
 #pragma unroll
     for (int f = 0; f < 2; ++f)
@@ -489,7 +552,7 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
       for (uint32_t j = 0; j < 4; ++j) {
         FencePlan pz = p2[f];
         pz.m = same[f] ? 0u : pz.m;  // (its counts come from the first search's keys)
-        a2[f][j] = fence_load(fence_ptr(f ? svm : svp, pz, 4 * j + 3, 0u));
+        a2[f][j] = fence_load(pivot_at(f, pz, 4 * j + 3));
       }
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -504,7 +567,7 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
     for (int f = 0; f < 2; ++f) {
 #pragma unroll
       for (uint32_t j = 0; j < 3; ++j) {
-        b1[f][j] = fence_load(fence_ptr(f ? svm : svp, p1[f], 4 * q1[f] + j, 0u));
+        b1[f][j] = fence_load(pivot_at(f, p1[f], 4 * q1[f] + j));
       }
       b1[f][3] = 0;
     }
@@ -523,7 +586,7 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
       for (uint32_t j = 0; j < 3; ++j) {
         FencePlan pz = p2[f];
         pz.m = mine ? pz.m : 0u;
-        b2[f][j] = fence_load(fence_ptr(f ? svm : svp, pz, 4 * q2[f] + j, 0u));
+        b2[f][j] = fence_load(pivot_at(f, pz, 4 * q2[f] + j));
       }
       b2[f][3] = 0;
     }
@@ -549,6 +612,8 @@ __device__ __forceinline__ void fence_round_dual(const StrandView& svp, const St
 //      (the small-region verification and lit_region_small want them in registers),
 //   3. each strand finishes as probe_resolve does (tail characters of long seeds).
 // Same regions as probe_resolve: the equal range of a key in a sorted slot does not depend on how it is searched.
+// pp / pm come from probe_entries_first: with fences, e[] of a slot of more than kScan entries holds the keys of the
+// first fence round's A pivots, not the slot's first entries.
 // DEFER (the staged kernels, reads above 134 bases): a key-equal range of more than `defer_min` slots that lies inside
 // dense candidate windows is NOT narrowed here by the care characters behind the key (>= 44; lit_region: a
 // LowerBound / UpperBound bisection per character, each step an entry load and a dependent genome load) -- the whole
@@ -602,18 +667,26 @@ __device__ __forceinline__ void probe_resolve_dual(const StrandView& svp, const 
       kary_init(ks[f], p.lo, p.lo + p.ne);
     }
   }
-  if (svp.fen[0] != nullptr && svm.fen[0] != nullptr) {  // uniform
+  if (dual_fences(svp, svm)) {  // uniform
+    // (the first round's A keys came with the probes: probe_entries_first, fence_round_dual<true>)
 #if defined(WALT_DIAG)
     if (WALT_DIAG_TWICE(0)) {
       KaryState k2[2] = {ks[0], ks[1]};
+      if (kary_busy(k2[0]) || kary_busy(k2[1])) fence_round_dual<true>(svp, svm, k2, T, M, pp.lo, pm.lo, &pp, &pm);
       while (kary_busy(k2[0]) || kary_busy(k2[1])) fence_round_dual(svp, svm, k2, T, M, pp.lo, pm.lo);
       if (k2[0].x1 == 0xFFFFFFF0u) ks[0] = k2[0];  // (keeps the copy alive)
     }
 #endif
-    while (kary_busy(ks[0]) || kary_busy(ks[1])) {
+    if (kary_busy(ks[0]) || kary_busy(ks[1])) {
       WALT_DIAG_COUNT(0, 1);                                                        // fence rounds run by a wavefront
       WALT_DIAG_COUNT(1, __popcll(__ballot(kary_busy(ks[0]) || kary_busy(ks[1]))));  // ... and the lanes that needed them
       WALT_DIAG_COUNT(6, __popcll(__ballot(kary_busy(ks[0]))) + __popcll(__ballot(kary_busy(ks[1]))));  // searches busy
+      fence_round_dual<true>(svp, svm, ks, T, M, pp.lo, pm.lo, &pp, &pm);
+    }
+    while (kary_busy(ks[0]) || kary_busy(ks[1])) {
+      WALT_DIAG_COUNT(0, 1);
+      WALT_DIAG_COUNT(1, __popcll(__ballot(kary_busy(ks[0]) || kary_busy(ks[1]))));
+      WALT_DIAG_COUNT(6, __popcll(__ballot(kary_busy(ks[0]))) + __popcll(__ballot(kary_busy(ks[1]))));
       fence_round_dual(svp, svm, ks, T, M, pp.lo, pm.lo);
     }
   } else {

@@ -555,8 +555,8 @@ __device__ __forceinline__ void pe_stage_dual(const IndexView& iv, BlockShared& 
     }
     pp.ne = (need_p && !lit_p && hi_p > pp.lo) ? hi_p - pp.lo : 0u;
     pm.ne = (need_m && !lit_m && hi_m > pm.lo) ? hi_m - pm.lo : 0u;
-    probe_entries(svp, pp);
-    probe_entries(svm, pm);
+    probe_entries_first(svp, pp, dual_fences(svp, svm));  // (long slots: the first fence round's A pivots, not entries)
+    probe_entries_first(svm, pm, dual_fences(svp, svm));
     Lookup lp, lm;
     bool tail_p, tail_m;
     bool defer_p = false, defer_m = false;  // long seeds: the verifier narrows the key-equal range (map_common.h DEFER)

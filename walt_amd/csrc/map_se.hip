@@ -696,8 +696,13 @@ __device__ __forceinline__ void se_process_dual(const IndexView& iv, BlockShared
       need_p = need_m = false;
       pp.ne = pm.ne = 0;
     }
-    probe_entries(svp, pp);
-    probe_entries(svm, pm);
+    if constexpr (HEAVY) {  // (probe_resolve_dual: long slots fetch their first fence round's pivots)
+      probe_entries_first(svp, pp, dual_fences(svp, svm));
+      probe_entries_first(svm, pm, dual_fences(svp, svm));
+    } else {
+      probe_entries(svp, pp);
+      probe_entries(svm, pm);
+    }
     Lookup lp, lm;
     bool tail_p, tail_m;
     if constexpr (HEAVY) {
@@ -1322,16 +1327,17 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
       pp.ne = (need_p && !lit_p && hi_p > pp.lo) ? hi_p - pp.lo : 0u;
       pm.ne = (need_m && !lit_m && hi_m > pm.lo) ? hi_m - pm.lo : 0u;
 #if defined(WALT_DIAG)
-      if (WALT_DIAG_TWICE(3)) {  // (other lines of the same slots: the entries behind the first four)
-        SlotProbe p2 = pp, m2 = pm;
-        p2.lo += p2.ne > 64 ? 48 : 0; m2.lo += m2.ne > 64 ? 48 : 0;
-        probe_entries(svp, p2);
-        probe_entries(svm, m2);
+      if (WALT_DIAG_TWICE(3)) {  // the slot's four loads once more, on other lines: a long slot without its first 48 entries
+        SlotProbe p2 = pp, m2 = pm;  // (still inside the slot and still long: the A pivot keys of that range's first plan)
+        if (p2.ne > 64) { p2.lo += 48; p2.ne -= 48; }
+        if (m2.ne > 64) { m2.lo += 48; m2.ne -= 48; }
+        probe_entries_first(svp, p2, dual_fences(svp, svm));
+        probe_entries_first(svm, m2, dual_fences(svp, svm));
         if (p2.e[1].pos == 0xFFFFFFF0u && m2.e[1].pos == 0xFFFFFFF1u) pp.lo = 0;  // (keeps the loads alive)
       }
 #endif
-      probe_entries(svp, pp);
-      probe_entries(svm, pm);
+      probe_entries_first(svp, pp, dual_fences(svp, svm));  // (long slots: the first fence round's A pivots, not entries)
+      probe_entries_first(svm, pm, dual_fences(svp, svm));
       Lookup lp, lm;
       bool tail_p, tail_m;
       bool defer_p = false, defer_m = false;  // long seeds: the verifier narrows the key-equal range (map_common.h DEFER)

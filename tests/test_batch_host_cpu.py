@@ -3,7 +3,11 @@
 refusals (a decreasing pair, a read above 1024 bases) with their messages, the running maximum over one or two read
 sets, and the offsets relative to the first read.  The harness is built twice, plain and with
 -fsanitize=address,undefined, and keeps every offsets array in a heap block of exactly n + 1 words, so the second build
-also pins that nothing beyond offsets[n] is read."""
+also pins that nothing beyond offsets[n] is read.
+
+The same header holds what the host forms of the methylation-side calls share (meth.hip, mbias.hip, dedup.hip): a strided
+array packed into a dense one, the stride and conversion refusals, and the per-read checks of the calling call in the
+order a caller sees them.  The harness drives those from its command line, under both builds."""
 import os
 import subprocess
 
@@ -48,6 +52,13 @@ def batch_host(request, scratch):
         os.remove(fout)
         return res
 
+    def piece(*args):
+        """the harness's command-line modes (pack, refuse, reads) -> the line it printed"""
+        pr = subprocess.run([exe] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
+        assert pr.returncode == 0, "batch_host_harness (%s) %s exit %d:\n%s" % (request.param, args, pr.returncode, pr.stdout[-4000:])
+        return pr.stdout.rstrip("\n")
+
+    run.piece = piece
     return run
 
 
@@ -126,3 +137,55 @@ def test_two_mates_share_the_maximum(batch_host):
     # a refusal in the second mate ends the call there
     res = batch_host(m1, [0, 100, 99, 200])
     assert [r[0] for r in res] == [None, DECREASING]
+
+
+# ---------------------------------------------------------------------------
+# what the methylation-side host forms share
+# ---------------------------------------------------------------------------
+RECORD_STRIDE = "record stride %d is smaller than a walt_best_match (16) or not a multiple of 4"
+CONV_STRIDE = "conv stride 0 is smaller than its element (1)"
+SKIP_STRIDE = "skip stride 0 is smaller than its element (1)"
+CONVERSION = "conversion %d is neither 'T' nor 'A'"
+T, A, C = ord("T"), ord("A"), ord("C")
+
+
+@pytest.mark.parametrize("n", [0, 1, 3])
+@pytest.mark.parametrize("elem,stride", [(16, 16), (16, 20), (16, 64), (1, 1), (1, 2), (1, 64)])
+def test_strided_packing_reads_the_element_and_no_more(batch_host, elem, stride, n):
+    """the source is a heap block that ends with the last element: the sanitised build reports a read of `stride` bytes
+    there; the harness compares the packed output element by element"""
+    assert batch_host.piece("pack", elem, stride, n) == "ok"
+
+
+def test_each_shared_refusal_alone_and_its_accepted_neighbours(batch_host):
+    piece = batch_host.piece
+    for stride in (8, 12, 18):
+        assert piece("refuse", "record", stride) == RECORD_STRIDE % stride
+    assert piece("refuse", "record", 16) == "ok" and piece("refuse", "record", 20) == "ok"
+    # a conv / skip stride of 0 with an array; without one the stride is not looked at
+    assert piece("refuse", "conv", 1, 0, T) == CONV_STRIDE and piece("refuse", "conv", 1, 1, T) == "ok"
+    assert piece("refuse", "skip", 1, 0) == SKIP_STRIDE and piece("refuse", "skip", 1, 1) == "ok"
+    assert piece("refuse", "skip", 0, 0) == "ok"
+    # a batch-wide conversion with no array; with one the batch-wide value is not looked at
+    assert piece("refuse", "conv", 0, 0, C) == CONVERSION % C
+    assert piece("refuse", "conv", 0, 0, T) == "ok" and piece("refuse", "conv", 0, 0, A) == "ok"
+    assert piece("refuse", "conv", 1, 1, C) == "ok"
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+def test_several_faults_in_one_batch_report_the_first_by_read_then_by_check(batch_host, stride):
+    """read i's order, then its length, then its conversion byte, before anything of read i + 1"""
+    piece = batch_host.piece
+    bad_conv = "who: conversion %d of read %%d is neither 'T' nor 'A'" % C
+    # a bad conversion byte at read 0, 1,025 bases at read 1
+    assert piece("reads", stride, 3, 0, 5, 1030, 1035, C, T, T) == bad_conv % 0
+    # 1,025 bases and a bad conversion byte, both at read 0
+    assert piece("reads", stride, 3, 0, 1025, 1030, 1035, C, T, T) == TOO_LONG
+    # a decreasing pair at read 1, a bad conversion byte at read 2
+    assert piece("reads", stride, 3, 0, 50, 40, 1035, T, T, C) == DECREASING
+    # each alone, the last read included; none; no conversions at all; no reads
+    assert piece("reads", stride, 3, 0, 50, 100, 150, T, A, C) == bad_conv % 2
+    assert piece("reads", stride, 3, 0, 50, 100, 1125, T, A, T) == TOO_LONG
+    assert piece("reads", stride, 3, 0, 50, 100, 99, T, A, T) == DECREASING
+    assert piece("reads", stride, 3, 0, 50, 100, 1124, T, A, T) == "ok"
+    assert piece("reads", stride, 3, 0, 50, 100, 150) == "ok" and piece("reads", stride, 0, 7) == "ok"

@@ -290,6 +290,60 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+# What the methylation-side calls take: a 1-d array or strided view with n elements, read in place.  Each helper returns
+# (the array to keep alive, its address or None when n == 0, its stride in bytes).
+def _records_arg(records, n=None):
+    records = np.asarray(records)
+    if records.dtype != best_match_dtype or records.ndim != 1 or (n is not None and records.shape[0] != n):
+        raise ValueError("records: a 1-d best_match_dtype array (or view)" + (" with one element per read" if n is not None else ""))
+    n = records.shape[0]
+    stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
+    if stride < 0:
+        records, stride = np.ascontiguousarray(records), best_match_dtype.itemsize
+    return records, records.ctypes.data if n else None, stride
+
+
+def _bytes_arg(a, n, error):
+    """conv or skip: uint8, any positive stride"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(error)
+    stride = a.strides[0] if n > 1 else 1
+    if stride <= 0:
+        a, stride = np.ascontiguousarray(a), 1
+    return a, a.ctypes.data if n else None, stride
+
+
+def _conv_arg(conv, n, per="read"):
+    """'T' / 'A' for the whole batch, or one byte per read -> (array to keep alive, address, stride, conversion)"""
+    if isinstance(conv, (str, bytes)):
+        return None, None, 0, ord(conv)
+    return _bytes_arg(conv, n, "conv: 'T', 'A' or a 1-d uint8 array with one element per %s" % per) + (0,)
+
+
+def _skip_arg(skip, n):
+    if skip is None:
+        return None, None, 1
+    return _bytes_arg(skip, n, "skip: a 1-d uint8 array with one element per read")
+
+
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip"):
+    """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
+    stride), excl = (address,), mbias = (handle, table), each None when the caller gave none.  The narrowest form that
+    takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a call with skip only.
+    Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
+    widest = "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    if widest is None:
+        name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
+    else:  # (these three take a null pile-up, a null skip and a null excl)
+        name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
+        if widest != "skip":
+            tail += excl or (None,)
+        if widest == "mbias":
+            tail += mbias
+    return getattr(L, name + ("_device" if device else "")), head, tail
+
+
 def pack_reads(seqs):
     """list of str/bytes -> (bases uint8[total], offsets uint64[n+1])."""
     bs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
@@ -611,22 +665,8 @@ class Index:
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
-        records = np.asarray(records)
-        if records.dtype != best_match_dtype or records.ndim != 1 or records.shape[0] != n:
-            raise ValueError("records: a 1-d best_match_dtype array (or view) with one element per read")
-        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
-        if rec_stride < 0:
-            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
-        conv_arr, conv_stride, conversion = None, 0, 0
-        if isinstance(conv, (str, bytes)):
-            conversion = ord(conv)
-        else:
-            conv_arr = np.asarray(conv)
-            if conv_arr.dtype != np.uint8 or conv_arr.ndim != 1 or conv_arr.shape[0] != n:
-                raise ValueError("conv: 'T', 'A' or a 1-d uint8 array with one element per read")
-            conv_stride = conv_arr.strides[0] if n > 1 else 1
-            if conv_stride <= 0:
-                conv_arr, conv_stride = np.ascontiguousarray(conv_arr), 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        conv_arr, conv_ptr, conv_stride, conversion = _conv_arg(conv, n)
         cl = None if call_len is None else np.ascontiguousarray(call_len, dtype=np.uint32)
         if cl is not None and cl.size != n:
             raise ValueError("call_len: one element per read")
@@ -637,34 +677,17 @@ class Index:
             stats = np.zeros(1, dtype=meth_stats_dtype)
         # calls is indexed like bases: offsets[0] bytes in front of the first read belong to neither
         calls_ptr = None if calls is None else calls.ctypes.data - int(offsets[0]) if n else calls.ctypes.data
-        bases_ptr = bases.ctypes.data
-        tail = (bases_ptr, _ptr(offsets), n, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
-                conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats))
-        skip_arr, skip_stride = None, 1
-        if skip is not None:
-            skip_arr = np.asarray(skip)
-            if skip_arr.dtype != np.uint8 or skip_arr.ndim != 1 or skip_arr.shape[0] != n:
-                raise ValueError("skip: a 1-d uint8 array with one element per read")
-            skip_stride = skip_arr.strides[0] if n > 1 else 1
-            if skip_stride <= 0:
-                skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
         excl_arr = None
         if excl is not None:
             excl_arr = np.ascontiguousarray(excl, dtype=np.uint32)
             if excl_arr.ndim != 1 or excl_arr.shape[0] != n:
                 raise ValueError("excl: a 1-d uint32 array with one word per read")
-        if mbias is not None:
-            self._ck(self._L.walt_meth_pileup_batch_mbias(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride,
-                                                          _ptr(excl_arr) if n else None, mbias.handle, int(mbias_table)))
-        elif excl is not None:
-            self._ck(self._L.walt_meth_pileup_batch_excl(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride,
-                                                         _ptr(excl_arr) if n else None))
-        elif skip is not None:
-            self._ck(self._L.walt_meth_pileup_batch_skip(self._h, pile, *tail, _ptr(skip_arr) if n else None, skip_stride))
-        elif pile is None:
-            self._ck(self._L.walt_meth_call_batch(self._h, *tail))
-        else:
-            self._ck(self._L.walt_meth_pileup_batch(self._h, pile, *tail))
+        form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
+                                      excl is not None and (_ptr(excl_arr) if n else None,),
+                                      mbias is not None and (mbias.handle, int(mbias_table)))
+        self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
+                      conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
@@ -674,20 +697,18 @@ class Index:
         whose table mbias_table takes the calls too (walt_meth_pileup_batch_mbias_device with a null pile-up; d_calls
         must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
         pile-up)."""
-        if mbias is not None:
-            self._ck(self._L.walt_meth_pileup_batch_mbias_device(
-                self._h, None, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, mbias.handle,
-                int(mbias_table), stream))
-            return
-        if d_skip is not None or d_excl is not None:
-            self._ck(self._L.walt_meth_pileup_batch_excl_device(
-                self._h, None, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, stream))
-            return
-        self._ck(self._L.walt_meth_call_batch_device(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride),
-                                                     d_conv, int(conv_stride), ord(conversion), d_call_len, d_calls,
-                                                     d_counts, d_stats, stream))
+        batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
+                 d_calls, d_counts, d_stats)
+        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table)
+
+    def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table):
+        """Index.meth_call_batch_device (pile null) and Pileup.add_batch_device.  batch: the C arguments from d_bases to
+        d_stats; skip_alone: the form a call with d_skip only goes to (the index's: walt_meth_pileup_batch_excl_device, a
+        pile-up's: walt_meth_pileup_batch_skip_device)."""
+        form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
+                                      d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
+                                      skip_alone)
+        self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
     def set_option(self, name, value):
@@ -795,25 +816,9 @@ class Pileup:
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
         MBias set whose table mbias_table takes the calls too (d_calls must be given)."""
-        if mbias is not None:
-            self._index._ck(self._L.walt_meth_pileup_batch_mbias_device(
-                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, mbias.handle,
-                int(mbias_table), stream))
-            return
-        if d_excl is not None:
-            self._index._ck(self._L.walt_meth_pileup_batch_excl_device(
-                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), d_excl, stream))
-            return
-        if d_skip is not None:
-            self._index._ck(self._L.walt_meth_pileup_batch_skip_device(
-                self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-                ord(conversion), d_call_len, d_calls, d_counts, d_stats, d_skip, int(skip_stride), stream))
-            return
-        self._index._ck(self._L.walt_meth_pileup_batch_device(
-            self._index._h, self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
-            ord(conversion), d_call_len, d_calls, d_counts, d_stats, stream))
+        batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
+                 d_calls, d_counts, d_stats)
+        self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table)
 
     def extract(self, pos_lo=0, pos_hi=None):
         """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the
@@ -876,26 +881,11 @@ class Dedup:
     def add_batch(self, records, conv="T", kind=0):
         """records: a best_match_dtype array or strided view (e.g. the m1 field of a pair_result_dtype array); conv: 'T' /
         'A' for all, or a uint8 array per record (any stride).  Returns dup uint8[n]."""
-        records = np.asarray(records)
-        if records.dtype != best_match_dtype or records.ndim != 1:
-            raise ValueError("records: a 1-d best_match_dtype array (or view)")
+        records, rec_ptr, rec_stride = _records_arg(records)
         n = records.shape[0]
-        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
-        if rec_stride < 0:
-            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
-        conv_arr, conv_stride, conversion = None, 0, 0
-        if isinstance(conv, (str, bytes)):
-            conversion = ord(conv)
-        else:
-            conv_arr = np.asarray(conv)
-            if conv_arr.dtype != np.uint8 or conv_arr.ndim != 1 or conv_arr.shape[0] != n:
-                raise ValueError("conv: 'T', 'A' or a 1-d uint8 array with one element per record")
-            conv_stride = conv_arr.strides[0] if n > 1 else 1
-            if conv_stride <= 0:
-                conv_arr, conv_stride = np.ascontiguousarray(conv_arr), 1
+        conv_arr, conv_ptr, conv_stride, conversion = _conv_arg(conv, n, "record")
         dup = np.zeros(n, dtype=np.uint8)
-        self._ck(self._L.walt_dedup_batch(self._h, records.ctypes.data if n else None, rec_stride, _ptr(conv_arr) if n else None,
-                                          conv_stride, conversion, int(kind), n, _ptr(dup)))
+        self._ck(self._L.walt_dedup_batch(self._h, rec_ptr, rec_stride, conv_ptr, conv_stride, conversion, int(kind), n, _ptr(dup)))
         return dup
 
     def add_pairs(self, pairs, conv="T"):
@@ -981,23 +971,10 @@ class MBias:
         calls = np.ascontiguousarray(calls, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
-        records = np.asarray(records)
-        if records.dtype != best_match_dtype or records.ndim != 1 or records.shape[0] != n:
-            raise ValueError("records: a 1-d best_match_dtype array (or view) with one element per read")
-        rec_stride = records.strides[0] if n > 1 else best_match_dtype.itemsize
-        if rec_stride < 0:
-            records, rec_stride = np.ascontiguousarray(records), best_match_dtype.itemsize
-        skip_arr, skip_stride = None, 1
-        if skip is not None:
-            skip_arr = np.asarray(skip)
-            if skip_arr.dtype != np.uint8 or skip_arr.ndim != 1 or skip_arr.shape[0] != n:
-                raise ValueError("skip: a 1-d uint8 array with one element per read")
-            skip_stride = skip_arr.strides[0] if n > 1 else 1
-            if skip_stride <= 0:
-                skip_arr, skip_stride = np.ascontiguousarray(skip_arr), 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
         calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
-        self._ck(self._L.walt_mbias_batch(self._h, int(table), calls_ptr, _ptr(offsets), n, records.ctypes.data if n else None,
-                                          rec_stride, _ptr(skip_arr) if n else None, skip_stride))
+        self._ck(self._L.walt_mbias_batch(self._h, int(table), calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
 
     def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, table=0, stream=0):
         """Device-pointer form (ints are HBM addresses on the set's device, stream a hipStream_t value); asynchronous."""

@@ -194,20 +194,28 @@ static int dd_reserve(walt_dedup* dd, const char* who, uint64_t n_more) {
 }
 
 static int dd_args_check(const char* who, size_t rec_stride, const void* conv, size_t conv_stride, int conversion) {
-  if (rec_stride < sizeof(walt_best_match) || rec_stride % 4)
-    return fail(WALT_EINVAL, std::string(who) + ": record stride " + std::to_string(rec_stride) +
-                                 " is smaller than a walt_best_match (16) or not a multiple of 4");
-  if (conv && conv_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": conv stride 0 is smaller than its element (1)");
-  if (!conv && conversion != 'T' && conversion != 'A')
-    return fail(WALT_EINVAL, std::string(who) + ": conversion " + std::to_string(conversion) + " is neither 'T' nor 'A'");
-  return WALT_OK;
+  std::string bad = record_stride_refusal(rec_stride);
+  if (bad.empty()) bad = conv_refusal(conv, conv_stride, conversion);
+  return bad.empty() ? WALT_OK : fail(WALT_EINVAL, std::string(who) + ": " + bad);
 }
 
+// one batch as the kernels read it (device arrays); pairs: walt_pair_result records, two conversions and two verdicts each
+struct DedupBatch {
+  bool pairs;
+  const void* records;
+  size_t rec_stride;
+  const void* conv;
+  size_t conv_stride;
+  int conversion, kind;
+  uint32_t n;
+  void* dup;
+};
+
 // insert, then mark, on `stream`; the host's bound on the keys moves by what the call can add
-static int dd_launch(walt_dedup* dd, const char* who, bool pairs, const void* d_records, size_t rec_stride, const void* d_conv,
-                     size_t conv_stride, int conversion, int kind, uint32_t n, void* d_dup, hipStream_t stream) {
+static int dd_launch(walt_dedup* dd, const char* who, const DedupBatch& b, hipStream_t stream) {
+  const uint32_t n = b.n;
   if (n == 0) return WALT_OK;
-  const uint64_t can_add = pairs ? 2ull * n : (uint64_t)n;
+  const uint64_t can_add = b.pairs ? 2ull * n : (uint64_t)n;
   if (dd->known_keys + dd->maybe_keys + can_add > dd->slots / 2)
     return fail(WALT_EINVAL, std::string(who) + ": the set may hold " + std::to_string(dd->known_keys + dd->maybe_keys) + " keys and this call may add " +
                                  std::to_string(can_add) + ", more than half of its " + std::to_string(dd->slots) +
@@ -215,17 +223,17 @@ static int dd_launch(walt_dedup* dd, const char* who, bool pairs, const void* d_
   WALT_HIP(hipSetDevice(dd->device));
   DedupArgs a;
   a.key = dd->key; a.first = dd->first; a.mask = dd->slots - 1; a.ctl = dd->ctl;
-  a.records = static_cast<const uint8_t*>(d_records);
-  a.rec_stride = rec_stride;
-  a.conv = static_cast<const uint8_t*>(d_conv);
-  a.conv_stride = conv_stride;
-  a.conversion = (uint32_t)conversion;
-  a.kind = (uint32_t)kind;
+  a.records = static_cast<const uint8_t*>(b.records);
+  a.rec_stride = b.rec_stride;
+  a.conv = static_cast<const uint8_t*>(b.conv);
+  a.conv_stride = b.conv_stride;
+  a.conversion = (uint32_t)b.conversion;
+  a.kind = (uint32_t)b.kind;
   a.n = n;
   a.ordinal0 = dd->fed;
-  a.dup = static_cast<uint8_t*>(d_dup);
+  a.dup = static_cast<uint8_t*>(b.dup);
   const dim3 grid(grid_for(n)), block(kBlock);
-  if (pairs) {
+  if (b.pairs) {
     hipLaunchKernelGGL(k_dedup_insert<true>, grid, block, 0, stream, a);
     hipLaunchKernelGGL(k_dedup_mark<true>, grid, block, 0, stream, a);
   } else {
@@ -238,13 +246,7 @@ static int dd_launch(walt_dedup* dd, const char* who, bool pairs, const void* d_
   return WALT_OK;
 }
 
-struct Scoped {
-  void* p = nullptr;
-  ~Scoped() { if (p) (void)hipFree(p); }
-  int get(size_t bytes) {
-    return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (duplicates)");
-  }
-};
+constexpr const char* kWhat = "duplicates";  // a host form's device temporaries, as its out-of-memory message names them
 
 // the end of a host form: wait, the error word, the verdicts
 static int dd_finish(walt_dedup* dd, const char* who, uint8_t* dup, const void* d_dup, size_t bytes) {
@@ -341,7 +343,7 @@ int walt_dedup_batch_device(walt_dedup* dd, const void* d_records, size_t record
   if (kind < 0 || kind > 2) return fail(WALT_EINVAL, std::string(who) + ": kind " + std::to_string(kind) + " is not 0, 1 or 2");
   if (n && (!d_records || !d_dup)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if ((uintptr_t)d_records & 3u) return fail(WALT_EINVAL, std::string(who) + ": records must be 4-byte aligned");
-  return dd_launch(dd, who, false, d_records, record_stride, d_conv, conv_stride, conversion, kind, n, d_dup,
+  return dd_launch(dd, who, {false, d_records, record_stride, d_conv, conv_stride, conversion, kind, n, d_dup},
                    reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -352,7 +354,7 @@ int walt_dedup_pairs_batch_device(walt_dedup* dd, const void* d_pairs, const voi
   if (rc || (rc = dd_args_check(who, kPairStride, d_conv, 2, conversion))) return rc;
   if (n && (!d_pairs || !d_dup)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if ((uintptr_t)d_pairs & 15u) return fail(WALT_EINVAL, std::string(who) + ": pairs must be 16-byte aligned");
-  return dd_launch(dd, who, true, d_pairs, kPairStride, d_conv, 2, conversion, 0, n, d_dup, reinterpret_cast<hipStream_t>(stream));
+  return dd_launch(dd, who, {true, d_pairs, kPairStride, d_conv, 2, conversion, 0, n, d_dup}, reinterpret_cast<hipStream_t>(stream));
 }
 
 int walt_dedup_batch(walt_dedup* dd, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
@@ -365,18 +367,12 @@ int walt_dedup_batch(walt_dedup* dd, const void* records, size_t record_stride, 
   if (!records || !dup) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if ((rc = dd_reserve(dd, who, n))) return rc;
   // the records and conversions as the kernel reads them: packed (the caller's strides stay on the host)
-  std::vector<walt_best_match> rec((size_t)n);
-  std::vector<uint8_t> cv;
-  for (uint32_t i = 0; i < n; ++i) memcpy(&rec[i], static_cast<const char*>(records) + (size_t)i * record_stride, sizeof(walt_best_match));
-  if (conv) {
-    cv.resize(n);
-    for (uint32_t i = 0; i < n; ++i) cv[i] = conv[(size_t)i * conv_stride];
-  }
-  Scoped d_rec, d_conv, d_dup;
-  if ((rc = d_rec.get((size_t)n * 16)) || (rc = d_dup.get(n)) || (conv && (rc = d_conv.get(n)))) return rc;
-  WALT_HIP(hipMemcpy(d_rec.p, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-  if (conv) WALT_HIP(hipMemcpy(d_conv.p, cv.data(), n, hipMemcpyHostToDevice));
-  if ((rc = dd_launch(dd, who, false, d_rec.p, 16, d_conv.p, 1, conversion, kind, n, d_dup.p, nullptr))) return rc;
+  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(records, record_stride, n);
+  const std::vector<uint8_t> cv = pack_strided<uint8_t>(conv, conv_stride, conv ? n : 0);
+  DeviceTemp d_rec, d_conv, d_dup;
+  if ((rc = d_rec.put(rec.data(), (size_t)n * 16, kWhat)) || (rc = d_dup.get(n, kWhat)) || (conv && (rc = d_conv.put(cv.data(), n, kWhat))))
+    return rc;
+  if ((rc = dd_launch(dd, who, {false, d_rec.p, 16, d_conv.p, 1, conversion, kind, n, d_dup.p}, nullptr))) return rc;
   return dd_finish(dd, who, dup, d_dup.p, n);
 }
 
@@ -388,11 +384,11 @@ int walt_dedup_pairs_batch(walt_dedup* dd, const walt_pair_result* pairs, const 
   if (n == 0) return WALT_OK;
   if (!pairs || !dup) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
   if ((rc = dd_reserve(dd, who, 2ull * n))) return rc;
-  Scoped d_rec, d_conv, d_dup;
-  if ((rc = d_rec.get((size_t)n * kPairStride)) || (rc = d_dup.get(2 * (size_t)n)) || (conv && (rc = d_conv.get(2 * (size_t)n)))) return rc;
-  WALT_HIP(hipMemcpy(d_rec.p, pairs, (size_t)n * kPairStride, hipMemcpyHostToDevice));
-  if (conv) WALT_HIP(hipMemcpy(d_conv.p, conv, 2 * (size_t)n, hipMemcpyHostToDevice));
-  if ((rc = dd_launch(dd, who, true, d_rec.p, kPairStride, d_conv.p, 2, conversion, 0, n, d_dup.p, nullptr))) return rc;
+  DeviceTemp d_rec, d_conv, d_dup;
+  if ((rc = d_rec.put(pairs, (size_t)n * kPairStride, kWhat)) || (rc = d_dup.get(2 * (size_t)n, kWhat)) ||
+      (conv && (rc = d_conv.put(conv, 2 * (size_t)n, kWhat))))
+    return rc;
+  if ((rc = dd_launch(dd, who, {true, d_rec.p, kPairStride, d_conv.p, 2, conversion, 0, n, d_dup.p}, nullptr))) return rc;
   return dd_finish(dd, who, dup, d_dup.p, 2 * (size_t)n);
 }
 

@@ -139,11 +139,35 @@ struct walt_mbias {
 };
 
 namespace walt {
-// mbias.hip: the argument checks of walt_mbias_batch_device (who: the entry point the message names), and the kernel on `stream`
-int mbias_check(const walt_mbias* mb, const char* who, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
-                const void* d_records, size_t rec_stride, const void* d_skip, size_t skip_stride);
-int mbias_launch(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
-                 size_t rec_stride, const void* d_skip, size_t skip_stride, hipStream_t stream);
+// mbias.hip: one batch of calls as the bias kernel reads it (device arrays), and the kernel on `stream`
+struct MbiasBatch {
+  const void *calls, *offsets;
+  uint32_t n;
+  const void* records;
+  size_t rec_stride;
+  const void* skip;  // null: none
+  size_t skip_stride;
+};
+int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream);
+
+// A device temporary of one call, freed on every return path.  `what` names the call in the out-of-memory message
+// ("methylation calls", "duplicates", ...).  The host forms of the methylation-side calls allocate theirs per call.
+struct DeviceTemp {
+  void* p = nullptr;
+  DeviceTemp() = default;
+  DeviceTemp(const DeviceTemp&) = delete;
+  DeviceTemp& operator=(const DeviceTemp&) = delete;
+  ~DeviceTemp() { if (p) (void)hipFree(p); }
+  int get(size_t bytes, const char* what) {  // (a zero-byte request still allocates a byte: p is a device address afterwards)
+    return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, std::string("hipMalloc failed (") + what + ")");
+  }
+  // get(bytes + room) and the host array's `bytes` copied in (pageable host memory: done when it returns)
+  int put(const void* host, size_t bytes, const char* what, size_t room = 0) {
+    if (const int rc = get(bytes + room, what)) return rc;
+    if (bytes) WALT_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return WALT_OK;
+  }
+};
 
 // grow-only device buffer `slot` of idx (freed by walt_index_close)
 inline hipError_t host_api_buffer(walt_index* idx, int slot, size_t bytes, void** out) {

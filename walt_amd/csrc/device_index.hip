@@ -354,10 +354,7 @@ int finish_strand_device(walt_index* idx, int strand, uint32_t* g2, const uint32
   if ((rc = dev_alloc(idx, &bad, kNumBuckets / 32))) return rc;
   if ((rc = dev_alloc(idx, &dir, (uint64_t)slots + 1))) return rc;
   if ((rc = dev_alloc(idx, &ent, (uint64_t)index_size + 1))) return rc;
-  struct Scoped {  // temporaries of this function: freed on every return path
-    void* p = nullptr;
-    ~Scoped() { if (p) hipFree(p); }
-  } err_buf, tmp_buf, cnt_buf;
+  DeviceTemp err_buf, tmp_buf, cnt_buf;  // temporaries of this function: freed on every return path
   WALT_HIP(hipMalloc(&err_buf.p, 8 * sizeof(uint32_t)));
   err = reinterpret_cast<uint32_t*>(err_buf.p);
   WALT_HIP(hipMemsetAsync(err, 0, 8 * sizeof(uint32_t), stream));
@@ -709,10 +706,7 @@ static int build_windows(walt_index* idx) {
     // The windows are an optional accelerator: when memory for them cannot be had after all (the budget came from
     // hipMemGetInfo a moment ago; another process or a caching allocator may have taken it since) the strand simply
     // has none and its large regions are verified from ent[] + g2[] -- same results, slower.
-    struct Scoped {  // temporaries: freed on every path
-      void* p = nullptr;
-      ~Scoped() { if (p) (void)hipFree(p); }
-    } flag_buf, cnt_buf, tmp_buf, bits_buf, rank_buf, win_buf, win2_buf;
+    DeviceTemp flag_buf, cnt_buf, tmp_buf, bits_buf, rank_buf, win_buf, win2_buf;  // temporaries: freed on every path
     auto give_up = [&](const char* what) {
       if (getenv("WALT_AMD_VERBOSE")) fprintf(stderr, "[walt_amd index: strand %d: no dense candidate windows (%s)]\n", s, what);
       (void)hipGetLastError();
@@ -758,7 +752,7 @@ static int build_windows(walt_index* idx) {
     WALT_HIP(hipStreamSynchronize(stream));
     WALT_HIP(hipGetLastError());
     // the strand keeps them: hand the four arrays over to the index
-    for (Scoped* b : {&bits_buf, &rank_buf, &win_buf, &win2_buf}) { idx->allocs.push_back(b->p); b->p = nullptr; }
+    for (DeviceTemp* b : {&bits_buf, &rank_buf, &win_buf, &win2_buf}) { idx->allocs.push_back(b->p); b->p = nullptr; }
     idx->device_bytes += ((uint64_t)nw + 1) * 12 + ((uint64_t)n_recs * (kWinWords + 1 + kWinWords2) + 32) * 4;
     idx->window_records[s] = n_recs;
     sv.wbits = bits; sv.wrank = rank; sv.win = win; sv.win2 = win2; sv.wcap = n_recs;

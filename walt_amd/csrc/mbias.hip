@@ -76,36 +76,29 @@ __global__ __launch_bounds__(kBlock) void k_mbias(const MbiasArgs a) {
 
 static uint64_t mbias_bytes(uint32_t n_tables) { return (uint64_t)n_tables * kMbiasReplicas * kMbiasWords * 8; }
 
-int mbias_check(const walt_mbias* mb, const char* who_c, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
-                const void* d_records, size_t rec_stride, const void* d_skip, size_t skip_stride) {
-  const std::string who(who_c);
+// what both forms refuse before they look at the batch
+static int mbias_set_check(const walt_mbias* mb, const std::string& who, uint32_t table, const MbiasBatch& b) {
   if (!mb) return fail(WALT_EINVAL, who + ": bad argument (null bias set)");
   if (table >= mb->n_tables)
     return fail(WALT_EINVAL, who + ": table " + std::to_string(table) + " of a bias set with " + std::to_string(mb->n_tables));
-  if (rec_stride < sizeof(walt_best_match) || rec_stride % 4)
-    return fail(WALT_EINVAL, who + ": record stride " + std::to_string(rec_stride) +
-                                 " is smaller than a walt_best_match (16) or not a multiple of 4");
-  if (d_skip && skip_stride < 1) return fail(WALT_EINVAL, who + ": skip stride 0 is smaller than its element (1)");
-  if (n && (!d_calls || !d_offsets || !d_records)) return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets or records)");
-  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_offsets & 7u))
-    return fail(WALT_EINVAL, who + ": records must be 4-byte aligned, offsets 8-byte aligned");
-  return WALT_OK;
+  std::string bad = record_stride_refusal(b.rec_stride);
+  if (bad.empty()) bad = skip_stride_refusal(b.skip, b.skip_stride);
+  return bad.empty() ? WALT_OK : fail(WALT_EINVAL, who + ": " + bad);
 }
 
-int mbias_launch(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
-                 size_t rec_stride, const void* d_skip, size_t skip_stride, hipStream_t stream) {
-  if (n == 0) return WALT_OK;
+int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream) {
+  if (b.n == 0) return WALT_OK;
   WALT_HIP(hipSetDevice(mb->device));
   MbiasArgs a;
-  a.calls = static_cast<const uint8_t*>(d_calls);
-  a.offsets = static_cast<const uint64_t*>(d_offsets);
-  a.n = n;
-  a.records = static_cast<const uint8_t*>(d_records);
-  a.rec_stride = rec_stride;
-  a.skip = static_cast<const uint8_t*>(d_skip);
-  a.skip_stride = skip_stride;
+  a.calls = static_cast<const uint8_t*>(b.calls);
+  a.offsets = static_cast<const uint64_t*>(b.offsets);
+  a.n = b.n;
+  a.records = static_cast<const uint8_t*>(b.records);
+  a.rec_stride = b.rec_stride;
+  a.skip = static_cast<const uint8_t*>(b.skip);
+  a.skip_stride = b.skip_stride;
   a.tabs = mb->tabs + (uint64_t)table * kMbiasReplicas * kMbiasWords;
-  const uint64_t want = ((uint64_t)n + kBlock / kMbiasGroup - 1) / (kBlock / kMbiasGroup);
+  const uint64_t want = ((uint64_t)b.n + kBlock / kMbiasGroup - 1) / (kBlock / kMbiasGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)mb->n_cu * kMbiasBlocksPerCu);
   hipLaunchKernelGGL(k_mbias, dim3(grid), dim3(kBlock), 0, stream, a);
   WALT_HIP(hipGetLastError());
@@ -190,50 +183,39 @@ int walt_mbias_read(walt_mbias* mb, uint32_t table, uint64_t* out) {
 
 int walt_mbias_batch_device(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
                             const void* d_records, size_t record_stride, const void* d_skip, size_t skip_stride, void* stream) {
-  const int rc = mbias_check(mb, "walt_mbias_batch_device", table, d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride);
-  if (rc) return rc;
-  return mbias_launch(mb, table, d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride,
-                      reinterpret_cast<hipStream_t>(stream));
+  const std::string who = "walt_mbias_batch_device";
+  const MbiasBatch b = {d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride};
+  if (const int rc = mbias_set_check(mb, who, table, b)) return rc;
+  if (n && (!d_calls || !d_offsets || !d_records)) return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets or records)");
+  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_offsets & 7u))
+    return fail(WALT_EINVAL, who + ": records must be 4-byte aligned, offsets 8-byte aligned");
+  return mbias_launch(mb, table, b, reinterpret_cast<hipStream_t>(stream));
 }
 
 int walt_mbias_batch(walt_mbias* mb, uint32_t table, const char* calls, const uint64_t* offsets, uint32_t n, const void* records,
                      size_t record_stride, const uint8_t* skip, size_t skip_stride) {
   const std::string who = "walt_mbias_batch";
   // (host arrays: no alignment is asked of them; the device copies below are aligned)
-  int rc = mbias_check(mb, "walt_mbias_batch", table, n ? calls : nullptr, nullptr, 0, nullptr, record_stride, skip, skip_stride);
+  int rc = mbias_set_check(mb, who, table, {calls, offsets, n, records, record_stride, skip, skip_stride});
   if (rc) return rc;
   if (n == 0) return WALT_OK;
   if (!offsets || !records || (!calls && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets or records)");
-  for (uint32_t i = 0; i < n; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, who + ": offsets not non-decreasing");
-    if (offsets[i + 1] - offsets[i] > kMbiasPositions) return fail(WALT_EINVAL, who + ": read length above 1024 is not supported");
-  }
+  uint32_t max_len = 0;
+  static_assert(kMbiasPositions == 1024, "scan_offsets refuses what the table has no position for");
+  if (const char* bad = scan_offsets(offsets, n, &max_len)) return fail(WALT_EINVAL, who + ": " + bad);
   WALT_HIP(hipSetDevice(mb->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   // records and skip bytes as the kernel reads them: packed (the caller's strides stay on the host)
-  std::vector<walt_best_match> rec((size_t)n);
-  for (uint32_t i = 0; i < n; ++i) memcpy(&rec[i], static_cast<const char*>(records) + (size_t)i * record_stride, sizeof(walt_best_match));
-  std::vector<uint8_t> sk;
-  if (skip) {
-    sk.resize(n);
-    for (uint32_t i = 0; i < n; ++i) sk[i] = skip[(size_t)i * skip_stride];
-  }
-  std::vector<uint64_t> rel((size_t)n + 1);
-  for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
-  struct Scoped {
-    void* p = nullptr;
-    ~Scoped() { if (p) (void)hipFree(p); }
-    int get(size_t bytes) {
-      return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (methylation bias)");
-    }
-  } d_calls, d_off, d_rec, d_skip;
-  if ((rc = d_calls.get(nbytes)) || (rc = d_off.get(((size_t)n + 1) * 8)) || (rc = d_rec.get((size_t)n * 16))) return rc;
-  if (skip && (rc = d_skip.get(n))) return rc;
-  if (nbytes) WALT_HIP(hipMemcpy(d_calls.p, calls + offsets[0], nbytes, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_off.p, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_rec.p, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-  if (skip) WALT_HIP(hipMemcpy(d_skip.p, sk.data(), n, hipMemcpyHostToDevice));
-  if ((rc = mbias_launch(mb, table, d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1, nullptr))) return rc;
+  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(records, record_stride, n);
+  const std::vector<uint8_t> sk = pack_strided<uint8_t>(skip, skip_stride, skip ? n : 0);
+  std::vector<uint64_t> rel;
+  const uint64_t* off = rebase_offsets(offsets, n, rel);
+  const char* what = "methylation bias";
+  DeviceTemp d_calls, d_off, d_rec, d_skip;
+  if ((rc = d_calls.put(nbytes ? calls + offsets[0] : nullptr, nbytes, what)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
+      (rc = d_rec.put(rec.data(), (size_t)n * 16, what)) || (skip && (rc = d_skip.put(sk.data(), n, what))))
+    return rc;
+  if ((rc = mbias_launch(mb, table, {d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1}, nullptr))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   return WALT_OK;
 }

@@ -102,17 +102,13 @@ int build_reference(walt_index* idx, const char* dbindex_path) {
                                  missing + " (open the index with WALT_WITH_REFERENCE instead)");
   }
   WALT_HIP(hipSetDevice(idx->device));
-  struct Scoped {
-    void* p = nullptr;
-    ~Scoped() { if (p) (void)hipFree(p); }
-  };
   const size_t allocs_before = idx->allocs.size();
   const uint64_t bytes_before = idx->device_bytes;
   uint32_t* ref[2] = {nullptr, nullptr};
   unsigned long long* shards = nullptr;
   int rc = WALT_OK;
   for (int o = 0; o < 2 && !rc; ++o) {
-    Scoped tmp[2];
+    DeviceTemp tmp[2];
     const uint32_t* g2[2] = {nullptr, nullptr};
     const uint8_t* bytes[2] = {nullptr, nullptr};
     for (int c = 0; c < 2 && !rc; ++c) {  // c = 0: the C->T strand of this orientation, 1: the G->A strand
@@ -329,65 +325,162 @@ __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned 
   if (sum) atomicAdd(&stats[t], sum);
 }
 
-static int meth_args_check(const walt_index* idx, const char* who, size_t rec_stride, const void* conv, size_t conv_stride,
-                           int conversion) {
-  if (!idx) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
-  if (!idx->ref[0])
-    return fail(WALT_EINVAL, std::string(who) + ": the index holds no reference (open it with WALT_WITH_REFERENCE or "
-                                                "call walt_index_enable_reference)");
-  if (rec_stride < sizeof(walt_best_match) || rec_stride % 4)
-    return fail(WALT_EINVAL, std::string(who) + ": record stride " + std::to_string(rec_stride) +
-                                 " is smaller than a walt_best_match (16) or not a multiple of 4");
-  if (conv && conv_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": conv stride 0 is smaller than its element (1)");
-  if (!conv && conversion != 'T' && conversion != 'A')
-    return fail(WALT_EINVAL, std::string(who) + ": conversion " + std::to_string(conversion) + " is neither 'T' nor 'A'");
+// One call of the calling kernel, through whichever of the ten entry points it came: the index, the destinations and
+// filters it may have, and the batch -- host arrays in a host form, device arrays in a device form and in meth_launch.
+// What an entry point does not have stays null.  (Initialised by name: hipcc takes designated initialisers in C++17.)
+struct MethCall {
+  const char* who = nullptr;       // the entry point, as the refusals name it
+  bool pile_required = false;      // the two oldest pile-up forms: a pile-up must be given (the newer ones: null is calls only)
+  walt_index* idx = nullptr;
+  walt_pileup* pile = nullptr;
+  const void *bases = nullptr, *offsets = nullptr;
+  uint32_t n = 0;
+  const void* records = nullptr;
+  size_t record_stride = 0;
+  const void* conv = nullptr;      // null: `conversion` for every read
+  size_t conv_stride = 0;
+  int conversion = 0;
+  const void* call_len = nullptr;
+  void *calls = nullptr, *counts = nullptr, *stats = nullptr;
+  const void* skip = nullptr;
+  size_t skip_stride = 0;
+  const void* excl = nullptr;
+  walt_mbias* mb = nullptr;        // the bias set whose `table` takes the calls too
+  uint32_t table = 0;
+  void* stream = nullptr;          // device forms
+};
+
+// What a host form and a device form refuse alike, before they look at the batch.  has_calls: the bias table is counted
+// from the calls on the device (a host form always has them there).
+static int meth_call_check(const MethCall& c, bool has_calls) {
+  const std::string who(c.who);
+  if (!c.idx) return fail(WALT_EINVAL, who + ": bad argument");
+  if (!c.pile && c.pile_required) return fail(WALT_EINVAL, who + ": bad argument (null pile-up)");
+  if (c.pile && c.pile->idx != c.idx) return fail(WALT_EINVAL, who + ": the pile-up belongs to another index");
+  if (!c.idx->ref[0])
+    return fail(WALT_EINVAL, who + ": the index holds no reference (open it with WALT_WITH_REFERENCE or "
+                                   "call walt_index_enable_reference)");
+  std::string bad = record_stride_refusal(c.record_stride);
+  if (bad.empty()) bad = conv_refusal(c.conv, c.conv_stride, c.conversion);
+  if (!bad.empty()) return fail(WALT_EINVAL, who + ": " + bad);
+  if (c.mb) {  // (include/walt_amd.h, "methylation bias by read position"): same device, a table it has, calls to count
+    if (c.mb->device != c.idx->device)
+      return fail(WALT_EINVAL, who + ": the bias set lives on device " + std::to_string(c.mb->device) +
+                                   ", the index on device " + std::to_string(c.idx->device));
+    if (c.table >= c.mb->n_tables)
+      return fail(WALT_EINVAL, who + ": table " + std::to_string(c.table) + " of a bias set with " + std::to_string(c.mb->n_tables));
+    if (!has_calls)
+      return fail(WALT_EINVAL, who + ": the bias table is counted from the calls: d_calls must not be NULL when a bias set is given");
+  }
+  if (!(bad = skip_stride_refusal(c.skip, c.skip_stride)).empty()) return fail(WALT_EINVAL, who + ": " + bad);
   return WALT_OK;
 }
 
-static int pile_check(const walt_index* idx, const walt_pileup* p, const char* who) {
-  if (!p) return fail(WALT_EINVAL, std::string(who) + ": bad argument (null pile-up)");
-  if (p->idx != idx) return fail(WALT_EINVAL, std::string(who) + ": the pile-up belongs to another index");
-  return WALT_OK;
-}
-
-static int meth_launch(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n, const void* d_records,
-                       size_t rec_stride, const void* d_conv, size_t conv_stride, int conversion, const void* d_call_len,
-                       void* d_calls, void* d_counts, void* d_stats, hipStream_t stream, walt_pileup* pile = nullptr,
-                       const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr) {
-  if (n == 0 || (!d_calls && !d_counts && !d_stats && !pile)) return WALT_OK;
+// c: a checked call whose arrays are on the device.  The calling kernel and, with a bias set (which comes with calls),
+// the bias kernel from the calls just written: behind it on the same stream.
+static int meth_launch(const MethCall& c) {
+  walt_index* const idx = c.idx;
+  if (c.n == 0 || (!c.calls && !c.counts && !c.stats && !c.pile)) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
+  const hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
   MethArgs a;
   a.ref[0] = idx->ref[0]; a.ref[1] = idx->ref[1];
   a.ref_last = ref_words(idx) - 1;
   a.genome_len = idx->head.genome_len;
   a.start_index = idx->view.start_index;
   a.n_chrom = idx->view.n_chrom;
-  a.bases = static_cast<const uint8_t*>(d_bases);
-  a.offsets = static_cast<const uint64_t*>(d_offsets);
-  a.n = n;
-  a.records = static_cast<const uint8_t*>(d_records);
-  a.rec_stride = rec_stride;
-  a.conv = static_cast<const uint8_t*>(d_conv);
-  a.conv_stride = conv_stride;
-  a.conversion = (uint32_t)conversion;
-  a.call_len = static_cast<const uint32_t*>(d_call_len);
-  a.calls = static_cast<uint8_t*>(d_calls);
-  a.counts = static_cast<unsigned long long*>(d_counts);
-  a.shards = d_stats ? idx->meth_shards : nullptr;
-  a.pile[0] = pile ? pile->plane[0] : nullptr;
-  a.pile[1] = pile ? pile->plane[1] : nullptr;
-  a.skip = static_cast<const uint8_t*>(d_skip);
-  a.skip_stride = skip_stride;
-  a.excl = static_cast<const uint32_t*>(d_excl);
-  const uint64_t want = ((uint64_t)n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
+  a.bases = static_cast<const uint8_t*>(c.bases);
+  a.offsets = static_cast<const uint64_t*>(c.offsets);
+  a.n = c.n;
+  a.records = static_cast<const uint8_t*>(c.records);
+  a.rec_stride = c.record_stride;
+  a.conv = static_cast<const uint8_t*>(c.conv);
+  a.conv_stride = c.conv_stride;
+  a.conversion = (uint32_t)c.conversion;
+  a.call_len = static_cast<const uint32_t*>(c.call_len);
+  a.calls = static_cast<uint8_t*>(c.calls);
+  a.counts = static_cast<unsigned long long*>(c.counts);
+  a.shards = c.stats ? idx->meth_shards : nullptr;
+  a.pile[0] = c.pile ? c.pile->plane[0] : nullptr;
+  a.pile[1] = c.pile ? c.pile->plane[1] : nullptr;
+  a.skip = static_cast<const uint8_t*>(c.skip);
+  a.skip_stride = c.skip_stride;
+  a.excl = static_cast<const uint32_t*>(c.excl);
+  const uint64_t want = ((uint64_t)c.n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
-  const auto kernel = a.excl ? (!pile ? k_meth_call_excl : idx->opt.pile_rows ? k_meth_pile_rows_excl : k_meth_pile_excl)
-                             : (!pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile);
+  const auto kernel = a.excl ? (!c.pile ? k_meth_call_excl : idx->opt.pile_rows ? k_meth_pile_rows_excl : k_meth_pile_excl)
+                             : (!c.pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
-  if (d_stats)
+  if (c.stats)
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
-                       static_cast<unsigned long long*>(d_stats));
+                       static_cast<unsigned long long*>(c.stats));
   WALT_HIP(hipGetLastError());
+  if (!c.mb) return WALT_OK;
+  return mbias_launch(c.mb, c.table, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream);
+}
+
+// the five device forms: asynchronous on the caller's stream
+static int meth_batch_device(const MethCall& c) {
+  const std::string who(c.who);
+  if (const int rc = meth_call_check(c, c.calls != nullptr)) return rc;
+  if (c.n && (!c.offsets || !c.records)) return fail(WALT_EINVAL, who + ": bad argument");
+  if (((uintptr_t)c.records & 3u) || ((uintptr_t)c.counts & 7u) || ((uintptr_t)c.call_len & 3u) || ((uintptr_t)c.stats & 7u))
+    return fail(WALT_EINVAL, who + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
+  if ((uintptr_t)c.excl & 3u) return fail(WALT_EINVAL, who + ": excl must be 4-byte aligned");
+  return meth_launch(c);
+}
+
+// The five host forms: the batch into device temporaries of this call (offsets relative to the first read, the
+// caller's strided arrays packed: its strides stay on the host), the kernels on the null stream, the results back --
+// calls at calls + offsets[0], stats accumulated into.
+static int meth_batch_host(const MethCall& c) {
+  const std::string who(c.who);
+  int rc = meth_call_check(c, true);
+  if (rc) return rc;
+  const uint32_t n = c.n;
+  if (n == 0) return WALT_OK;
+  const uint64_t* offsets = static_cast<const uint64_t*>(c.offsets);
+  const char* bases = static_cast<const char*>(c.bases);
+  if (!offsets || !c.records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument");
+  const std::string bad = call_reads_refusal(c.who, offsets, n, static_cast<const uint8_t*>(c.conv), c.conv_stride);
+  if (!bad.empty()) return fail(WALT_EINVAL, bad);
+  walt_meth_stats* stats = static_cast<walt_meth_stats*>(c.stats);
+  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb) return WALT_OK;
+  WALT_HIP(hipSetDevice(c.idx->device));
+  const uint64_t nbytes = offsets[n] - offsets[0];
+  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(c.records, c.record_stride, n);
+  const std::vector<uint8_t> cv = pack_strided<uint8_t>(c.conv, c.conv_stride, c.conv ? n : 0);
+  const std::vector<uint8_t> sk = pack_strided<uint8_t>(c.skip, c.skip_stride, c.skip ? n : 0);
+  std::vector<uint64_t> rel;
+  const uint64_t* off = rebase_offsets(offsets, n, rel);
+  const char* const what = "methylation calls";
+  DeviceTemp d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl;
+  if ((rc = d_bases.put(bases + offsets[0], nbytes, what, 16)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
+      (rc = d_rec.put(rec.data(), (size_t)n * 16, what)))
+    return rc;
+  if (c.conv && (rc = d_conv.put(cv.data(), n, what))) return rc;
+  if (c.call_len && (rc = d_len.put(c.call_len, (size_t)n * 4, what))) return rc;
+  if (c.skip && (rc = d_skip.put(sk.data(), n, what))) return rc;
+  if (c.excl && (rc = d_excl.put(c.excl, (size_t)n * 4, what))) return rc;
+  if ((c.calls || c.mb) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias table is counted from the device copy)
+  if (c.counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts), what))) return rc;
+  if (stats && (rc = d_stats.get(sizeof(walt_meth_stats), what))) return rc;
+  if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
+  MethCall d = c;  // the same call on the device copies
+  d.bases = d_bases.p; d.offsets = d_off.p; d.records = d_rec.p; d.record_stride = 16;
+  d.conv = d_conv.p; d.conv_stride = 1; d.call_len = d_len.p;
+  d.calls = d_calls.p; d.counts = d_counts.p; d.stats = d_stats.p;
+  d.skip = d_skip.p; d.skip_stride = 1; d.excl = d_excl.p; d.stream = nullptr;
+  if ((rc = meth_launch(d))) return rc;
+  WALT_HIP(hipStreamSynchronize(nullptr));
+  if (c.calls && nbytes) WALT_HIP(hipMemcpy(static_cast<char*>(c.calls) + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
+  if (c.counts) WALT_HIP(hipMemcpy(c.counts, d_counts.p, (size_t)n * sizeof(walt_meth_counts), hipMemcpyDeviceToHost));
+  if (stats) {
+    walt_meth_stats st;
+    WALT_HIP(hipMemcpy(&st, d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+    stats->reads += st.reads;
+    for (int i = 0; i < 4; ++i) { stats->meth[i] += st.meth[i]; stats->unmeth[i] += st.unmeth[i]; }
+  }
   return WALT_OK;
 }
 
@@ -404,158 +497,42 @@ int walt_index_enable_reference(walt_index* idx) {
 
 int walt_index_has_reference(const walt_index* idx) { return idx && idx->ref[0] ? 1 : 0; }
 
-}  // extern "C"
-
-namespace walt {
-// a bias set beside the calling (include/walt_amd.h, "methylation bias by read position"): same device, a table it has,
-// and calls to count
-static int mbias_with_calls_check(const walt_index* idx, const char* who, const walt_mbias* mb, uint32_t table, bool has_calls) {
-  if (mb->device != idx->device)
-    return fail(WALT_EINVAL, std::string(who) + ": the bias set lives on device " + std::to_string(mb->device) +
-                                 ", the index on device " + std::to_string(idx->device));
-  if (table >= mb->n_tables)
-    return fail(WALT_EINVAL, std::string(who) + ": table " + std::to_string(table) + " of a bias set with " + std::to_string(mb->n_tables));
-  if (!has_calls)
-    return fail(WALT_EINVAL, std::string(who) + ": the bias table is counted from the calls: d_calls must not be NULL when a bias set is given");
-  return WALT_OK;
-}
-
-// the two device forms (pile null: walt_meth_call_batch_device)
-static int meth_batch_device(const char* who, walt_index* idx, walt_pileup* pile, const void* d_bases, const void* d_offsets,
-                             uint32_t n, const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
-                             int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
-                             void* stream, const void* d_skip = nullptr, size_t skip_stride = 0, const void* d_excl = nullptr,
-                             walt_mbias* mb = nullptr, uint32_t table = 0) {
-  int rc = meth_args_check(idx, who, record_stride, d_conv, conv_stride, conversion);
-  if (rc) return rc;
-  if (mb && (rc = mbias_with_calls_check(idx, who, mb, table, d_calls != nullptr))) return rc;
-  if (d_skip && skip_stride < 1) return fail(WALT_EINVAL, std::string(who) + ": skip stride 0 is smaller than its element (1)");
-  if (n && (!d_offsets || !d_records)) return fail(WALT_EINVAL, std::string(who) + ": bad argument");
-  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || ((uintptr_t)d_call_len & 3u) || ((uintptr_t)d_stats & 7u))
-    return fail(WALT_EINVAL, std::string(who) + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
-  if ((uintptr_t)d_excl & 3u) return fail(WALT_EINVAL, std::string(who) + ": excl must be 4-byte aligned");
-  rc = meth_launch(idx, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
-                   d_calls, d_counts, d_stats, reinterpret_cast<hipStream_t>(stream), pile, d_skip, skip_stride, d_excl);
-  if (rc || !mb) return rc;
-  // the bias table, from the calls just written: behind the calling kernel on the same stream
-  return mbias_launch(mb, table, d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride,
-                      reinterpret_cast<hipStream_t>(stream));
-}
-
-// the two host forms (pile null: walt_meth_call_batch)
-static int meth_batch_host(const char* who_c, walt_index* idx, walt_pileup* pile, const char* bases, const uint64_t* offsets,
-                           uint32_t n, const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
-                           int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
-                           walt_meth_stats* stats, const uint8_t* skip = nullptr, size_t skip_stride = 0,
-                           const uint32_t* excl = nullptr, walt_mbias* mb = nullptr, uint32_t table = 0) {
-  const std::string who(who_c);
-  int rc = meth_args_check(idx, who_c, record_stride, conv, conv_stride, conversion);
-  if (rc) return rc;
-  if (mb && (rc = mbias_with_calls_check(idx, who_c, mb, table, true))) return rc;
-  if (skip && skip_stride < 1) return fail(WALT_EINVAL, who + ": skip stride 0 is smaller than its element (1)");
-  if (n == 0) return WALT_OK;
-  if (!offsets || !records || (!bases && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument");
-  for (uint32_t i = 0; i < n; ++i) {
-    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, "offsets not non-decreasing");
-    if (offsets[i + 1] - offsets[i] > kMaxReadLenAny) return fail(WALT_EINVAL, "read length above 1024 is not supported");
-    if (conv && conv[(size_t)i * conv_stride] != 'T' && conv[(size_t)i * conv_stride] != 'A')
-      return fail(WALT_EINVAL, who + ": conversion " + std::to_string((int)conv[(size_t)i * conv_stride]) +
-                                   " of read " + std::to_string(i) + " is neither 'T' nor 'A'");
-  }
-  if (!calls && !counts && !stats && !pile && !mb) return WALT_OK;
-  WALT_HIP(hipSetDevice(idx->device));
-  const uint64_t nbytes = offsets[n] - offsets[0];
-  // the records and conversions as the kernel reads them: packed (the caller's strides stay on the host)
-  std::vector<walt_best_match> rec((size_t)n);
-  std::vector<uint8_t> cv;
-  for (uint32_t i = 0; i < n; ++i) memcpy(&rec[i], static_cast<const char*>(records) + (size_t)i * record_stride, sizeof(walt_best_match));
-  if (conv) {
-    cv.resize(n);
-    for (uint32_t i = 0; i < n; ++i) cv[i] = conv[(size_t)i * conv_stride];
-  }
-  std::vector<uint8_t> sk;
-  if (skip) {
-    sk.resize(n);
-    for (uint32_t i = 0; i < n; ++i) sk[i] = skip[(size_t)i * skip_stride];
-  }
-  std::vector<uint64_t> rel((size_t)n + 1);
-  for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - offsets[0];
-  struct Scoped {
-    void* p = nullptr;
-    ~Scoped() { if (p) (void)hipFree(p); }
-    int get(size_t bytes) {
-      return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (methylation calls)");
-    }
-  } d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl;
-  if ((rc = d_bases.get(nbytes + 16)) || (rc = d_off.get(((size_t)n + 1) * 8)) || (rc = d_rec.get((size_t)n * 16))) return rc;
-  if (conv && (rc = d_conv.get(n))) return rc;
-  if (call_len && (rc = d_len.get((size_t)n * 4))) return rc;
-  if (skip && (rc = d_skip.get(n))) return rc;
-  if (excl && (rc = d_excl.get((size_t)n * 4))) return rc;
-  if ((calls || mb) && (rc = d_calls.get(nbytes + 16))) return rc;  // (the bias table is counted from the device copy)
-  if (counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts)))) return rc;
-  if (stats && (rc = d_stats.get(sizeof(walt_meth_stats)))) return rc;
-  WALT_HIP(hipMemcpy(d_bases.p, bases + offsets[0], nbytes, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_off.p, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_rec.p, rec.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-  if (conv) WALT_HIP(hipMemcpy(d_conv.p, cv.data(), n, hipMemcpyHostToDevice));
-  if (call_len) WALT_HIP(hipMemcpy(d_len.p, call_len, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (skip) WALT_HIP(hipMemcpy(d_skip.p, sk.data(), n, hipMemcpyHostToDevice));
-  if (excl) WALT_HIP(hipMemcpy(d_excl.p, excl, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
-  rc = meth_launch(idx, d_bases.p, d_off.p, n, d_rec.p, 16, d_conv.p, 1, conversion, d_len.p, d_calls.p, d_counts.p,
-                   d_stats.p, nullptr, pile, d_skip.p, 1, d_excl.p);
-  if (rc) return rc;
-  if (mb && (rc = mbias_launch(mb, table, d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1, nullptr))) return rc;
-  WALT_HIP(hipStreamSynchronize(nullptr));
-  if (calls && nbytes) WALT_HIP(hipMemcpy(calls + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
-  if (counts) WALT_HIP(hipMemcpy(counts, d_counts.p, (size_t)n * sizeof(walt_meth_counts), hipMemcpyDeviceToHost));
-  if (stats) {
-    walt_meth_stats st;
-    WALT_HIP(hipMemcpy(&st, d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
-    stats->reads += st.reads;
-    for (int i = 0; i < 4; ++i) { stats->meth[i] += st.meth[i]; stats->unmeth[i] += st.unmeth[i]; }
-  }
-  return WALT_OK;
-}
-}  // namespace walt
-
-extern "C" {
-
 int walt_meth_call_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
                                 const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                                 int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                 void* stream) {
-  return meth_batch_device("walt_meth_call_batch_device", idx, nullptr, d_bases, d_offsets, n, d_records, record_stride, d_conv,
-                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream);
+  return meth_batch_device({.who = "walt_meth_call_batch_device", .idx = idx,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats, .stream = stream});
 }
 
 int walt_meth_call_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
                          size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
                          const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
-  return meth_batch_host("walt_meth_call_batch", idx, nullptr, bases, offsets, n, records, record_stride, conv, conv_stride,
-                         conversion, call_len, calls, counts, stats);
+  return meth_batch_host({.who = "walt_meth_call_batch", .idx = idx,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats});
 }
 
 int walt_meth_pileup_batch_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
                                   const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                                   int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                   void* stream) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_device: bad argument");
-  const int rc = pile_check(idx, p, "walt_meth_pileup_batch_device");
-  if (rc) return rc;
-  return meth_batch_device("walt_meth_pileup_batch_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
-                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream);
+  return meth_batch_device({.who = "walt_meth_pileup_batch_device", .pile_required = true, .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats, .stream = stream});
 }
 
 int walt_meth_pileup_batch(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
                            const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
                            const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch: bad argument");
-  const int rc = pile_check(idx, p, "walt_meth_pileup_batch");
-  if (rc) return rc;
-  return meth_batch_host("walt_meth_pileup_batch", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
-                         conversion, call_len, calls, counts, stats);
+  return meth_batch_host({.who = "walt_meth_pileup_batch", .pile_required = true, .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats});
 }
 
 // the pile-up forms plus skip (include/walt_amd.h, "duplicates"); here the pile-up may be null: calls only
@@ -563,20 +540,22 @@ int walt_meth_pileup_batch_skip_device(walt_index* idx, walt_pileup* p, const vo
                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                        const void* d_skip, size_t skip_stride, void* stream) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_skip_device: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_skip_device");
-  return meth_batch_device("walt_meth_pileup_batch_skip_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
-                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride);
+  return meth_batch_device({.who = "walt_meth_pileup_batch_skip_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .stream = stream});
 }
 
 int walt_meth_pileup_batch_skip(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
                                 const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
                                 int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
                                 walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_skip: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_skip");
-  return meth_batch_host("walt_meth_pileup_batch_skip", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
-                         conversion, call_len, calls, counts, stats, skip, skip_stride);
+  return meth_batch_host({.who = "walt_meth_pileup_batch_skip", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride});
 }
 
 // the skip forms plus excl (include/walt_amd.h, "overlap of a pair"); the pile-up and skip may be null
@@ -584,20 +563,22 @@ int walt_meth_pileup_batch_excl_device(walt_index* idx, walt_pileup* p, const vo
                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                        const void* d_skip, size_t skip_stride, const void* d_excl, void* stream) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_excl_device: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_excl_device");
-  return meth_batch_device("walt_meth_pileup_batch_excl_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
-                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl);
+  return meth_batch_device({.who = "walt_meth_pileup_batch_excl_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .stream = stream});
 }
 
 int walt_meth_pileup_batch_excl(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
                                 const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
                                 int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
                                 walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_excl: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_excl");
-  return meth_batch_host("walt_meth_pileup_batch_excl", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
-                         conversion, call_len, calls, counts, stats, skip, skip_stride, excl);
+  return meth_batch_host({.who = "walt_meth_pileup_batch_excl", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl});
 }
 
 // the excl forms plus a bias set (include/walt_amd.h, "methylation bias by read position"); mb null: the excl form
@@ -606,11 +587,11 @@ int walt_meth_pileup_batch_mbias_device(walt_index* idx, walt_pileup* p, const v
                                         int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
                                         const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
                                         uint32_t table, void* stream) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_mbias_device: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_mbias_device");
-  return meth_batch_device("walt_meth_pileup_batch_mbias_device", idx, p, d_bases, d_offsets, n, d_records, record_stride, d_conv,
-                           conv_stride, conversion, d_call_len, d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl,
-                           mb, table);
+  return meth_batch_device({.who = "walt_meth_pileup_batch_mbias_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .mb = mb, .table = table, .stream = stream});
 }
 
 int walt_meth_pileup_batch_mbias(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
@@ -618,10 +599,11 @@ int walt_meth_pileup_batch_mbias(walt_index* idx, walt_pileup* p, const char* ba
                                  int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
                                  walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
                                  walt_mbias* mb, uint32_t table) {
-  if (!idx) return fail(WALT_EINVAL, "walt_meth_pileup_batch_mbias: bad argument");
-  if (p && p->idx != idx) return pile_check(idx, p, "walt_meth_pileup_batch_mbias");
-  return meth_batch_host("walt_meth_pileup_batch_mbias", idx, p, bases, offsets, n, records, record_stride, conv, conv_stride,
-                         conversion, call_len, calls, counts, stats, skip, skip_stride, excl, mb, table);
+  return meth_batch_host({.who = "walt_meth_pileup_batch_mbias", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table});
 }
 
 }  // extern "C"

@@ -66,23 +66,30 @@ __global__ __launch_bounds__(kBlock) void k_pair_overlap(const OverlapArgs a) {
   }
 }
 
-static int overlap_launch(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2, uint32_t n,
-                          const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals, hipStream_t stream) {
-  if (n == 0) return WALT_OK;
+// one batch as the kernel reads it (device arrays)
+struct OverlapBatch {
+  const void *pairs, *offsets1, *offsets2;
+  uint32_t n;
+  const void *call_len1, *call_len2;
+  void *excl, *totals;
+};
+
+static int overlap_launch(walt_index* idx, const OverlapBatch& b, hipStream_t stream) {
+  if (b.n == 0) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   OverlapArgs a;
   a.start_index = idx->view.start_index;
   a.n_chrom = idx->view.n_chrom;
   a.genome_len = idx->head.genome_len;
-  a.pairs = static_cast<const uint32_t*>(d_pairs);
-  a.offsets1 = static_cast<const uint64_t*>(d_offsets1);
-  a.offsets2 = static_cast<const uint64_t*>(d_offsets2);
-  a.call_len1 = static_cast<const uint32_t*>(d_call_len1);
-  a.call_len2 = static_cast<const uint32_t*>(d_call_len2);
-  a.n = n;
-  a.excl = static_cast<uint32_t*>(d_excl);
-  a.totals = static_cast<unsigned long long*>(d_totals);
-  hipLaunchKernelGGL(k_pair_overlap, dim3(grid_for(n)), dim3(kBlock), 0, stream, a);
+  a.pairs = static_cast<const uint32_t*>(b.pairs);
+  a.offsets1 = static_cast<const uint64_t*>(b.offsets1);
+  a.offsets2 = static_cast<const uint64_t*>(b.offsets2);
+  a.call_len1 = static_cast<const uint32_t*>(b.call_len1);
+  a.call_len2 = static_cast<const uint32_t*>(b.call_len2);
+  a.n = b.n;
+  a.excl = static_cast<uint32_t*>(b.excl);
+  a.totals = static_cast<unsigned long long*>(b.totals);
+  hipLaunchKernelGGL(k_pair_overlap, dim3(grid_for(b.n)), dim3(kBlock), 0, stream, a);
   WALT_HIP(hipGetLastError());
   return WALT_OK;
 }
@@ -102,7 +109,7 @@ int walt_pair_overlap_batch_device(walt_index* idx, const void* d_pairs, const v
   if (((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_call_len1 & 3u) || ((uintptr_t)d_call_len2 & 3u) || ((uintptr_t)d_excl & 3u) ||
       ((uintptr_t)d_offsets1 & 7u) || ((uintptr_t)d_offsets2 & 7u) || ((uintptr_t)d_totals & 7u))
     return fail(WALT_EINVAL, who + ": pairs, call_len and excl must be 4-byte aligned, offsets and totals 8-byte aligned");
-  return overlap_launch(idx, d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2, d_excl, d_totals,
+  return overlap_launch(idx, {d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2, d_excl, d_totals},
                         reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -115,29 +122,19 @@ int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, cons
   for (uint32_t i = 0; i < n; ++i)
     if (offsets1[i + 1] < offsets1[i] || offsets2[i + 1] < offsets2[i]) return fail(WALT_EINVAL, who + ": offsets not non-decreasing");
   WALT_HIP(hipSetDevice(idx->device));
-  struct Scoped {
-    void* p = nullptr;
-    ~Scoped() { if (p) (void)hipFree(p); }
-    int get(size_t bytes) {
-      return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? WALT_OK : fail(WALT_ENOMEM, "hipMalloc failed (overlap of a pair)");
-    }
-  } d_pairs, d_off1, d_off2, d_len1, d_len2, d_excl, d_totals;
+  const char* what = "overlap of a pair";
+  DeviceTemp d_pairs, d_off1, d_off2, d_len1, d_len2, d_excl, d_totals;
   int rc;
   const size_t off_bytes = ((size_t)n + 1) * 8;
-  if ((rc = d_pairs.get((size_t)n * 64)) || (rc = d_off1.get(off_bytes)) || (rc = d_off2.get(off_bytes)) ||
-      (rc = d_excl.get((size_t)n * 4)))
-    return rc;
-  if (call_len1 && (rc = d_len1.get((size_t)n * 4))) return rc;
-  if (call_len2 && (rc = d_len2.get((size_t)n * 4))) return rc;
-  if (totals && (rc = d_totals.get(kOverlapTotals * 8))) return rc;
   // (only the differences of the offsets are used: relative to offsets[0] or not is the same)
-  WALT_HIP(hipMemcpy(d_pairs.p, pairs, (size_t)n * 64, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_off1.p, offsets1, off_bytes, hipMemcpyHostToDevice));
-  WALT_HIP(hipMemcpy(d_off2.p, offsets2, off_bytes, hipMemcpyHostToDevice));
-  if (call_len1) WALT_HIP(hipMemcpy(d_len1.p, call_len1, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (call_len2) WALT_HIP(hipMemcpy(d_len2.p, call_len2, (size_t)n * 4, hipMemcpyHostToDevice));
+  if ((rc = d_pairs.put(pairs, (size_t)n * 64, what)) || (rc = d_off1.put(offsets1, off_bytes, what)) ||
+      (rc = d_off2.put(offsets2, off_bytes, what)) || (rc = d_excl.get((size_t)n * 4, what)))
+    return rc;
+  if (call_len1 && (rc = d_len1.put(call_len1, (size_t)n * 4, what))) return rc;
+  if (call_len2 && (rc = d_len2.put(call_len2, (size_t)n * 4, what))) return rc;
+  if (totals && (rc = d_totals.get(kOverlapTotals * 8, what))) return rc;
   if (totals) WALT_HIP(hipMemset(d_totals.p, 0, kOverlapTotals * 8));
-  if ((rc = overlap_launch(idx, d_pairs.p, d_off1.p, d_off2.p, n, d_len1.p, d_len2.p, d_excl.p, d_totals.p, nullptr))) return rc;
+  if ((rc = overlap_launch(idx, {d_pairs.p, d_off1.p, d_off2.p, n, d_len1.p, d_len2.p, d_excl.p, d_totals.p}, nullptr))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   WALT_HIP(hipMemcpy(excl, d_excl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (totals) {

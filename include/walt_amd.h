@@ -619,6 +619,52 @@ int walt_meth_pileup_batch_mbias_device(walt_index* idx, walt_pileup* p, const v
                                         const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
                                         uint32_t table, void* stream);
 
+/* ---- ignored read ends: the first and last bases of a read kept out of the calls, per calling call ---------------------
+ * The reference has no such mode.  The bias table above shows which sequencing cycles are biased -- the end-repair fill-in
+ * at the 5' end of mate 2, adaptor and low-quality calls at the 3' end, the first cycles of random-primed PBAT libraries;
+ * these bounds keep them out of the counts (Bismark's --ignore, --ignore_3prime, --ignore_r2, --ignore_3prime_r2).  The
+ * contract is defined here.
+ *
+ * trim5 and trim3 are two uint32_t per calling call, uniform over the batch; a caller that calls one mate's reads per call
+ * so has per-mate values.  For a record of the batch, limit = min(length, call_len) as in the methylation calls.  Read
+ * position i may get a call exactly when  trim5 <= i  and  i + trim3 < limit  and every other rule allows it.  Positions
+ * are those of `bases` as given: the read as sequenced.  A position outside these bounds is treated exactly like a position
+ * at or beyond call_len: letter '.', no count in walt_meth_counts, no total in walt_meth_stats, no add to the pile-up --
+ * and nothing in the bias table, which is counted from the calls.  `reads` of walt_meth_stats is unchanged.  trim3 counts
+ * back from the clip point, not from the raw length: an adaptor that call_len clipped is not part of the molecule.  Any
+ * value is legal: trim5 >= limit, trim3 >= limit or trim5 + trim3 >= limit leaves a record with all '.' and zero counts.
+ * trim5 == trim3 == 0 is the call as it was.
+ *
+ * walt_meth_pileup_batch_trim[_device] are walt_meth_pileup_batch_mbias[_device] plus trim5 and trim3.  They refuse what
+ * the bias forms refuse and nothing else: alignment, strides and null arguments as there; the pile-up, skip, excl and the
+ * bias set may each be NULL.  Every older entry point is this call with both bounds 0 and gives what it always gave.
+ *
+ * walt_pair_overlap_batch_trim[_device] are walt_pair_overlap_batch[_device] plus the bounds of both mates.  Mate 1's
+ * called span becomes
+ *   S1 = { f(p1 + j) : trim5_1 <= j, j + trim3_1 < min(len1, call_len1), p1 + j < hi }
+ * -- still one interval of forward positions; the word is 0 when it is empty.  Bases of mate 1 that are ignored are not
+ * called by mate 1, so mate 2 keeps its calls there.  The word's encoding and its clipping to [0, len2] are unchanged.
+ * Mate 2's own bounds do not move the interval (the calling call applies them); they enter totals[1], which counts the
+ * interval's positions j with trim5_2 <= j and j + trim3_2 < min(len2, call_len2): the calls mate 2 can actually lose.
+ * totals[0] counts the pairs with a non-zero word, as before.  All four bounds 0: the older call. */
+int walt_meth_pileup_batch_trim(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3);
+int walt_meth_pileup_batch_trim_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                       uint32_t table, uint32_t trim5, uint32_t trim3, void* stream);
+int walt_pair_overlap_batch_trim(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
+                                 uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl,
+                                 uint64_t* totals /*[2]: pairs, bases*/, uint32_t trim5_1, uint32_t trim3_1, uint32_t trim5_2,
+                                 uint32_t trim3_2);
+int walt_pair_overlap_batch_trim_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
+                                        uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
+                                        uint32_t trim5_1, uint32_t trim3_1, uint32_t trim5_2, uint32_t trim3_2, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -705,6 +705,98 @@ def run_soak_mbias(seeds, pattern=3):
         pattern, len(seeds), pairs_total, calls_total)
 
 
+def run_soak_trim(seeds, pattern=3):
+    """Ignored read ends (walt_meth_pileup_batch_trim, walt_pair_overlap_batch_trim) on the genomes of `seeds`: pairs cut
+    from fragments of every length, mapped on the GPU, then called with random bounds per mate -- 0, small, around the read
+    length, beyond it -- with and without the overlap's interval, clip points, skip bytes and the pile_rows option, into a
+    pile-up and a bias set.  Intervals, calls, counts, totals, the pile-up and the bias table are compared with the
+    restatement of tests/test_gpu_trim.py.  Returns the summary line, raises SoakMismatch at the first difference."""
+    import refio
+    import walt_amd
+    import test_gpu_trim as rule_of
+    from test_gpu_meth import reference_bases
+    from test_gpu_overlap import pile_letters
+    from test_gpu_pileup import expected_table
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 150)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    pairs_total = blanked_total = kept_total = 0
+    mb = walt_amd.MBias(0, 2, pattern=pattern)
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 49979687 + 23)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_trim_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern, many=rng.random() < 0.3)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                db = refio.DbIndex(path)
+                R = reference_bases(db)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                pile = None
+                try:
+                    idx.set_option("pile_rows", rng.randrange(2))
+                    r1, r2 = sample_fragments(rng, seqs, 120, lo, hi, refio)
+                    b1, o1 = walt_amd.pack_reads(r1)
+                    b2, o2 = walt_amd.pack_reads(r2)
+                    res, _ = idx.map_pe_batch(b1, o1, b2, o2, frag_range=2 * hi + 200)
+                    bound = lambda: rng.choice([0, 0, rng.randrange(1, 20), rng.randrange(lo - 3, hi + 3), 5000])
+                    t = [(bound(), bound()), (bound(), bound())]
+                    cl = [[rng.choice([len(r), len(r), len(r) // 2, 0, len(r) + 3]) for r in reads] if rng.random() < 0.5 else None
+                          for reads in (r1, r2)]
+                    skip = np.array([[rng.random() < 0.2, rng.random() < 0.2] for _ in r1], dtype=np.uint8) if rng.random() < 0.5 else None
+                    no_overlap = rng.random() < 0.6
+                    ex = words = None
+                    if no_overlap:
+                        ex, words, totals = rule_of.want_words(db.start_index, db.genome_len, res, r1, r2, cl[0], cl[1], t[0], t[1])
+                        got_words, got_totals = idx.pair_overlap(res, o1, o2, cl[0], cl[1], trim1=t[0], trim2=t[1])
+                        if got_words.tolist() != words.tolist() or got_totals.tolist() != totals:
+                            raise SoakMismatch("MISMATCH trim seed %d: intervals or totals differ under bounds %s (%s against %s)" % (
+                                seed, t, got_totals.tolist(), totals))
+                    pile = idx.pileup()
+                    mb.clear()
+                    acc = None
+                    for k, (b, o, reads, mate, cv) in enumerate(((b1, o1, r1, "m1", "T"), (b2, o2, r2, "m2", "A"))):
+                        sk = None if skip is None else skip[:, k]
+                        want = rule_of.want_mate(R, db.start_index, reads, res[mate], cv, cl[k], ex if k else None, sk, t[k])
+                        got = pile.add_batch(b, o, res[mate], cv, call_len=cl[k], skip=sk, excl=words if k else None, mbias=mb, mbias_table=k,
+                                             trim5=t[k][0], trim3=t[k][1])
+                        try:
+                            rule_of.assert_mate(got, want, "seed %d mate %d bounds %s" % (seed, k + 1, t[k]))
+                        except AssertionError as e:
+                            raise SoakMismatch("MISMATCH trim " + str(e)[:600])
+                        if not np.array_equal(mb.read(k), rule_of.want_table(want[0], o, res[mate], sk)):
+                            raise SoakMismatch("MISMATCH trim seed %d mate %d: the bias table differs" % (seed, k + 1))
+                        acc = pile_letters(db.start_index, db.genome_len, want[0], res[mate], sk, into=acc)
+                        plain = rule_of.want_mate(R, db.start_index, reads, res[mate], cv, cl[k], ex if k else None, sk)
+                        kept_total += int(want[1].sum())
+                        blanked_total += int(plain[1].sum() - want[1].sum())
+                    sites, off = pile.extract()
+                    want_sites, want_off = expected_table(R[0], db.start_index, *acc)
+                    if sites.tobytes() != want_sites.tobytes() or [int(off[0]), int(off[1])] != want_off:
+                        raise SoakMismatch("MISMATCH trim seed %d: the pile-up differs under bounds %s" % (seed, t))
+                    pairs_total += len(r1)
+                finally:
+                    if pile is not None:
+                        pile.close()
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        mb.close()
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    if len(seeds) >= 5 and (blanked_total < pairs_total or kept_total < pairs_total):
+        raise SoakMismatch("soak too thin: %d calls blanked, %d kept over %d pairs" % (blanked_total, kept_total, pairs_total))
+    return "soak ok: trim, pattern %d, %d genomes, %d pairs, %d calls kept and %d ignored identical to the restatement" % (
+        pattern, len(seeds), pairs_total, kept_total, blanked_total)
+
+
 def rpbat_rule(c, g):
     """The random-PBAT rule (include/walt_amd.h) on two single-conversion record arrays -> (records, conv)."""
     ct, gt = c["times"].astype(np.int64), g["times"].astype(np.int64)

@@ -249,6 +249,12 @@ def lib(pattern=None):
                                                c.c_size_t, vp, vp, u32]
     L.walt_meth_pileup_batch_mbias_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                       vp, c.c_size_t, vp, vp, u32, vp]
+    L.walt_meth_pileup_batch_trim.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                              c.c_size_t, vp, vp, u32, u32, u32]
+    L.walt_meth_pileup_batch_trim_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                     vp, c.c_size_t, vp, vp, u32, u32, u32, vp]
+    L.walt_pair_overlap_batch_trim.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, u32]
+    L.walt_pair_overlap_batch_trim_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -327,20 +333,30 @@ def _skip_arg(skip, n):
     return _bytes_arg(skip, n, "skip: a 1-d uint8 array with one element per read")
 
 
-def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip"):
+def _trim_arg(trim5, trim3):
+    """the ignored read ends of a call -> (trim5, trim3) when one is non-zero, else None; any uint32 value is legal"""
+    trim5, trim3 = int(trim5), int(trim3)
+    if not (0 <= trim5 < 1 << 32 and 0 <= trim3 < 1 << 32):
+        raise ValueError("trim5, trim3: 0 .. 2^32 - 1")
+    return (trim5, trim3) if trim5 or trim3 else None
+
+
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None):
     """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
-    stride), excl = (address,), mbias = (handle, table), each None when the caller gave none.  The narrowest form that
-    takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a call with skip only.
-    Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
-    widest = "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), each None when the caller gave none.  The
+    narrowest form that takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a
+    call with skip only.  Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
+    widest = "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
     if widest is None:
         name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
     else:  # (these three take a null pile-up, a null skip and a null excl)
         name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
         if widest != "skip":
             tail += excl or (None,)
-        if widest == "mbias":
-            tail += mbias
+        if widest in ("mbias", "trim"):
+            tail += mbias or (None, 0)
+        if widest == "trim":
+            tail += trim
     return getattr(L, name + ("_device" if device else "")), head, tail
 
 
@@ -607,7 +623,7 @@ class Index:
         self._ck(self._L.walt_index_enable_reference(self._h))
 
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                        stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
+                        stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
         strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
@@ -617,16 +633,20 @@ class Index:
         excl: a uint32 array with one word per read, as Index.pair_overlap returns it: the read positions
         [excl & 0xFFFF, excl >> 16) get no call (walt_meth_pileup_batch_excl; only when given).  mbias: an MBias set on
         this index's device; the calls of the batch are added to its table mbias_table under the same skip
-        (walt_meth_pileup_batch_mbias; only when given; want_calls may be False)."""
+        (walt_meth_pileup_batch_mbias; only when given; want_calls may be False).  trim5 / trim3: the first trim5 read
+        positions and the last trim3 before the clip point get no call (include/walt_amd.h, "ignored read ends":
+        walt_meth_pileup_batch_trim; only when one is non-zero)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
-                                skip, excl, mbias, mbias_table)
+                                skip, excl, mbias, mbias_table, trim5, trim3)
 
     # -- overlap of a pair (include/walt_amd.h states the rules) --------------------------------------------------
-    def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None):
+    def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None, trim1=(0, 0), trim2=(0, 0)):
         """Host-buffer form of walt_pair_overlap_batch.  pairs: a pair_result_dtype array; offsets1 / offsets2: the two
         mates' offsets (n + 1 each).  Returns (excl uint32[n]: per pair the read positions of mate 2 that mate 1 already
         calls, ex_lo | ex_hi << 16, 0 for none; totals uint64[2]: pairs with a non-empty interval, mate-2 bases
-        excluded)."""
+        excluded).  trim1 / trim2: (trim5, trim3) of mate 1 / mate 2, the ignored read ends their calling calls get
+        (walt_pair_overlap_batch_trim; only when one is non-zero)."""
+        trim = (_trim_arg(*trim1) or (0, 0)) + (_trim_arg(*trim2) or (0, 0))
         pairs = np.ascontiguousarray(pairs, dtype=pair_result_dtype)
         offsets1 = np.ascontiguousarray(offsets1, dtype=np.uint64)
         offsets2 = np.ascontiguousarray(offsets2, dtype=np.uint64)
@@ -641,24 +661,26 @@ class Index:
             cl.append(a)
         excl = np.zeros(n, dtype=np.uint32)
         totals = np.zeros(2, dtype=np.uint64)
-        self._ck(self._L.walt_pair_overlap_batch(self._h, _ptr(pairs) if n else None, _ptr(offsets1), _ptr(offsets2), n,
-                                                 _ptr(cl[0]) if n else None, _ptr(cl[1]) if n else None,
-                                                 _ptr(excl) if n else None, _ptr(totals)))
+        form, tail = (self._L.walt_pair_overlap_batch_trim, trim) if any(trim) else (self._L.walt_pair_overlap_batch, ())
+        self._ck(form(self._h, _ptr(pairs) if n else None, _ptr(offsets1), _ptr(offsets2), n,
+                      _ptr(cl[0]) if n else None, _ptr(cl[1]) if n else None, _ptr(excl) if n else None, _ptr(totals), *tail))
         return excl, totals
 
     def pair_overlap_device(self, d_pairs, d_offsets1, d_offsets2, n, d_excl, d_call_len1=None, d_call_len2=None,
-                            d_totals=None, stream=0):
+                            d_totals=None, stream=0, trim1=(0, 0), trim2=(0, 0)):
         """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  d_totals
-        (uint64[2]) is accumulated into, not cleared."""
-        self._ck(self._L.walt_pair_overlap_batch_device(self._h, d_pairs, d_offsets1, d_offsets2, int(n), d_call_len1,
-                                                        d_call_len2, d_excl, d_totals, stream))
+        (uint64[2]) is accumulated into, not cleared.  trim1 / trim2: as in pair_overlap
+        (walt_pair_overlap_batch_trim_device; only when one is non-zero)."""
+        trim = (_trim_arg(*trim1) or (0, 0)) + (_trim_arg(*trim2) or (0, 0))
+        form, tail = (self._L.walt_pair_overlap_batch_trim_device, trim) if any(trim) else (self._L.walt_pair_overlap_batch_device, ())
+        self._ck(form(self._h, d_pairs, d_offsets1, d_offsets2, int(n), d_call_len1, d_call_len2, d_excl, d_totals, *tail, stream))
 
     def pileup(self):
         """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
+                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
         records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
         positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
@@ -685,29 +707,30 @@ class Index:
                 raise ValueError("excl: a 1-d uint32 array with one word per read")
         form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
                                       excl is not None and (_ptr(excl_arr) if n else None,),
-                                      mbias is not None and (mbias.handle, int(mbias_table)))
+                                      mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3))
         self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
                       conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                                conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0,
-                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0):
+                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  mbias: an MBias set
         whose table mbias_table takes the calls too (walt_meth_pileup_batch_mbias_device with a null pile-up; d_calls
         must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
-        pile-up)."""
+        pile-up); trim5 / trim3: as in meth_call_batch (walt_meth_pileup_batch_trim_device)."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
-        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table)
+        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3)
 
-    def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table):
+    def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5=0,
+                           trim3=0):
         """Index.meth_call_batch_device (pile null) and Pileup.add_batch_device.  batch: the C arguments from d_bases to
         d_stats; skip_alone: the form a call with d_skip only goes to (the index's: walt_meth_pileup_batch_excl_device, a
         pile-up's: walt_meth_pileup_batch_skip_device)."""
         form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
                                       d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
-                                      skip_alone)
+                                      skip_alone, _trim_arg(trim5, trim3))
         self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
@@ -805,20 +828,20 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0):
+                  want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip, excl, mbias, mbias_table)
+                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
-                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0):
+                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
         MBias set whose table mbias_table takes the calls too (d_calls must be given)."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
-        self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table)
+        self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3)
 
     def extract(self, pos_lo=0, pos_hi=None):
         """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the

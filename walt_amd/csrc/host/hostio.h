@@ -470,5 +470,28 @@ inline void put_mbias_block(Sink& out, const uint64_t* count) {
     }
 }
 
+// ---------------------------------------------------------------- ignored read ends (bin/walt -I5 -I3 -I5R2 -I3R2)
+// The value of one of the four options (include/walt_amd.h, "ignored read ends"): a decimal integer from 0 to 1024
+// (no read is longer), nothing in front of or behind the digits.
+static const uint32_t kMaxIgnore = 1024;
+inline bool parse_ignore_value(const std::string& text, uint32_t& out) {
+  if (text.empty() || text.size() > 4) return false;
+  uint32_t v = 0;
+  for (const char c : text) {
+    if (c < '0' || c > '9') return false;
+    v = v * 10 + (uint32_t)(c - '0');
+  }
+  out = v;
+  return v <= kMaxIgnore;
+}
+// The settings line that ends a read file's part of <out>.methstats when a bound is non-zero, in the user's order:
+//   ignore <TAB> i5 <TAB> i3                              single-end (n = 2)
+//   ignore <TAB> i5 <TAB> i3 <TAB> i5r2 <TAB> i3r2        paired (n = 4)
+inline void put_ignore_line(Sink& out, const uint32_t* v, int n) {
+  out.lit("ignore");
+  for (int k = 0; k < n; ++k) { out.ch('\t'); out.u32(v[k]); }
+  out.ch('\n');
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

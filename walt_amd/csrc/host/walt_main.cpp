@@ -55,6 +55,11 @@ struct Options {
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
+  // -I5 -I3 -I5R2 -I3R2: the first / last bases of a read that get no methylation call (walt_meth_pileup_batch_trim), of
+  // the reads of -r or -1 ([0], [1]) and of the reads of -2 ([2], [3]); the user's order, also under -P and -RP
+  uint32_t ignore[4] = {0, 0, 0, 0};
+  bool ignore_given[4] = {false, false, false, false};
+  bool ignoring() const { return ignore[0] || ignore[1] || ignore[2] || ignore[3]; }
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -97,6 +102,14 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
+    else if (is_opt(a, "I5", "ignore") || is_opt(a, "I3", "ignore-3prime") || is_opt(a, "I5R2", "ignore-r2") ||
+             is_opt(a, "I3R2", "ignore-3prime-r2")) {  // extension: read ends kept out of the methylation calls
+      const int k = is_opt(a, "I5", "ignore") ? 0 : is_opt(a, "I3", "ignore-3prime") ? 1 : is_opt(a, "I5R2", "ignore-r2") ? 2 : 3;
+      const string v = val();
+      if (!hostio::parse_ignore_value(v, o.ignore[k]))
+        die(a + " (ignored read ends) wants a number of bases from 0 to 1024, not \"" + v + "\"");
+      o.ignore_given[k] = true;
+    }
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -130,6 +143,10 @@ static Options parse(int argc, const char** argv) {
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
   if (o.no_overlap && !o.meth && !o.methcounts && !o.mbias)
     die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB) there is nothing for it to do");
+  if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.meth && !o.methcounts && !o.mbias)
+    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC or -MB there is nothing for them to do");
+  if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
+    die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -677,14 +694,15 @@ static void process_se(const Options& o, const string& reads_file, const string&
     };
     // the calls of a share, on the device that mapped it: one call takes whatever the options give it -- the pile-up (-MC),
     // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB) -- each null without its
-    // option (all null: walt_meth_call_batch)
+    // option (all null: walt_meth_call_batch) -- and the ignored read ends (-I5 / -I3; both 0 without them: the kernels a
+    // run always launched)
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       if (!calling) return (int)WALT_OK;
-      return walt_meth_pileup_batch_mbias(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
-                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
-                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
-                                          o.meth ? &meth_of[d] : nullptr, dups.on() ? dups.dup.data() + lo : nullptr, 1, nullptr,
-                                          mbs.of(d), 0);
+      return walt_meth_pileup_batch_trim(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+                                         sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
+                                         clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
+                                         o.meth ? &meth_of[d] : nullptr, dups.on() ? dups.dup.data() + lo : nullptr, 1, nullptr,
+                                         mbs.of(d), 0, o.ignore[0], o.ignore[1]);
     };
     if (!dups.on()) {
       dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
@@ -754,8 +772,10 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.meth) {
     Sink ms;
     put_meth_block(ms, meth_total);
+    if (o.ignoring()) hostio::put_ignore_line(ms, o.ignore, 2);
     write_methstats(out_file, ms);
   }
+  if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\n", o.ignore[0], o.ignore[1]);
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
   if (mbs.on()) {
     Sink ms;
@@ -948,6 +968,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   // a pair"); the user's mate 1 sits in slot 1 under -P.  The totals: pairs with an overlap, mate-2 bases left uncalled
   vector<uint32_t> excl;
   const int over_slot = pbat ? 0 : 1;  // the slot whose calls take the interval
+  // -I5 -I3 -I5R2 -I3R2: the bounds are given for the user's mate 1 and mate 2; under -P slot 0 holds the user's mate 2
+  const uint32_t* const trim_slot[2] = {o.ignore + (pbat ? 2 : 0), o.ignore + (pbat ? 0 : 2)};
   uint64_t overlap_total[2] = {0, 0};
   walt_meth_stats meth_total[2];  // per slot
   memset(meth_total, 0, sizeof meth_total);
@@ -1010,7 +1032,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
     // The calls of a share, on the device that mapped it.  -NO: first the share's intervals from the records in user order.
     // Then both slots through one call that takes whatever the options give it -- the pile-up (-MC: both mates into the
     // device's), the verdicts as skip bytes (-D), the interval words for the user's mate 2 (-NO; none for mate 1: the call
-    // it always got), the bias set (-MB: table k takes slot k) -- each null without its option.  Slot 0 was mapped C->T,
+    // it always got), the bias set (-MB: table k takes slot k) -- each null without its option -- and the slot's ignored
+    // read ends (0 without -I5 -I3 -I5R2 -I3R2: the kernels a run always launched).  Slot 0 was mapped C->T,
     // slot 1 G->A (-RP: as conv says).
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       int rc = WALT_OK;
@@ -1022,18 +1045,20 @@ static void process_pe(const Options& o, const string& file1, const string& file
           user.assign(pr + lo, pr + hi);
           for (walt_pair_result& p : user) std::swap(p.m1, p.m2);
         }
-        rc = walt_pair_overlap_batch(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
-                                     clip[u1].empty() ? nullptr : clip[u1].data() + lo,
-                                     clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
-                                     &overlap_of[2 * d]);
+        // (with ignored read ends, mate 1's called span is what they leave of it; mate 2's enter the second total)
+        rc = walt_pair_overlap_batch_trim(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
+                                          clip[u1].empty() ? nullptr : clip[u1].data() + lo,
+                                          clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
+                                          &overlap_of[2 * d], o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
       }
       for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_mbias(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
-                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
-                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
-                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
-                                          dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
-                                          o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k);
+        rc = walt_meth_pileup_batch_trim(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
+                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
+                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
+                                         dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
+                                         o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k,
+                                         trim_slot[k][0], trim_slot[k][1]);
       return rc;
     };
     if (!dups.on()) {
@@ -1159,10 +1184,12 @@ static void process_pe(const Options& o, const string& file1, const string& file
       snprintf(num, sizeof num, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
       ms.lit(num);
     }
+    if (o.ignoring()) hostio::put_ignore_line(ms, o.ignore, 4);
     write_methstats(out_file, ms);
   }
   if (o.no_overlap && o.verbose)
     fprintf(stderr, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
+  if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\t%u\t%u\n", o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
   if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
   if (mbs.on()) {  // in the user's order, as <out>.methstats
     Sink ms;
@@ -1183,7 +1210,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

@@ -163,6 +163,7 @@ struct MethArgs {
   const uint8_t* skip;         // null: none; else a record with a non-zero byte at skip[r * skip_stride] is not counted
   uint64_t skip_stride;
   const uint32_t* excl;        // null: none; else excl[r] = ex_lo | ex_hi << 16, read positions of record r that get no call
+  uint32_t trim5, trim3;       // the ignored read ends of the batch (include/walt_amd.h, "ignored read ends"); read by the kTrim instances alone
 };
 
 // One call of the pile-up: a 32-bit add whose result nobody reads (no value comes back from the memory side).
@@ -199,7 +200,11 @@ __device__ __forceinline__ void pile_rows(uint32_t cm, uint32_t cu, long long q0
 // kExcl: the batch comes with excluded intervals (a.excl).  An instance of its own: the calls without them run the
 // code they always ran (the word's load and the mask's arithmetic per slice cost the calling kernel 3 % when both
 // lived in one instance).
-template <int kPile, bool kExcl>
+// kTrim: the batch comes with ignored read ends (a.trim5, a.trim3: two scalars of the call, no load per record).  The 3'
+// bound comes off `limit`, the 5' bound is the lower end of every slice's range; a slice wholly outside them returns
+// inside meth_read_slice before it loads anything (all eight lanes of a group still take every trip: pile_rows).
+// Instances of their own for the same reason as kExcl: a call without bounds runs the code it always ran.
+template <int kPile, bool kExcl, bool kTrim>
 __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   __shared__ uint32_t s_start[kLdsChroms + 1];
   __shared__ unsigned long long s_red[kBlock / 64][kMethTotals];
@@ -220,6 +225,8 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     const uint32_t len = end > off && end - off <= kMaxReadLenAny ? (uint32_t)(end - off) : 0u;
     uint32_t limit = a.call_len ? a.call_len[r] : len;
     limit = limit < len ? limit : len;
+    if (kTrim) limit = meth_trim_limit(limit, a.trim3);
+    const uint32_t trim5 = kTrim ? a.trim5 : 0u;
     // unmapped, made up (a position outside the genome, an unknown conversion) or empty: no call anywhere
     const bool valid = times != 0 && pos < a.genome_len && (cv == 'T' || cv == 'A');
     const bool mapped = valid && limit != 0;
@@ -246,7 +253,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
           if (i0 < total) {
             uint32_t out[4];
             meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                            batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi);
+                            batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5);
             if (cb) meth_store_slice(cb + done, total, i0, out);
           }
           if (counted) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
@@ -264,7 +271,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
         for (int i0 = -h + 16 * (int)sub; i0 < total; i0 += 16 * (int)kMethGroup) {
           uint32_t out[4], cm, cu;
           meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                          batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi);
+                          batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5);
           if (kPile == 1 && counted)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
             pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
                        [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
@@ -307,12 +314,18 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) { meth_call_body<0, false>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile(const MethArgs a) { meth_call_body<1, false>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile_rows(const MethArgs a) { meth_call_body<2, false>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_call_excl(const MethArgs a) { meth_call_body<0, true>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile_excl(const MethArgs a) { meth_call_body<1, true>(a); }
-__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_excl(const MethArgs a) { meth_call_body<2, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call(const MethArgs a) { meth_call_body<0, false, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile(const MethArgs a) { meth_call_body<1, false, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows(const MethArgs a) { meth_call_body<2, false, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call_excl(const MethArgs a) { meth_call_body<0, true, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_excl(const MethArgs a) { meth_call_body<1, true, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_excl(const MethArgs a) { meth_call_body<2, true, false>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call_trim(const MethArgs a) { meth_call_body<0, false, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_trim(const MethArgs a) { meth_call_body<1, false, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_trim(const MethArgs a) { meth_call_body<2, false, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call_excl_trim(const MethArgs a) { meth_call_body<0, true, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_excl_trim(const MethArgs a) { meth_call_body<1, true, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_excl_trim(const MethArgs a) { meth_call_body<2, true, true>(a); }
 
 // folds the shards into walt_meth_stats (accumulating) and clears them
 __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
@@ -325,7 +338,7 @@ __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned 
   if (sum) atomicAdd(&stats[t], sum);
 }
 
-// One call of the calling kernel, through whichever of the ten entry points it came: the index, the destinations and
+// One call of the calling kernel, through whichever of the twelve entry points it came: the index, the destinations and
 // filters it may have, and the batch -- host arrays in a host form, device arrays in a device form and in meth_launch.
 // What an entry point does not have stays null.  (Initialised by name: hipcc takes designated initialisers in C++17.)
 struct MethCall {
@@ -347,6 +360,7 @@ struct MethCall {
   const void* excl = nullptr;
   walt_mbias* mb = nullptr;        // the bias set whose `table` takes the calls too
   uint32_t table = 0;
+  uint32_t trim5 = 0, trim3 = 0;   // the ignored read ends (include/walt_amd.h, "ignored read ends"); both 0: none
   void* stream = nullptr;          // device forms
 };
 
@@ -406,10 +420,16 @@ static int meth_launch(const MethCall& c) {
   a.skip = static_cast<const uint8_t*>(c.skip);
   a.skip_stride = c.skip_stride;
   a.excl = static_cast<const uint32_t*>(c.excl);
+  a.trim5 = c.trim5;
+  a.trim3 = c.trim3;
   const uint64_t want = ((uint64_t)c.n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
-  const auto kernel = a.excl ? (!c.pile ? k_meth_call_excl : idx->opt.pile_rows ? k_meth_pile_rows_excl : k_meth_pile_excl)
-                             : (!c.pile ? k_meth_call : idx->opt.pile_rows ? k_meth_pile_rows : k_meth_pile);
+  // [bounds][excl][no pile-up, pile-up, pile_rows]: a call whose bounds are both 0 runs the instances it always ran
+  static void (*const kernels[2][2][3])(const MethArgs) = {
+      {{k_meth_call, k_meth_pile, k_meth_pile_rows}, {k_meth_call_excl, k_meth_pile_excl, k_meth_pile_rows_excl}},
+      {{k_meth_call_trim, k_meth_pile_trim, k_meth_pile_rows_trim},
+       {k_meth_call_excl_trim, k_meth_pile_excl_trim, k_meth_pile_rows_excl_trim}}};
+  const auto kernel = kernels[c.trim5 || c.trim3][a.excl != nullptr][!c.pile ? 0 : idx->opt.pile_rows ? 2 : 1];
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   if (c.stats)
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
@@ -419,7 +439,7 @@ static int meth_launch(const MethCall& c) {
   return mbias_launch(c.mb, c.table, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream);
 }
 
-// the five device forms: asynchronous on the caller's stream
+// the six device forms: asynchronous on the caller's stream
 static int meth_batch_device(const MethCall& c) {
   const std::string who(c.who);
   if (const int rc = meth_call_check(c, c.calls != nullptr)) return rc;
@@ -430,7 +450,7 @@ static int meth_batch_device(const MethCall& c) {
   return meth_launch(c);
 }
 
-// The five host forms: the batch into device temporaries of this call (offsets relative to the first read, the
+// The six host forms: the batch into device temporaries of this call (offsets relative to the first read, the
 // caller's strided arrays packed: its strides stay on the host), the kernels on the null stream, the results back --
 // calls at calls + offsets[0], stats accumulated into.
 static int meth_batch_host(const MethCall& c) {
@@ -604,6 +624,33 @@ int walt_meth_pileup_batch_mbias(walt_index* idx, walt_pileup* p, const char* ba
                           .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
                           .calls = calls, .counts = counts, .stats = stats,
                           .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table});
+}
+
+// the bias forms plus the ignored read ends of the batch (include/walt_amd.h, "ignored read ends"); both 0: the bias form
+int walt_meth_pileup_batch_trim_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                       uint32_t table, uint32_t trim5, uint32_t trim3, void* stream) {
+  return meth_batch_device({.who = "walt_meth_pileup_batch_trim_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .mb = mb, .table = table,
+                            .trim5 = trim5, .trim3 = trim3, .stream = stream});
+}
+
+int walt_meth_pileup_batch_trim(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3) {
+  return meth_batch_host({.who = "walt_meth_pileup_batch_trim", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
+                          .trim5 = trim5, .trim3 = trim3});
 }
 
 }  // extern "C"

@@ -93,10 +93,13 @@ WALT_HD MethSlice meth_slice(const uint32_t rd[4], unsigned long long ext, uint3
 // of a read at genome position p in the chromosome [lo, hi), with `limit` = min(read length, call_len).
 // [ex_lo, ex_hi): read positions that get no call although they could (include/walt_amd.h, "overlap of a pair": the
 // other mate of the pair calls them); empty when ex_lo >= ex_hi.
+// trim5 >= 0: the read positions below it get no call (include/walt_amd.h, "ignored read ends").  The read's start and
+// the 5' bound are two lower ends of one range, the larger wins: the bound is the range's lower end, 0 without one.
+// (The 3' bound has no term here: the caller takes it off `limit`, meth_trim_limit.)
 WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long hi, long long limit, uint32_t ga,
-                              uint32_t& call, uint32_t& v1, uint32_t& v2, long long ex_lo, long long ex_hi) {
+                              uint32_t& call, uint32_t& v1, uint32_t& v2, long long ex_lo, long long ex_hi, long long trim5) {
   const long long room = hi - p;  // read positions below it lie inside the chromosome
-  call = meth_range(-i0, (limit < room ? limit : room) - i0) & ~meth_range(ex_lo - i0, ex_hi - i0);
+  call = meth_range(trim5 - i0, (limit < room ? limit : room) - i0) & ~meth_range(ex_lo - i0, ex_hi - i0);
   if (ga) {  // context at q - 1, q - 2 >= lo  <=>  k >= lo + 1 - p - i0, lo + 2 - p - i0
     v1 = meth_range(lo + 1 - p - i0, 16);
     v2 = meth_range(lo + 2 - p - i0, 16);
@@ -106,9 +109,16 @@ WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long
   }
 }
 WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long hi, long long limit, uint32_t ga,
-                              uint32_t& call, uint32_t& v1, uint32_t& v2) {
-  meth_slice_flags(i0, p, lo, hi, limit, ga, call, v1, v2, 0, 0);
+                              uint32_t& call, uint32_t& v1, uint32_t& v2, long long ex_lo, long long ex_hi) {
+  meth_slice_flags(i0, p, lo, hi, limit, ga, call, v1, v2, ex_lo, ex_hi, 0);
 }
+WALT_HD void meth_slice_flags(long long i0, long long p, long long lo, long long hi, long long limit, uint32_t ga,
+                              uint32_t& call, uint32_t& v1, uint32_t& v2) {
+  meth_slice_flags(i0, p, lo, hi, limit, ga, call, v1, v2, 0, 0, 0);
+}
+// limit = min(read length, call_len) with the last trim3 positions before it taken off, saturating at 0: the 3' bound
+// counts back from the clip point (include/walt_amd.h, "ignored read ends")
+WALT_HD uint32_t meth_trim_limit(uint32_t limit, uint32_t trim3) { return limit > trim3 ? limit - trim3 : 0u; }
 
 // ext of meth_slice from the packed reference: positions qs = q0 - 2 .. qs + 31 (qs may be negative at the genome's
 // start: the fields below position 0 read as 0 and are never used, their positions lie outside every chromosome).
@@ -132,16 +142,18 @@ WALT_HD unsigned long long meth_ref_ext(const uint32_t* ref, long long qs, uint3
 // inside the batch (the neighbouring read's bases are masked out by the flags), byte by byte at the batch's two ends.
 // cm / cu = the slice's positions called methylated / unmethylated (field masks; 0 where nothing is called): what a
 // per-cytosine pile-up adds (pileup_core.h).  [ex_lo, ex_hi): the read positions excluded from calling (meth_slice_flags).
+// trim5: the read positions below it get no call; `limit` comes with the 3' bound taken off (meth_trim_limit).  A slice
+// that lies wholly below trim5 returns like one at or beyond `limit`: before any read byte or reference word is loaded.
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
                              uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
                              unsigned long long before, unsigned long long after, uint32_t out[4],
                              unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
-                             uint32_t ex_lo, uint32_t ex_hi) {
+                             uint32_t ex_lo, uint32_t ex_hi, uint32_t trim5) {
   out[0] = out[1] = out[2] = out[3] = 0x2E2E2E2Eu;
   cm = cu = 0;
-  if (!mapped || i0 >= (int)limit) return;
+  if (!mapped || i0 >= (int)limit || (long long)i0 + 16 <= (long long)trim5) return;
   uint32_t call, v1, v2;
-  meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2, ex_lo, ex_hi);
+  meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2, ex_lo, ex_hi, trim5);
   if (!call) return;
   uint32_t rd[4] = {0, 0, 0, 0};
   if ((i0 >= 0 || (unsigned long long)(-i0) <= before) && (unsigned long long)(i0 + 16) <= after) {
@@ -157,7 +169,14 @@ WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool 
   meth += s.meth; unmeth += s.unmeth;
   cm = s.cm; cu = s.cu;
 }
-// the forms without an excluded interval: what they always gave
+// the form without ignored ends, and the forms without an excluded interval: what they always gave
+WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
+                             uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
+                             unsigned long long before, unsigned long long after, uint32_t out[4],
+                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
+                             uint32_t ex_lo, uint32_t ex_hi) {
+  meth_read_slice(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu, ex_lo, ex_hi, 0u);
+}
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
                              uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
                              unsigned long long before, unsigned long long after, uint32_t out[4],

@@ -26,6 +26,7 @@ struct OverlapArgs {
   uint32_t n;
   uint32_t* excl;
   unsigned long long* totals;  // null: not wanted
+  uint32_t trim[4];            // the ignored read ends: trim5_1, trim3_1, trim5_2, trim3_2 (all 0: none)
 };
 
 // One pair per lane: 64 bytes of record, two offsets per mate, the optional clip points, one look-up over the staged
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_overlap(const OverlapArgs a) {
     const uint64_t b1 = a.offsets1[i], e1 = a.offsets1[i + 1], b2 = a.offsets2[i], e2 = a.offsets2[i + 1];
     const uint64_t len1 = e1 > b1 ? e1 - b1 : 0, len2 = e2 > b2 ? e2 - b2 : 0;
     word = overlap_pair(s_start, a.start_index, tab, a.genome_len, p1, t1, s1 == '-', p2, t2, s2 == '-', best_times, len1, len2,
-                        a.call_len1 ? a.call_len1[i] : ~0u, a.call_len2 ? a.call_len2[i] : ~0u, bases);
+                        a.call_len1 ? a.call_len1[i] : ~0u, a.call_len2 ? a.call_len2[i] : ~0u, bases, a.trim[0], a.trim[1], a.trim[2], a.trim[3]);
     a.excl[i] = word;
   }
   if (!a.totals) return;  // (uniform)
@@ -72,6 +73,7 @@ struct OverlapBatch {
   uint32_t n;
   const void *call_len1, *call_len2;
   void *excl, *totals;
+  uint32_t trim[4] = {0, 0, 0, 0};  // trim5_1, trim3_1, trim5_2, trim3_2
 };
 
 static int overlap_launch(walt_index* idx, const OverlapBatch& b, hipStream_t stream) {
@@ -89,33 +91,35 @@ static int overlap_launch(walt_index* idx, const OverlapBatch& b, hipStream_t st
   a.n = b.n;
   a.excl = static_cast<uint32_t*>(b.excl);
   a.totals = static_cast<unsigned long long*>(b.totals);
+  for (int k = 0; k < 4; ++k) a.trim[k] = b.trim[k];
   hipLaunchKernelGGL(k_pair_overlap, dim3(grid_for(b.n)), dim3(kBlock), 0, stream, a);
   WALT_HIP(hipGetLastError());
   return WALT_OK;
 }
 
-}  // namespace walt
-
-using namespace walt;
-
-extern "C" {
-
-int walt_pair_overlap_batch_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
-                                   uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
-                                   void* stream) {
-  const std::string who = "walt_pair_overlap_batch_device";
+// the two device forms: asynchronous on the caller's stream (b: the caller's arrays, on the device)
+static int overlap_batch_device(const char* name, walt_index* idx, const OverlapBatch& b, void* stream) {
+  const std::string who(name);
+  const void *d_pairs = b.pairs, *d_offsets1 = b.offsets1, *d_offsets2 = b.offsets2, *d_call_len1 = b.call_len1, *d_call_len2 = b.call_len2;
+  const void *d_excl = b.excl, *d_totals = b.totals;
+  const uint32_t n = b.n;
   if (!idx) return fail(WALT_EINVAL, who + ": bad argument (null index)");
   if (n && (!d_pairs || !d_offsets1 || !d_offsets2 || !d_excl)) return fail(WALT_EINVAL, who + ": bad argument");
   if (((uintptr_t)d_pairs & 3u) || ((uintptr_t)d_call_len1 & 3u) || ((uintptr_t)d_call_len2 & 3u) || ((uintptr_t)d_excl & 3u) ||
       ((uintptr_t)d_offsets1 & 7u) || ((uintptr_t)d_offsets2 & 7u) || ((uintptr_t)d_totals & 7u))
     return fail(WALT_EINVAL, who + ": pairs, call_len and excl must be 4-byte aligned, offsets and totals 8-byte aligned");
-  return overlap_launch(idx, {d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2, d_excl, d_totals},
-                        reinterpret_cast<hipStream_t>(stream));
+  return overlap_launch(idx, b, reinterpret_cast<hipStream_t>(stream));
 }
 
-int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
-                            uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl, uint64_t* totals) {
-  const std::string who = "walt_pair_overlap_batch";
+// the two host forms: the batch into device temporaries of this call, the kernel on the null stream, the results back
+static int overlap_batch_host(const char* name, walt_index* idx, const OverlapBatch& b) {
+  const std::string who(name);
+  const walt_pair_result* pairs = static_cast<const walt_pair_result*>(b.pairs);
+  const uint64_t *offsets1 = static_cast<const uint64_t*>(b.offsets1), *offsets2 = static_cast<const uint64_t*>(b.offsets2);
+  const uint32_t *call_len1 = static_cast<const uint32_t*>(b.call_len1), *call_len2 = static_cast<const uint32_t*>(b.call_len2);
+  uint32_t* excl = static_cast<uint32_t*>(b.excl);
+  uint64_t* totals = static_cast<uint64_t*>(b.totals);
+  const uint32_t n = b.n;
   if (!idx) return fail(WALT_EINVAL, who + ": bad argument (null index)");
   if (n == 0) return WALT_OK;
   if (!pairs || !offsets1 || !offsets2 || !excl) return fail(WALT_EINVAL, who + ": bad argument");
@@ -134,7 +138,10 @@ int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, cons
   if (call_len2 && (rc = d_len2.put(call_len2, (size_t)n * 4, what))) return rc;
   if (totals && (rc = d_totals.get(kOverlapTotals * 8, what))) return rc;
   if (totals) WALT_HIP(hipMemset(d_totals.p, 0, kOverlapTotals * 8));
-  if ((rc = overlap_launch(idx, {d_pairs.p, d_off1.p, d_off2.p, n, d_len1.p, d_len2.p, d_excl.p, d_totals.p}, nullptr))) return rc;
+  OverlapBatch d = b;  // the same batch on the device copies
+  d.pairs = d_pairs.p; d.offsets1 = d_off1.p; d.offsets2 = d_off2.p; d.call_len1 = d_len1.p; d.call_len2 = d_len2.p;
+  d.excl = d_excl.p; d.totals = d_totals.p;
+  if ((rc = overlap_launch(idx, d, nullptr))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   WALT_HIP(hipMemcpy(excl, d_excl.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (totals) {
@@ -143,6 +150,40 @@ int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, cons
     for (uint32_t k = 0; k < kOverlapTotals; ++k) totals[k] += t[k];
   }
   return WALT_OK;
+}
+
+}  // namespace walt
+
+using namespace walt;
+
+extern "C" {
+
+int walt_pair_overlap_batch_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
+                                   uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
+                                   void* stream) {
+  return overlap_batch_device("walt_pair_overlap_batch_device", idx, {d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2,
+                                                                      d_excl, d_totals}, stream);
+}
+
+int walt_pair_overlap_batch(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
+                            uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl, uint64_t* totals) {
+  return overlap_batch_host("walt_pair_overlap_batch", idx, {pairs, offsets1, offsets2, n, call_len1, call_len2, excl, totals});
+}
+
+// the same with the ignored read ends of the two mates (include/walt_amd.h, "ignored read ends"); all 0: the calls above
+int walt_pair_overlap_batch_trim_device(walt_index* idx, const void* d_pairs, const void* d_offsets1, const void* d_offsets2,
+                                        uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
+                                        uint32_t trim5_1, uint32_t trim3_1, uint32_t trim5_2, uint32_t trim3_2, void* stream) {
+  return overlap_batch_device("walt_pair_overlap_batch_trim_device", idx,
+                              {d_pairs, d_offsets1, d_offsets2, n, d_call_len1, d_call_len2, d_excl, d_totals,
+                               {trim5_1, trim3_1, trim5_2, trim3_2}}, stream);
+}
+
+int walt_pair_overlap_batch_trim(walt_index* idx, const walt_pair_result* pairs, const uint64_t* offsets1, const uint64_t* offsets2,
+                                 uint32_t n, const uint32_t* call_len1, const uint32_t* call_len2, uint32_t* excl, uint64_t* totals,
+                                 uint32_t trim5_1, uint32_t trim3_1, uint32_t trim5_2, uint32_t trim3_2) {
+  return overlap_batch_host("walt_pair_overlap_batch_trim", idx,
+                            {pairs, offsets1, offsets2, n, call_len1, call_len2, excl, totals, {trim5_1, trim3_1, trim5_2, trim3_2}});
 }
 
 }  // extern "C"

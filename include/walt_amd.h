@@ -665,6 +665,77 @@ int walt_pair_overlap_batch_trim_device(walt_index* idx, const void* d_pairs, co
                                         uint32_t n, const void* d_call_len1, const void* d_call_len2, void* d_excl, void* d_totals,
                                         uint32_t trim5_1, uint32_t trim3_1, uint32_t trim5_2, uint32_t trim3_2, void* stream);
 
+/* ---- non-converted reads: reads that bisulfite did not convert, judged from their calls ----------------------------------
+ * The reference has no such mode (its users run a second program over the mapped reads: Bismark's filter_non_conversion
+ * with --threshold, --consecutive, --percentage_cutoff and --minimum_count); the contract is defined here.  A molecule that
+ * escaped conversion keeps its cytosines in non-CpG context, where most mammalian tissue has next to no methylation, so
+ * several methylated CHG / CHH calls in one read are a conversion failure, not biology.  The verdict needs the calls, their
+ * offsets and the records' times alone; acting on it is the caller's step: OR the byte into the skip array of the calling
+ * call that counts ("duplicates" above).
+ *
+ * Tally of a read.  Scan the bytes of its calls in read order, as walt_meth_call_batch wrote them:
+ *   meth  = the number of H and X bytes (methylated CHH and CHG);
+ *   total = meth + the number of h and x bytes;
+ *   run   = the longest run of H / X in read order, where only an h or an x ends a run.
+ * Every other byte -- '.', z, Z, u, U and anything else -- neither extends nor ends a run.
+ *
+ * Rule.  A judged read fails when any enabled test fires:
+ *   min_meth > 0     and  meth >= min_meth;
+ *   min_run > 0      and  run >= min_run;
+ *   min_percent > 0  and  total >= max(min_total, 1)  and  100 * meth >= min_percent * total   (integer arithmetic).
+ * A field of 0 switches its test off; a rule of all zeros filters nobody.  min_percent > 100 is WALT_EINVAL.
+ *
+ * Which records are judged.  A record is judged when times == 1 and its read has 1 to 1024 calls (device form: and its
+ * offsets lie inside [offsets[0], offsets[n])).  Every other record gets filt = 0 and a zero tally, and the kernel forms
+ * no address from it.  The verdict is a pure function of the read's calls and the rule: it does not depend on the grid,
+ * on the alignment of the calls or on how a stream of reads is cut into calls.
+ *
+ * walt_nonconv_batch[_device] judge calls that exist.  idx names the device (any strands, with or without the reference).
+ * filt[i * filt_stride] is written as 0 or 1 for every record (filt_stride at least 1; 2 with a base of filt or filt + 1 for
+ * one mate of a pair); tally[n] is optional (NULL: not wanted).  Strides and alignment as in walt_mbias_batch: a record
+ * stride of at least 16 and a multiple of 4; d_records 4-byte aligned, d_offsets and d_tally 8-byte aligned, d_calls and
+ * d_filt at any address.  Host form: offsets relative to offsets[0] or not, as the caller has them (calls + offsets[0] is
+ * the first byte read); a read of more than 1024 calls is not refused, it is not judged; it waits for the result.  Device
+ * form: pointers are HBM addresses on idx's device, asynchronous on `stream`.  WALT_EINVAL, with a message naming the
+ * cause, for a null index or rule, min_percent > 100, a null array with n > 0, a bad stride, a misaligned pointer.
+ *
+ * walt_meth_nonconv_batch[_device] call and judge in one step: the arguments of walt_meth_call_batch[_device] up to
+ * call_len, the optional output calls, then rule, filt, filt_stride and tally as above.  They refuse what the calling call
+ * refuses, and what walt_nonconv_batch refuses of the rule and filt.  They neither pile up nor sum statistics, and take
+ * no skip, excluded interval or ignored read end: the verdict is made from the whole read up to call_len, as Bismark's
+ * filter sees the whole XM string.  The host form stages the batch once and keeps its device copy of the calls for the
+ * judging kernel (it allocates the device array for itself when the caller's calls is NULL), so the calls do not cross the
+ * bus for the verdict.  The device form launches the judging kernel behind the calling kernel on the same stream;
+ * WALT_EINVAL when d_calls is NULL (the verdict is made from the calls).
+ *
+ * walt_nonconv_pairs_batch[_device] apply the pair rule in place on filt[2n], mate k + 1 of pair i at filt[2i + k]: for a
+ * pair with best_times == 1 both bytes become filt[2i] | filt[2i + 1] -- when either mate fails the pair goes, as in
+ * Bismark; any other pair keeps its mates' own verdicts.  The rule is symmetric in the mates.  d_pairs 4-byte aligned.
+ *
+ * Every older entry point is unchanged. */
+typedef struct {
+  uint16_t meth, total, run, reserved; /* reserved written as 0 */
+} walt_nonconv_tally; /* 8 bytes */
+typedef struct {
+  uint32_t min_meth, min_run, min_percent, min_total;
+} walt_nonconv_rule;
+int walt_nonconv_batch(walt_index* idx, const char* calls, const uint64_t* offsets, uint32_t n, const void* records,
+                       size_t record_stride, const walt_nonconv_rule* rule, uint8_t* filt, size_t filt_stride,
+                       walt_nonconv_tally* tally);
+int walt_nonconv_batch_device(walt_index* idx, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
+                              size_t record_stride, const walt_nonconv_rule* rule, void* d_filt, size_t filt_stride,
+                              void* d_tally, void* stream);
+int walt_meth_nonconv_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                            size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                            const uint32_t* call_len, char* calls, const walt_nonconv_rule* rule, uint8_t* filt,
+                            size_t filt_stride, walt_nonconv_tally* tally);
+int walt_meth_nonconv_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                   const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                   int conversion, const void* d_call_len, void* d_calls, const walt_nonconv_rule* rule,
+                                   void* d_filt, size_t filt_stride, void* d_tally, void* stream);
+int walt_nonconv_pairs_batch(walt_index* idx, const walt_pair_result* pairs, uint32_t n, uint8_t* filt /*[2n]*/);
+int walt_nonconv_pairs_batch_device(walt_index* idx, const void* d_pairs, uint32_t n, void* d_filt /*[2n]*/, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -705,6 +705,95 @@ def run_soak_mbias(seeds, pattern=3):
         pattern, len(seeds), pairs_total, calls_total)
 
 
+def run_soak_nonconv(seeds, pattern=3):
+    """Non-converted reads (walt_meth_nonconv_batch, walt_nonconv_batch, walt_nonconv_pairs_batch) on the genomes of `seeds`:
+    pairs cut from fragments of every length, some with call_len, mapped on the GPU; each mate called and judged in one
+    step under a random rule, the verdicts and tallies compared with the restatement in tests/test_gpu_nonconv.py over the
+    calls of the plain calling call, the pair rule with its restatement, and the totals of the calling call that takes the
+    verdicts as skip bytes with the letters of the kept unique records counted in Python.  Returns the summary line, raises
+    SoakMismatch at the first difference."""
+    import refio
+    import walt_amd
+    import test_gpu_nonconv as rule_of
+    refio.set_pattern(pattern)
+    walt_amd.set_pattern(pattern)
+    lo, hi = refio.MIN_READ_LEN[pattern], min(refio.MAX_READ_LEN[pattern], 150)
+    base = "/dev/shm" if os.path.isdir("/dev/shm") else None
+    pairs_total = judged_total = filtered_total = 0
+    try:
+        for seed in seeds:
+            rng = random.Random(seed * 49979687 + 23)
+            tmp = tempfile.mkdtemp(prefix="walt_soak_nonconv_", dir=base)
+            try:
+                seqs = make_genome(rng, pattern, many=rng.random() < 0.3)
+                fa = os.path.join(tmp, "g.fa")
+                with open(fa, "w") as f:
+                    for nm, sq in seqs:
+                        f.write(">%s\n%s\n" % (nm, sq))
+                path = os.path.join(tmp, "g.dbindex")
+                walt_amd.makedb(fa, path, threads=4)
+                idx = walt_amd.Index.open(path, device=0, strands=walt_amd.STRANDS_ALL | walt_amd.WITH_REFERENCE)
+                try:
+                    r1, r2 = sample_fragments(rng, seqs, 300, lo, hi, refio)
+                    b1, o1 = walt_amd.pack_reads(r1)
+                    b2, o2 = walt_amd.pack_reads(r2)
+                    res, _ = idx.map_pe_batch(b1, o1, b2, o2, frag_range=2 * hi + 200)
+                    # (the library keeps about half of its C: rules around that level, so that both outcomes occur)
+                    rule = (rng.choice([0, 0, 8, 12, 20]), rng.choice([0, 0, 4, 6]), rng.choice([0, 0, 50, 60, 100]), rng.choice([0, 1, 5, 12]))
+                    if not any(rule[:3]):
+                        rule = (10,) + rule[1:]
+                    r = walt_amd.nonconv_rule(*rule)
+                    cols, kept = [], []
+                    for k, (b, o, reads, mate, cv) in enumerate(((b1, o1, r1, "m1", "T"), (b2, o2, r2, "m2", "A"))):
+                        cl = [rng.choice([len(x), len(x), len(x) // 2, 0, len(x) + 3]) for x in reads] if rng.random() < 0.5 else None
+                        calls = idx.meth_call_batch(b, o, res[mate], cv, call_len=cl, want_counts=False, want_stats=False)[0]
+                        want_f, want_t = rule_of.expected_verdicts(calls, o, res[mate]["times"], rule)
+                        filt, tally, got_calls = idx.meth_nonconv_batch(b, o, res[mate], r, cv, call_len=cl, want_calls=True)
+                        again, tally2 = idx.nonconv_batch(calls, o, res[mate], r)
+                        if got_calls.tobytes() != calls.tobytes():
+                            raise SoakMismatch("MISMATCH nonconv seed %d mate %d: the calls of the one-step form differ" % (seed, k + 1))
+                        for f, t in ((filt, tally), (again, tally2)):
+                            if not (np.array_equal(f, want_f) and np.array_equal(rule_of.tally_array(t), want_t)):
+                                bad = np.nonzero((f != want_f) | (rule_of.tally_array(t) != want_t).any(axis=1))[0][:4]
+                                raise SoakMismatch("MISMATCH nonconv seed %d mate %d rule %s: reads %s" % (seed, k + 1, rule, bad.tolist()))
+                        cols.append(filt)
+                        kept.append((b, o, mate, cv, cl, calls))
+                        judged_total += int((res[mate]["times"] == 1).sum())
+                    filt = np.stack(cols, axis=1)
+                    want = rule_of.pair_rule(filt, res["best_times"])
+                    got = idx.nonconv_pairs(res, filt.copy())
+                    if not np.array_equal(got, want):
+                        raise SoakMismatch("MISMATCH nonconv seed %d: the pair rule differs at %s" % (seed, np.argwhere(got != want)[:4].tolist()))
+                    for k, (b, o, mate, cv, cl, calls) in enumerate(kept):
+                        stats = idx.meth_call_batch(b, o, res[mate], cv, call_len=cl, want_calls=False, want_counts=False,
+                                                    skip=np.ascontiguousarray(got[:, k]))[2]
+                        m, u, reads = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), 0
+                        for i in range(len(o) - 1):
+                            if int(res[mate]["times"][i]) != 1 or got[i, k]:
+                                continue
+                            reads += 1
+                            seg = calls[int(o[i]):int(o[i + 1])].tobytes()
+                            for c, pair in enumerate(("zZ", "xX", "hH", "uU")):
+                                u[c] += np.uint64(seg.count(pair[0].encode()))
+                                m[c] += np.uint64(seg.count(pair[1].encode()))
+                        if not (int(stats["reads"][0]) == reads and np.array_equal(m, stats["meth"][0]) and np.array_equal(u, stats["unmeth"][0])):
+                            raise SoakMismatch("MISMATCH nonconv seed %d mate %d: totals of the filtered call %s, counted %d %s %s" % (
+                                seed, k + 1, stats, reads, m, u))
+                    filtered_total += int(got.sum())
+                    pairs_total += len(r1)
+                finally:
+                    idx.close()
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
+    finally:
+        refio.set_pattern(3)
+        walt_amd.set_pattern(3)
+    if filtered_total == 0 or filtered_total >= judged_total:
+        raise SoakMismatch("soak too thin: %d of %d judged reads filtered" % (filtered_total, judged_total))
+    return "soak ok: nonconv, pattern %d, %d genomes, %d pairs, %d unique reads judged, %d verdicts of 1, all identical to the restatement" % (
+        pattern, len(seeds), pairs_total, judged_total, filtered_total)
+
+
 def run_soak_trim(seeds, pattern=3):
     """Ignored read ends (walt_meth_pileup_batch_trim, walt_pair_overlap_batch_trim) on the genomes of `seeds`: pairs cut
     from fragments of every length, mapped on the GPU, then called with random bounds per mate -- 0, small, around the read

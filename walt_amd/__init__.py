@@ -85,6 +85,10 @@ METH_CONTEXTS = ("CpG", "CHG", "CHH", "unknown")
 meth_site_dtype = np.dtype([("pos", "<u4"), ("meth", "<u4"), ("unmeth", "<u4"), ("strand", "u1"), ("context", "u1"),
                             ("reserved", "<u2")])
 assert meth_site_dtype.itemsize == 16
+# walt_nonconv_tally / walt_nonconv_rule (include/walt_amd.h, "non-converted reads")
+nonconv_tally_dtype = np.dtype([("meth", "<u2"), ("total", "<u2"), ("run", "<u2"), ("reserved", "<u2")])
+nonconv_rule_dtype = np.dtype([("min_meth", "<u4"), ("min_run", "<u4"), ("min_percent", "<u4"), ("min_total", "<u4")])
+assert nonconv_tally_dtype.itemsize == 8 and nonconv_rule_dtype.itemsize == 16
 assert meth_counts_dtype.itemsize == 16 and meth_stats_dtype.itemsize == 72
 assert best_match_dtype.itemsize == 16 and candidate_dtype.itemsize == 12
 assert pair_result_dtype.itemsize == 64 and batch_stats_dtype.itemsize == 32
@@ -255,6 +259,13 @@ def lib(pattern=None):
                                                      vp, c.c_size_t, vp, vp, u32, u32, u32, vp]
     L.walt_pair_overlap_batch_trim.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, u32]
     L.walt_pair_overlap_batch_trim_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, u32, vp]
+    L.walt_nonconv_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, vp, c.c_size_t, vp]
+    L.walt_nonconv_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, vp, c.c_size_t, vp, vp]
+    L.walt_meth_nonconv_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, c.c_size_t, vp]
+    L.walt_meth_nonconv_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, c.c_size_t,
+                                                 vp, vp]
+    L.walt_nonconv_pairs_batch.argtypes = [vp, vp, u32, vp]
+    L.walt_nonconv_pairs_batch_device.argtypes = [vp, vp, u32, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -339,6 +350,26 @@ def _trim_arg(trim5, trim3):
     if not (0 <= trim5 < 1 << 32 and 0 <= trim3 < 1 << 32):
         raise ValueError("trim5, trim3: 0 .. 2^32 - 1")
     return (trim5, trim3) if trim5 or trim3 else None
+
+
+def nonconv_rule(min_meth=0, min_run=0, min_percent=0, min_total=0):
+    """A walt_nonconv_rule (include/walt_amd.h, "non-converted reads") as a 1-element nonconv_rule_dtype array: a read
+    fails with min_meth or more methylated non-CpG calls, with a run of min_run or more of them, or with min_percent
+    percent or more of its non-CpG calls methylated when it has at least max(min_total, 1); 0 switches a test off.  Any
+    uint32 is taken here: the library refuses min_percent above 100."""
+    r = np.zeros(1, dtype=nonconv_rule_dtype)
+    for name, v in (("min_meth", min_meth), ("min_run", min_run), ("min_percent", min_percent), ("min_total", min_total)):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError("%s: 0 .. 2^32 - 1" % name)
+        r[name] = int(v)
+    return r
+
+
+def _rule_arg(rule):
+    rule = np.ascontiguousarray(rule, dtype=nonconv_rule_dtype)
+    if rule.size != 1:
+        raise ValueError("rule: one nonconv_rule_dtype element (walt_amd.nonconv_rule(...))")
+    return rule
 
 
 def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None):
@@ -638,6 +669,75 @@ class Index:
         walt_meth_pileup_batch_trim; only when one is non-zero)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
                                 skip, excl, mbias, mbias_table, trim5, trim3)
+
+    # -- non-converted reads (include/walt_amd.h states the rules) ------------------------------------------------
+    def nonconv_batch(self, calls, offsets, records, rule, want_tally=True):
+        """Host-buffer form of walt_nonconv_batch.  calls: the uint8 array Index.meth_call_batch returned (indexed from
+        offsets[0]); records: a best_match_dtype array or strided view; rule: walt_amd.nonconv_rule(...).  Returns (filt
+        uint8[n]: 1 for a read the rule fails, tally nonconv_tally_dtype[n] or None).  Waits for the result."""
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        rule = _rule_arg(rule)
+        n = offsets.size - 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        filt = np.zeros(n, dtype=np.uint8)
+        tally = np.zeros(n, dtype=nonconv_tally_dtype) if want_tally else None
+        calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
+        self._ck(self._L.walt_nonconv_batch(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, _ptr(rule),
+                                            _ptr(filt) if n else None, 1, _ptr(tally) if n else None))
+        return filt, tally
+
+    def nonconv_batch_device(self, d_calls, d_offsets, n, d_records, rule, d_filt, record_stride=16, filt_stride=1, d_tally=None,
+                             stream=0):
+        """Device-pointer form (ints are HBM addresses on this index's device, stream a hipStream_t value); asynchronous."""
+        rule = _rule_arg(rule)
+        self._ck(self._L.walt_nonconv_batch_device(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride), _ptr(rule),
+                                                   d_filt, int(filt_stride), d_tally, stream))
+
+    def nonconv_pairs(self, pairs, filt):
+        """The pair rule in place (walt_nonconv_pairs_batch).  pairs: a pair_result_dtype array; filt: a contiguous uint8
+        array of 2 n bytes (shape [2n] or [n, 2]), mate k + 1 of pair i at 2 i + k.  Returns filt."""
+        pairs = np.ascontiguousarray(pairs, dtype=pair_result_dtype)
+        n = pairs.size
+        if not isinstance(filt, np.ndarray) or filt.dtype != np.uint8 or filt.size != 2 * n or not filt.flags.c_contiguous:
+            raise ValueError("filt: a contiguous uint8 array with two bytes per pair")
+        self._ck(self._L.walt_nonconv_pairs_batch(self._h, _ptr(pairs) if n else None, n, _ptr(filt) if n else None))
+        return filt
+
+    def nonconv_pairs_device(self, d_pairs, n, d_filt, stream=0):
+        """Device-pointer form of the pair rule; asynchronous."""
+        self._ck(self._L.walt_nonconv_pairs_batch_device(self._h, d_pairs, int(n), d_filt, stream))
+
+    def meth_nonconv_batch(self, bases, offsets, records, rule, conv="T", call_len=None, want_calls=False, want_tally=True):
+        """Calls and judges in one step (walt_meth_nonconv_batch): the arguments of meth_call_batch plus the rule.  Returns
+        (filt uint8[n], tally nonconv_tally_dtype[n] or None, calls uint8[total bases] or None)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        rule = _rule_arg(rule)
+        n = offsets.size - 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        conv_arr, conv_ptr, conv_stride, conversion = _conv_arg(conv, n)
+        cl = None if call_len is None else np.ascontiguousarray(call_len, dtype=np.uint32)
+        if cl is not None and cl.size != n:
+            raise ValueError("call_len: one element per read")
+        total = int(offsets[n] - offsets[0]) if n else 0
+        calls = np.zeros(total, dtype=np.uint8) if want_calls else None
+        calls_ptr = None if calls is None else calls.ctypes.data - int(offsets[0]) if n else calls.ctypes.data
+        filt = np.zeros(n, dtype=np.uint8)
+        tally = np.zeros(n, dtype=nonconv_tally_dtype) if want_tally else None
+        self._ck(self._L.walt_meth_nonconv_batch(self._h, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr,
+                                                 conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(rule),
+                                                 _ptr(filt) if n else None, 1, _ptr(tally) if n else None))
+        return filt, tally, calls
+
+    def meth_nonconv_batch_device(self, d_bases, d_offsets, n, d_records, rule, d_calls, d_filt, record_stride=16, d_conv=None,
+                                  conv_stride=1, conversion="T", d_call_len=None, filt_stride=1, d_tally=None, stream=0):
+        """Device-pointer form: the calling kernel, then the judging kernel on the calls it wrote, on `stream`; d_calls
+        must be given."""
+        rule = _rule_arg(rule)
+        self._ck(self._L.walt_meth_nonconv_batch_device(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv,
+                                                        int(conv_stride), ord(conversion), d_call_len, d_calls, _ptr(rule), d_filt,
+                                                        int(filt_stride), d_tally, stream))
 
     # -- overlap of a pair (include/walt_amd.h states the rules) --------------------------------------------------
     def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None, trim1=(0, 0), trim2=(0, 0)):

@@ -150,6 +150,23 @@ struct MbiasBatch {
 };
 int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream);
 
+// nonconv.hip: one batch of calls as the judging kernel reads it (device arrays; tally null: not wanted), the kernel on
+// `stream` of idx's device, what every form refuses of a rule and a filt array (empty: nothing), and the end of a host
+// form: the packed device verdicts into the caller's strided bytes, the tallies as they are
+struct NonconvBatch {
+  const void *calls, *offsets;
+  uint32_t n;
+  const void* records;
+  size_t rec_stride;
+  walt_nonconv_rule rule;
+  void* filt;
+  size_t filt_stride;
+  void* tally;
+};
+int nonconv_launch(const walt_index* idx, const NonconvBatch& b, hipStream_t stream);
+std::string nonconv_refusal(const walt_nonconv_rule* rule, const void* filt, size_t filt_stride);
+int nonconv_results(const void* d_filt, const void* d_tally, uint32_t n, uint8_t* filt, size_t filt_stride, walt_nonconv_tally* tally);
+
 // A device temporary of one call, freed on every return path.  `what` names the call in the out-of-memory message
 // ("methylation calls", "duplicates", ...).  The host forms of the methylation-side calls allocate theirs per call.
 struct DeviceTemp {

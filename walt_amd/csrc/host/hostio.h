@@ -493,5 +493,28 @@ inline void put_ignore_line(Sink& out, const uint32_t* v, int n) {
   out.ch('\n');
 }
 
+// ---------------------------------------------------------------- non-converted reads (bin/walt -F -FC -FP -FM)
+// The value of one of the four options (include/walt_amd.h, "non-converted reads"): a decimal integer from lo to hi (at
+// most four digits), nothing in front of or behind the digits.
+inline bool parse_filter_value(const std::string& text, uint32_t lo, uint32_t hi, uint32_t& out) {
+  uint32_t v = 0;
+  if (!parse_ignore_value(text, v) || v < lo || v > hi) return false;
+  out = v;
+  return true;
+}
+// One read file's block of <out>.filterstats: the unique reads, unique pairs and lone unique mates that are not
+// duplicates, those of them the rule filtered, the rate as %.6f (NA without records), and the rule's four fields:
+//   rule <TAB> min_meth <TAB> min_run <TAB> min_percent <TAB> min_total
+inline void put_filter_block(Sink& out, uint64_t records, uint64_t filtered, const uint32_t rule[4]) {
+  char num[160];
+  if (records) snprintf(num, sizeof num, "records: %llu\nfiltered: %llu\nfilter rate: %.6f\n", (unsigned long long)records,
+                        (unsigned long long)filtered, (double)filtered / (double)records);
+  else snprintf(num, sizeof num, "records: %llu\nfiltered: %llu\nfilter rate: NA\n", (unsigned long long)records, (unsigned long long)filtered);
+  out.lit(num);
+  out.lit("rule");
+  for (int k = 0; k < 4; ++k) { out.ch('\t'); out.u32(rule[k]); }
+  out.ch('\n');
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

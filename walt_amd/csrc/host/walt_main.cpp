@@ -60,6 +60,11 @@ struct Options {
   uint32_t ignore[4] = {0, 0, 0, 0};
   bool ignore_given[4] = {false, false, false, false};
   bool ignoring() const { return ignore[0] || ignore[1] || ignore[2] || ignore[3]; }
+  // -F -FC -FP -FM: reads whose non-CpG calls say that bisulfite did not convert them (walt_meth_nonconv_batch) are kept out
+  // of the methylation counts: min_meth, min_run, min_percent, min_total of the rule; [3] is accepted only beside [2]
+  uint32_t filter[4] = {0, 0, 0, 0};
+  bool filter_given[4] = {false, false, false, false};
+  bool filtering() const { return filter_given[0] || filter_given[1] || filter_given[2]; }
   uint32_t max_mismatches = 6, batch_size = 10000000, b = 5000, top_k = 50;
   int frag_range = 1000, threads = 0;
   std::vector<int> devices;  // -g 0,1,...: every listed GPU holds an index replica and maps a contiguous share of each batch
@@ -110,6 +115,15 @@ static Options parse(int argc, const char** argv) {
         die(a + " (ignored read ends) wants a number of bases from 0 to 1024, not \"" + v + "\"");
       o.ignore_given[k] = true;
     }
+    else if (is_opt(a, "F", "filter-nonconv") || a == "--filter-non-conversion" || is_opt(a, "FC", "filter-consecutive") ||
+             is_opt(a, "FP", "filter-percent") || is_opt(a, "FM", "filter-min-count")) {  // extension: non-converted reads
+      const int k = is_opt(a, "FC", "filter-consecutive") ? 1 : is_opt(a, "FP", "filter-percent") ? 2 : is_opt(a, "FM", "filter-min-count") ? 3 : 0;
+      const uint32_t hi = k == 2 ? 100 : 1024;
+      const string v = val();
+      if (!hostio::parse_filter_value(v, 1, hi, o.filter[k]))
+        die(a + " (non-converted reads) wants a number from 1 to " + std::to_string(hi) + ", not \"" + v + "\"");
+      o.filter_given[k] = true;
+    }
     else if (is_opt(a, "b", "bucket")) o.b = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "k", "topk")) o.top_k = (uint32_t)strtoul(val().c_str(), 0, 10);
     else if (is_opt(a, "L", "fraglen")) o.frag_range = atoi(val().c_str());
@@ -147,6 +161,11 @@ static Options parse(int argc, const char** argv) {
     die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC or -MB there is nothing for them to do");
   if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
     die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
+  if (o.filter_given[3] && !o.filter_given[2])
+    die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
+  if ((o.filtering() || o.filter_given[3]) && !o.meth && !o.methcounts && !o.mbias)
+    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC or -MB there is nothing for them to do");
+  if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
 }
@@ -477,6 +496,53 @@ struct DupSet {
   }
 };
 
+// ---------------------------------------------------------------- -F -FC -FP -FM: non-converted reads
+// The verdicts of the current batch -- one byte per read, two per pair, as DupSet's -- made share by share on the device
+// that mapped the share: a first calling pass whose calls stay on the device and are judged there, then the pair rule.
+// skip is what the calling call that counts takes: the verdict ORed with the duplicate's byte.  A duplicate is judged like
+// any read, and a filtered read still enters the duplicate set (walt_dedup_* has no skip).
+struct FilterSet {
+  bool active = false;
+  walt_nonconv_rule rule = {0, 0, 0, 0};
+  vector<uint8_t> filt, skip;
+  uint64_t records = 0, filtered = 0;  // unique reads, unique pairs and lone unique mates that are no duplicates; those that failed
+  void open(const Options& o) {
+    active = o.filtering();
+    rule = walt_nonconv_rule{o.filter[0], o.filter[1], o.filter[2], o.filter[3]};
+  }
+  bool on() const { return active; }
+  void start(size_t bytes) { filt.assign(bytes, 0); skip.assign(bytes, 0); }
+  // the skip bytes [lo, hi) of the batch, stride 1 (a share's thread owns its range)
+  void merge(size_t lo, size_t hi, const uint8_t* dup) {
+    for (size_t j = lo; j < hi; ++j) skip[j] = (uint8_t)(filt[j] | (dup ? dup[j] : 0));
+  }
+  void count_se(const walt_best_match* res, const uint8_t* dup, uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j)
+      if (res[j].times == 1 && !(dup && dup[j])) { ++records; filtered += filt[j] != 0; }
+  }
+  void count_pe(const walt_pair_result* pr, const uint8_t* dup, uint32_t n) {
+    for (uint32_t j = 0; j < n; ++j) {
+      const size_t a = 2 * (size_t)j;
+      if (pr[j].best_times == 1) {
+        if (!(dup && dup[a])) { ++records; filtered += filt[a] != 0; }
+        continue;
+      }
+      if (pr[j].m1.times == 1 && !(dup && dup[a])) { ++records; filtered += filt[a] != 0; }
+      if (pr[j].m2.times == 1 && !(dup && dup[a + 1])) { ++records; filtered += filt[a + 1] != 0; }
+    }
+  }
+  void write_stats(const string& out_file, bool verbose) const {
+    Sink ms;
+    const uint32_t r[4] = {rule.min_meth, rule.min_run, rule.min_percent, rule.min_total};
+    hostio::put_filter_block(ms, records, filtered, r);
+    OutFile f;
+    if (!f.open_append(out_file + ".filterstats")) die("cannot open input file " + out_file + ".filterstats");
+    f.write(ms.p, ms.n);
+    f.close();
+    if (verbose) fwrite(ms.p, 1, ms.n, stderr);
+  }
+};
+
 static double g_t_main = 0;  // start of main (timeline under -v)
 static int host_threads(const Options& o) { return o.threads > 0 ? o.threads : hostio::effective_cpus(); }
 static double now_s() {
@@ -634,6 +700,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.mbias) mbs.open(dev.ids, 1);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
+  FilterSet flt;
+  flt.open(o);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   OutFile fout;
@@ -696,12 +764,24 @@ static void process_se(const Options& o, const string& reads_file, const string&
     // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB) -- each null without its
     // option (all null: walt_meth_call_batch) -- and the ignored read ends (-I5 / -I3; both 0 without them: the kernels a
     // run always launched)
+    // -F -FC -FP: first the share's verdicts (the whole read up to its clip point, whatever -I5 / -I3 say), ORed into the
+    // skip bytes beside -D's
+    if (flt.on()) flt.start(n);
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       if (!calling) return (int)WALT_OK;
+      const uint8_t* skip = dups.on() ? dups.dup.data() + lo : nullptr;
+      if (flt.on()) {
+        const int rc = walt_meth_nonconv_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
+                                               o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
+                                               clip.empty() ? nullptr : clip.data() + lo, nullptr, &flt.rule, flt.filt.data() + lo, 1, nullptr);
+        if (rc != WALT_OK) return rc;
+        flt.merge(lo, hi, dups.on() ? dups.dup.data() : nullptr);
+        skip = flt.skip.data() + lo;
+      }
       return walt_meth_pileup_batch_trim(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
-                                         o.meth ? &meth_of[d] : nullptr, dups.on() ? dups.dup.data() + lo : nullptr, 1, nullptr,
+                                         o.meth ? &meth_of[d] : nullptr, skip, 1, nullptr,
                                          mbs.of(d), 0, o.ignore[0], o.ignore[1]);
     };
     if (!dups.on()) {
@@ -714,6 +794,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
       dups.feed_se(res, o.rpbat ? conv.data() : nullptr, o.ag ? 'A' : 'T', n);
       if (calling) dev.for_each_share(n, meth_share);
     }
+    if (flt.on()) flt.count_se(res, dups.on() ? dups.dup.data() : nullptr, n);
     for (uint64_t v : short_of) st.too_short += (uint32_t)v;
     for (const walt_meth_stats& m : meth_of) add_meth(meth_total, m);
     t_map += now_s() - t0;
@@ -732,11 +813,13 @@ static void process_se(const Options& o, const string& reads_file, const string&
         // -R: a record of the G->A conversion is written as a -A run writes it (MR), or tagged (SAM)
         const bool ag = o.rpbat ? conv[j] == 'A' : o.ag;
         const bool dup = dups.on() && dups.dup[j];  // (a duplicate has times == 1: its only line is the main file's)
-        if (!o.sam) { if (!dup) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
+        const bool gone = flt.on() && flt.filt[j];  // (and so has a filtered read)
+        if (!o.sam) { if (!dup && !gone) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
                                                    s[kMain], s[kAmb1], s[kUnm1]); }
         else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain],
                             o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
-                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0}, dup ? 0x400 : 0);
+                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0},
+                            (dup ? 0x400 : 0) + (gone ? 0x200 : 0));
       }
       acc[t] = c;
     }
@@ -784,6 +867,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     mbs.close();
   }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
+  if (flt.on()) flt.write_stats(out_file, o.verbose);
   const double t_c0 = now_s();
   dev.close();
   if (o.verbose)
@@ -940,6 +1024,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   if (o.mbias) mbs.open(dev.ids, 2);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
+  FilterSet flt;
+  flt.open(o);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   hostio::FastqReader rd[2];
@@ -1035,9 +1121,24 @@ static void process_pe(const Options& o, const string& file1, const string& file
     // it always got), the bias set (-MB: table k takes slot k) -- each null without its option -- and the slot's ignored
     // read ends (0 without -I5 -I3 -I5R2 -I3R2: the kernels a run always launched).  Slot 0 was mapped C->T,
     // slot 1 G->A (-RP: as conv says).
+    // -F -FC -FP: before all that the verdicts of the share's two slots (each mate's whole read up to its clip point), the
+    // pair rule over them, and the skip bytes: the verdicts ORed with -D's
+    if (flt.on()) flt.start(2 * (size_t)n);
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       int rc = WALT_OK;
       if (!calling) return rc;
+      const uint8_t* skip = dups.on() ? dups.dup.data() : nullptr;
+      if (flt.on()) {
+        for (int k = 0; k < 2 && rc == WALT_OK; ++k)
+          rc = walt_meth_nonconv_batch(dev.idx[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
+                                       sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
+                                       clip[k].empty() ? nullptr : clip[k].data() + lo, nullptr, &flt.rule,
+                                       flt.filt.data() + 2 * (size_t)lo + k, 2, nullptr);
+        if (rc == WALT_OK) rc = walt_nonconv_pairs_batch(dev.idx[d], pr + lo, hi - lo, flt.filt.data() + 2 * (size_t)lo);
+        if (rc != WALT_OK) return rc;
+        flt.merge(2 * (size_t)lo, 2 * (size_t)hi, skip);
+        skip = flt.skip.data();
+      }
       if (o.no_overlap) {
         const int u1 = 1 - over_slot;
         vector<walt_pair_result> user;  // -P: mate 1 of the records is the user's mate 2
@@ -1056,7 +1157,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
-                                         dups.on() ? dups.dup.data() + 2 * (size_t)lo + k : nullptr, 2,
+                                         skip ? skip + 2 * (size_t)lo + k : nullptr, 2,
                                          o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k,
                                          trim_slot[k][0], trim_slot[k][1]);
       return rc;
@@ -1071,6 +1172,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
       dups.feed_pe(pr, rp ? conv.data() : nullptr, n);
       if (calling) dev.for_each_share(n, meth_share);
     }
+    if (flt.on()) flt.count_pe(pr, dups.on() ? dups.dup.data() : nullptr, n);
     for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
     for (size_t d = 0; 2 * d < overlap_of.size(); ++d) { overlap_total[0] += overlap_of[2 * d]; overlap_total[1] += overlap_of[2 * d + 1]; }
     for (size_t d = 0; d < dev.size(); ++d) { st1.too_short += (uint32_t)short1[d]; st2.too_short += (uint32_t)short2[d]; }
@@ -1093,14 +1195,16 @@ static void process_pe(const Options& o, const string& file1, const string& file
         const bool ag1 = rp && conv[2 * (size_t)j] == 'A', ag2 = !rp || conv[2 * (size_t)j + 1] == 'A';
         // -D: a duplicate's MR line is not written (the one fragment line of a duplicate pair), its SAM lines get 0x400
         const bool dup1 = dups.on() && dups.dup[2 * (size_t)j], dup2 = dups.on() && dups.dup[2 * (size_t)j + 1];
+        // -F -FC -FP: the same for a filtered record, with 0x200 (a unique pair's two bytes are equal: the pair rule)
+        const bool gone1 = flt.on() && flt.filt[2 * (size_t)j], gone2 = flt.on() && flt.filt[2 * (size_t)j + 1];
         if (p.best_times == 1) {
           a.unique_pairs++;
           walt_candidate r1 = {p.m1.genome_pos, p.m1.strand, {0, 0, 0}, p.m1.mismatch};
           walt_candidate r2 = {p.m2.genome_pos, p.m2.strand, {0, 0, 0}, p.m2.mismatch};
           if (ag1)  // -RP rule 3: the fragment of the mate-exchanged orientation, written from the T-rich mate 2 as -P writes it
-            len = put_fragment(r2, r1, o.frag_range, g, name, q2, k2, q1, k1, o.sam || dup1, s[kMain]);
+            len = put_fragment(r2, r1, o.frag_range, g, name, q2, k2, q1, k1, o.sam || dup1 || gone1, s[kMain]);
           else
-            len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam || dup1, s[kMain]);
+            len = put_fragment(r1, r2, o.frag_range, g, name, q1, k1, q2, k2, o.sam || dup1 || gone1, s[kMain]);
           a.frag_count[len]++;
           if (o.sam) { is_paired = true; bm1 = p.m1; bm2 = p.m2; }
         } else {
@@ -1109,18 +1213,18 @@ static void process_pe(const Options& o, const string& file1, const string& file
           a.st1.update(bm1.times);
           a.st2.update(bm2.times);
           if (!o.sam && !pbat) {  // (-RP: each mate by the writer of its conversion)
-            if (!dup1) out_single_results(bm1, name, q1, k1, g, ag1, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
-            if (!dup2) out_single_results(bm2, name, q2, k2, g, ag2, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
+            if (!dup1 && !gone1) out_single_results(bm1, name, q1, k1, g, ag1, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
+            if (!dup2 && !gone2) out_single_results(bm2, name, q2, k2, g, ag2, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
           } else if (!o.sam) {  // the user's mate 1 sits in slot 1
-            if (!dup2) out_single_results(bm2, name, q2, k2, g, true, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
-            if (!dup1) out_single_results(bm1, name, q1, k1, g, false, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
+            if (!dup2 && !gone2) out_single_results(bm2, name, q2, k2, g, true, side1.out_amb, side1.out_unm, s[kMain], s[kAmb1], s[kUnm1]);
+            if (!dup1 && !gone1) out_single_results(bm1, name, q1, k1, g, false, side2.out_amb, side2.out_unm, s[kMain], s[kAmb2], s[kUnm2]);
           }
         }
         if (o.sam) {
           int fl1 = sam_flag(is_paired, bm1.times == 0, bm2.times == 0, bm1.strand == '-', bm2.strand == '-', !pbat, bm1.times >= 2);
           int fl2 = sam_flag(is_paired, bm2.times == 0, bm1.times == 0, bm2.strand == '-', bm1.strand == '-', pbat, bm2.times >= 2);
-          fl1 += dup1 ? 0x400 : 0;
-          fl2 += dup2 ? 0x400 : 0;
+          fl1 += (dup1 ? 0x400 : 0) + (gone1 ? 0x200 : 0);
+          fl2 += (dup2 ? 0x400 : 0) + (gone2 ? 0x200 : 0);
           out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain],
                          rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
                          o.meth ? View{calls[0].data() + bt[0].offsets[j], q1.len} : View{nullptr, 0},
@@ -1199,6 +1303,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     mbs.close();
   }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
+  if (flt.on()) flt.write_stats(out_file, o.verbose);
   dev.close();
   if (o.verbose)
     fprintf(stderr, "[walt_amd: %d host threads, %zu GPU(s); index %.2f s, ingest not hidden behind the previous batch %.2f s, map %.2f s, "
@@ -1210,7 +1315,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1230,6 +1335,7 @@ int main(int argc, const char** argv) {
     if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
     if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
+    if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");
     size_t k = 0;

@@ -361,6 +361,12 @@ struct MethCall {
   walt_mbias* mb = nullptr;        // the bias set whose `table` takes the calls too
   uint32_t table = 0;
   uint32_t trim5 = 0, trim3 = 0;   // the ignored read ends (include/walt_amd.h, "ignored read ends"); both 0: none
+  // the rule that judges the calls too (include/walt_amd.h, "non-converted reads"; null: none), and where the verdicts go
+  bool rule_form = false;          // walt_meth_nonconv_batch[_device]: a rule must be given
+  const walt_nonconv_rule* rule = nullptr;
+  void* filt = nullptr;
+  size_t filt_stride = 0;
+  void* tally = nullptr;
   void* stream = nullptr;          // device forms
 };
 
@@ -387,6 +393,18 @@ static int meth_call_check(const MethCall& c, bool has_calls) {
       return fail(WALT_EINVAL, who + ": the bias table is counted from the calls: d_calls must not be NULL when a bias set is given");
   }
   if (!(bad = skip_stride_refusal(c.skip, c.skip_stride)).empty()) return fail(WALT_EINVAL, who + ": " + bad);
+  return WALT_OK;
+}
+
+// walt_meth_nonconv_batch[_device] on top of that: the rule, somewhere for the verdicts, calls to judge
+static int meth_nonconv_check(const MethCall& c, bool has_calls) {
+  const std::string who(c.who);
+  if (const int rc = meth_call_check(c, has_calls)) return rc;
+  const std::string bad = nonconv_refusal(c.rule, c.filt, c.filt_stride);
+  if (!bad.empty()) return fail(WALT_EINVAL, who + ": " + bad);
+  if (c.n && !c.filt) return fail(WALT_EINVAL, who + ": bad argument (null filt)");
+  if (!has_calls)
+    return fail(WALT_EINVAL, who + ": the verdict is made from the calls: d_calls must not be NULL");
   return WALT_OK;
 }
 
@@ -435,17 +453,21 @@ static int meth_launch(const MethCall& c) {
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
                        static_cast<unsigned long long*>(c.stats));
   WALT_HIP(hipGetLastError());
-  if (!c.mb) return WALT_OK;
-  return mbias_launch(c.mb, c.table, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream);
+  if (c.mb)
+    if (const int rc = mbias_launch(c.mb, c.table, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream))
+      return rc;
+  if (!c.rule) return WALT_OK;
+  return nonconv_launch(idx, {c.calls, c.offsets, c.n, c.records, c.record_stride, *c.rule, c.filt, c.filt_stride, c.tally}, stream);
 }
 
 // the six device forms: asynchronous on the caller's stream
 static int meth_batch_device(const MethCall& c) {
   const std::string who(c.who);
-  if (const int rc = meth_call_check(c, c.calls != nullptr)) return rc;
+  if (const int rc = c.rule_form ? meth_nonconv_check(c, c.calls != nullptr) : meth_call_check(c, c.calls != nullptr)) return rc;
   if (c.n && (!c.offsets || !c.records)) return fail(WALT_EINVAL, who + ": bad argument");
   if (((uintptr_t)c.records & 3u) || ((uintptr_t)c.counts & 7u) || ((uintptr_t)c.call_len & 3u) || ((uintptr_t)c.stats & 7u))
     return fail(WALT_EINVAL, who + ": records and call_len must be 4-byte aligned, counts and stats 8-byte aligned");
+  if ((uintptr_t)c.tally & 7u) return fail(WALT_EINVAL, who + ": tally must be 8-byte aligned");
   if ((uintptr_t)c.excl & 3u) return fail(WALT_EINVAL, who + ": excl must be 4-byte aligned");
   return meth_launch(c);
 }
@@ -455,7 +477,7 @@ static int meth_batch_device(const MethCall& c) {
 // calls at calls + offsets[0], stats accumulated into.
 static int meth_batch_host(const MethCall& c) {
   const std::string who(c.who);
-  int rc = meth_call_check(c, true);
+  int rc = c.rule_form ? meth_nonconv_check(c, true) : meth_call_check(c, true);
   if (rc) return rc;
   const uint32_t n = c.n;
   if (n == 0) return WALT_OK;
@@ -465,7 +487,7 @@ static int meth_batch_host(const MethCall& c) {
   const std::string bad = call_reads_refusal(c.who, offsets, n, static_cast<const uint8_t*>(c.conv), c.conv_stride);
   if (!bad.empty()) return fail(WALT_EINVAL, bad);
   walt_meth_stats* stats = static_cast<walt_meth_stats*>(c.stats);
-  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb) return WALT_OK;
+  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb && !c.rule) return WALT_OK;
   WALT_HIP(hipSetDevice(c.idx->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(c.records, c.record_stride, n);
@@ -474,7 +496,7 @@ static int meth_batch_host(const MethCall& c) {
   std::vector<uint64_t> rel;
   const uint64_t* off = rebase_offsets(offsets, n, rel);
   const char* const what = "methylation calls";
-  DeviceTemp d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl;
+  DeviceTemp d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl, d_filt, d_tally;
   if ((rc = d_bases.put(bases + offsets[0], nbytes, what, 16)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
       (rc = d_rec.put(rec.data(), (size_t)n * 16, what)))
     return rc;
@@ -482,7 +504,9 @@ static int meth_batch_host(const MethCall& c) {
   if (c.call_len && (rc = d_len.put(c.call_len, (size_t)n * 4, what))) return rc;
   if (c.skip && (rc = d_skip.put(sk.data(), n, what))) return rc;
   if (c.excl && (rc = d_excl.put(c.excl, (size_t)n * 4, what))) return rc;
-  if ((c.calls || c.mb) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias table is counted from the device copy)
+  if ((c.calls || c.mb || c.rule) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias table is counted, the verdict made, from the device copy)
+  if (c.rule && (rc = d_filt.get(n, what))) return rc;
+  if (c.rule && c.tally && (rc = d_tally.get((size_t)n * sizeof(walt_nonconv_tally), what))) return rc;
   if (c.counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts), what))) return rc;
   if (stats && (rc = d_stats.get(sizeof(walt_meth_stats), what))) return rc;
   if (stats) WALT_HIP(hipMemset(d_stats.p, 0, sizeof(walt_meth_stats)));
@@ -491,10 +515,14 @@ static int meth_batch_host(const MethCall& c) {
   d.conv = d_conv.p; d.conv_stride = 1; d.call_len = d_len.p;
   d.calls = d_calls.p; d.counts = d_counts.p; d.stats = d_stats.p;
   d.skip = d_skip.p; d.skip_stride = 1; d.excl = d_excl.p; d.stream = nullptr;
+  d.filt = d_filt.p; d.filt_stride = 1; d.tally = d_tally.p;
   if ((rc = meth_launch(d))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (c.calls && nbytes) WALT_HIP(hipMemcpy(static_cast<char*>(c.calls) + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
   if (c.counts) WALT_HIP(hipMemcpy(c.counts, d_counts.p, (size_t)n * sizeof(walt_meth_counts), hipMemcpyDeviceToHost));
+  if (c.rule && (rc = nonconv_results(d_filt.p, d_tally.p, n, static_cast<uint8_t*>(c.filt), c.filt_stride,
+                                      static_cast<walt_nonconv_tally*>(c.tally))))
+    return rc;
   if (stats) {
     walt_meth_stats st;
     WALT_HIP(hipMemcpy(&st, d_stats.p, sizeof(st), hipMemcpyDeviceToHost));
@@ -651,6 +679,30 @@ int walt_meth_pileup_batch_trim(walt_index* idx, walt_pileup* p, const char* bas
                           .calls = calls, .counts = counts, .stats = stats,
                           .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
                           .trim5 = trim5, .trim3 = trim3});
+}
+
+// the calling call plus the verdict on its calls (include/walt_amd.h, "non-converted reads"): no pile-up, no statistics
+int walt_meth_nonconv_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                   const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                   int conversion, const void* d_call_len, void* d_calls, const walt_nonconv_rule* rule,
+                                   void* d_filt, size_t filt_stride, void* d_tally, void* stream) {
+  return meth_batch_device({.who = "walt_meth_nonconv_batch_device", .idx = idx,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls,
+                            .rule_form = true, .rule = rule, .filt = d_filt, .filt_stride = filt_stride, .tally = d_tally,
+                            .stream = stream});
+}
+
+int walt_meth_nonconv_batch(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                            size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                            const uint32_t* call_len, char* calls, const walt_nonconv_rule* rule, uint8_t* filt,
+                            size_t filt_stride, walt_nonconv_tally* tally) {
+  return meth_batch_host({.who = "walt_meth_nonconv_batch", .idx = idx,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls,
+                          .rule_form = true, .rule = rule, .filt = filt, .filt_stride = filt_stride, .tally = tally});
 }
 
 }  // extern "C"

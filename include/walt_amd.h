@@ -755,6 +755,11 @@ int walt_nonconv_pairs_batch_device(walt_index* idx, const void* d_pairs, uint32
  *                     3 / 4 for reads of up to 128 bases, 2 / 3 up to 160)
  *   se_carry       1  pass 1 hands its state to the staged rounds (0: they start over at seed 0)
  *   se_heavy_mono  0  the one-kernel heavy pass instead of the staged rounds
+ *   se_verify_share 1 reads of up to 128 bases: the dense work items of a round grouped by the region they name, a
+ *                     region's records streamed once per group of reads (0: once per item, the launches as they were;
+ *                     2: grouped and counted, verified one by one -- tools/verify_share_bench.py)
+ *   se_share_r     0  with se_verify_share = 2 only: items per counted group at most (0: 4, as the verifier's; up to 64)
+ *   se_share_cap   0  items of a launch that are grouped (0: all; a test hook: the others are verified one by one)
  *   grid           0  blocks of the persistent kernels (0: 8 per compute unit)
  *   pe_mode        0  0: staged path, 1: list kernels only
  *   pe_chunk       0  pairs per pass (0: default)          pe_rounds    0  rounds of a staged list (0: default, 1, 2, 4)

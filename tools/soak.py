@@ -126,6 +126,9 @@ def run_soak(seconds, seed0=1, pattern=3, max_genomes=None):
             # is short, map_pe.hip k_pe_stage); drawn from a generator of its own so that a seed's genome and reads stay
             if random.Random(seed * 7919 + 13).random() < 0.25:
                 idx.set_option("pe_lit_fuse", 0)
+            # the dense items grouped by region (default) or verified one by one (map_se.hip k_se_verify_shared); a
+            # generator of its own again
+            idx.set_option("se_verify_share", random.Random(seed * 104729 + 7).choice([1, 1, 0]))
             lengths = [lo + 2, lo + 3, 40, 45, 60, 100, 100, 100, 131, 140, min(150, hi), min(200, hi), hi]
             # the kernels are instantiated per read-length class (up to 112, 128, 160 ... bases: the batch's longest read
             # selects the instance): some genomes get batches that stop at 112 or 128 bases

@@ -51,6 +51,9 @@ struct walt_options {
   int se_stage_occ = 0;       // wavefronts per SIMD the stage kernel is built for (0: default)
   int se_carry = 1;           // pass 1 hands its state to the staged rounds (0: they start over at seed 0)
   int se_heavy_mono = 0;      // the one-kernel heavy pass instead of the staged rounds (comparison)
+  int se_verify_share = 1;    // dense items of reads up to 128 bases grouped by region, a region streamed once per group (0: once per item)
+  int se_share_r = 0;         // se_verify_share = 2 (measurement: groups counted, items verified one by one): items per group at most (0: 4, the verifier's)
+  long long se_share_cap = 0; // items of a launch that are grouped (0: all; test hook: the others are verified one by one)
   long long grid = 0;         // blocks of the persistent mapping kernels (0: 8 per compute unit)
   // paired-end
   int pe_mode = 0;            // 0: staged path, 1: list kernels only

@@ -17,6 +17,7 @@
 
 #include "map_common.h"
 #include "map_items.h"
+#include "group_core.h"
 
 namespace walt {
 
@@ -1619,6 +1620,385 @@ __global__ __launch_bounds__(kBlock, G > 1 ? (NW <= 8 ? 3 : 2) : DENSE ? (NW <= 
   flush_counters({0u, sink.n_verified, 0u}, 0u, stats);
 }
 
+// ---------------------------------------------------------------------------
+// Dense items grouped by region (group_core.h; option se_verify_share).  Reads whose seeds have the same key name
+// the same region, and k_se_verify streams it once per item.  Between a round's stage launch and its dense verifier:
+// the items are counted per bucket of (strand, first record), the counts scanned, the item numbers scattered into
+// bucket order, and every bucket cut into UNITS of at most r items of equal key and size; k_se_verify_shared then
+// streams a unit's records once and evaluates all its reads on them.  Every item still gets its own RegionSummary in
+// its own row of HeavyStage::sums.  Reads of up to 128 bases whose seeds end inside the key (no tail characters).
+// ---------------------------------------------------------------------------
+template <int NW>
+constexpr bool share_nw() { return NW <= 8 && !(kPat != 3 && long_seed_nw<NW>()); }
+constexpr int kShareR = 4;  // items per unit (measured: 2 and 8 were slower)
+constexpr uint32_t kShareRounds = 8 * kPat;  // (chunk, round) pairs of the staged heavy pass
+struct SeShare {
+  uint32_t* count;   // [kGroupBuckets] items per bucket; zero outside these launches
+  uint32_t* cursor;  // [kGroupBuckets] first place of a bucket in `order`; after the scatter, its end
+  uint32_t* order;   // [cap] item numbers (the dense verifier's: giants first) in bucket order, every slice of 64 regrouped
+  uint2* units;      // [cap] units of more than kBigFirst candidates from the front, the others from the back:
+                     // {first place in `order`, items}; a unit of ONE item holds the item's number itself
+  uint32_t* ctl;     // this (chunk, round): [0] units from the front, [1] from the back, [2] the verifier's cursor
+  unsigned long long* recs;  // this (chunk, round): [0] records of all items (sum of size), [1] records of all units
+  uint32_t cap;      // items that are grouped; those behind (a smaller array: test hook) are units of one, in no list
+  uint32_t r;        // items per unit at most
+};
+__device__ __forceinline__ void share_counts(const HeavyStage& hs, uint32_t& n_big, uint32_t& n_all) {
+  const uint32_t g = hs.ctl[5], d = hs.ctl[0];
+  n_big = g < hs.hcap / 8 ? g : hs.hcap / 8;
+  n_all = n_big + (d < 2 * hs.hcap ? d : 2 * hs.hcap);
+}
+template <int NW>
+__device__ __forceinline__ const uint4* share_item(const HeavyStage& hs, uint32_t i, uint32_t n_big) {
+  constexpr uint32_t Q = item_quads<NW>();
+  return i < n_big ? hs.giants + (uint64_t)Q * i : hs.items + (uint64_t)Q * (i - n_big);
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// SCATTER = false: items per bucket; true: the item numbers into bucket order (the cursors come from k_se_share_scan)
+template <int NW, bool SCATTER>
+__global__ __launch_bounds__(kBlock) void k_se_share_bin(HeavyStage hs, SeShare sh) {
+  uint32_t n_big, n_all;
+  share_counts(hs, n_big, n_all);
+  const uint32_t n_grp = n_all < sh.cap ? n_all : sh.cap;
+  unsigned long long beyond = 0;  // records of the items behind the grouped ones
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (SCATTER ? n_grp : n_all); i += gridDim.x * blockDim.x) {
+    const uint4 h = load_global(share_item<NW>(hs, i, n_big));
+    if (i < n_grp) {
+      const uint32_t bk = group_bucket(group_key(h.x, h.w));
+      if constexpr (SCATTER) {
+        const uint32_t at = atomicAdd(&sh.cursor[bk], 1u);
+        if (at < sh.cap) sh.order[at] = i;
+      } else {
+        atomicAdd(&sh.count[bk], 1u);
+      }
+    } else {
+      beyond += h.z;
+    }
+  }
+  if constexpr (!SCATTER) {
+    if (n_all > n_grp) {  // (uniform)
+      beyond = wave_sum_u64(beyond);
+      if ((threadIdx.x & 63) == 0 && beyond) {
+        atomicAdd(&sh.recs[0], beyond);
+        atomicAdd(&sh.recs[1], beyond);
+      }
+    }
+  }
+}
+
+// exclusive scan of the bucket counts into the cursors: one block, every thread a run of buckets
+constexpr uint32_t kShareScanThreads = 1024;
+__global__ __launch_bounds__(kShareScanThreads) void k_se_share_scan(SeShare sh) {
+  constexpr uint32_t per = kGroupBuckets / kShareScanThreads;
+  __shared__ uint32_t part[kShareScanThreads];
+  const uint32_t t = threadIdx.x;
+  uint32_t s = 0;
+  for (uint32_t k = 0; k < per; ++k) s += sh.count[t * per + k];
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t off = 1; off < kShareScanThreads; off <<= 1) {
+    const uint32_t v = t >= off ? part[t - off] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - s;
+  for (uint32_t k = 0; k < per; ++k) {  // (the counts are left zero for the next round)
+    sh.cursor[t * per + k] = run;
+    run += sh.count[t * per + k];
+    sh.count[t * per + k] = 0u;
+  }
+}
+
+// One wavefront per slice of 64 places of `order` (group_core.h; equal keys lie in one bucket, so next to each other
+// but for the slice borders): lane t holds the slice's t-th item; the lanes equal to the first lane not yet placed are
+// found by a ballot and placed behind what has been placed.
+template <int NW>
+__global__ __launch_bounds__(kBlock) void k_se_share_cut(HeavyStage hs, SeShare sh) {
+  uint32_t n_big, n_all;
+  share_counts(hs, n_big, n_all);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t r = sh.r ? sh.r : 1u;
+  unsigned long long rec_items = 0, rec_units = 0;
+  uint32_t rode = 0;
+  const uint32_t end = n_all < sh.cap ? n_all : sh.cap;
+  for (uint32_t s = wave * kGroupSlice; s < end; s += n_waves * kGroupSlice) {
+    const uint32_t p = s + lane;
+    const bool valid = p < end;
+    uint32_t item = sh.order[valid ? p : s];
+    item = item < n_all ? item : 0u;
+    const uint4* it = share_item<NW>(hs, item, n_big);
+    const uint4 h0 = load_global(it), h1 = load_global(it + 1);
+    const uint64_t key = group_key(h0.x, h0.w);
+    const uint32_t size = h0.z, tail = h1.z;
+    unsigned long long rem = __ballot(valid);
+    uint32_t placed = 0;
+    GroupPlace mine = {0u, 0u, 1u, true};
+    while (rem) {
+      const int ld = (int)__ffsll((long long)rem) - 1;
+      const uint64_t lkey = group_key(bcast(h0.x, ld), bcast(h0.w, ld));
+      const bool join = (int)lane == ld || group_joins(key, size, tail, lkey, bcast(size, ld), bcast(tail, ld));
+      const unsigned long long m = __ballot(join) & rem;
+      if ((m >> lane) & 1ull) mine = group_place(m, lane, placed, r);
+      placed += (uint32_t)__popcll(m);
+      rem &= ~m;
+    }
+    if (valid) sh.order[s + mine.pos] = item;
+    const bool leads = valid && mine.leads, big = size > kBigFirst;
+    const unsigned long long mb = __ballot(leads && big), mr = __ballot(leads && !big);
+    uint32_t base_b = 0, base_r = 0;
+    if (lane == 0) {
+      if (mb) base_b = atomicAdd(&sh.ctl[0], (uint32_t)__popcll(mb));
+      if (mr) base_r = atomicAdd(&sh.ctl[1], (uint32_t)__popcll(mr));
+    }
+    base_b = bcast(base_b, 0);
+    base_r = bcast(base_r, 0);
+    if (leads) {
+      const unsigned long long below = (1ull << lane) - 1ull;
+      const uint32_t k = big ? base_b + (uint32_t)__popcll(mb & below) : base_r + (uint32_t)__popcll(mr & below);
+      if (k < sh.cap) sh.units[big ? k : sh.cap - 1u - k] = make_uint2(mine.unit_n == 1u ? item : s + mine.unit_first, mine.unit_n);
+    }
+    rec_items += valid ? size : 0u;
+    rec_units += leads ? size : 0u;
+    rode += (valid && !mine.leads) ? 1u : 0u;
+  }
+  rec_items = wave_sum_u64(rec_items);
+  rec_units = wave_sum_u64(rec_units);
+  rode = wave_sum_u32(rode);
+  if (lane == 0) {
+    if (rec_items) atomicAdd(&sh.recs[0], rec_items);
+    if (rec_units) atomicAdd(&sh.recs[1], rec_units);
+    if (rode) atomicAdd(&hs.ctl[7], rode);
+  }
+}
+
+// The units of a (chunk, round), one per wavefront: the region's records streamed once (item_stream's two record
+// buffers, every step the same loads), every step evaluated for the unit's reads.  What depends on the record alone --
+// the edge bit, the chromosome bounds, the words -- is done once per step; a read brings its seed shift, length, words
+// and masks, wave-uniform, read out of the lanes that loaded its header (lane 8 r + q: quad q of the unit's r-th item).
+// Units in the numbering of the launch: the large ones (dealt round robin, as item_stream deals), the others, then
+// one per item behind the grouped ones.
+template <int NW, int R>
+__global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
+    IndexView iv, uint32_t strand_base, unsigned long long* __restrict__ stats, HeavyStage hs, SeShare sh, uint32_t b,
+    uint32_t* __restrict__ err) {
+  static_assert(share_nw<NW>() && item_quads<NW>() <= 8 && R >= 1 && R <= 8, "a unit's headers are fetched by one wavefront load");
+  constexpr uint32_t Q = item_quads<NW>();
+  {
+    ItemQueue q;
+    q.items = hs.items; q.ctl = hs.ctl; q.cap = 2 * hs.hcap; q.ovf = err + 2;
+    if (blockIdx.x == 0 && threadIdx.x == 0) items_overflow_check(q);
+  }
+  uint32_t n_big, n_all;
+  share_counts(hs, n_big, n_all);
+  if (n_all == 0) return;
+  const uint32_t n_grp = n_all < sh.cap ? n_all : sh.cap;
+  uint32_t nbu = sh.ctl[0], nru = sh.ctl[1];
+  nbu = nbu < sh.cap ? nbu : sh.cap;
+  nru = nru < sh.cap - nbu ? nru : sh.cap - nbu;
+  const uint32_t nu = nbu + nru, n_units = nu + (n_all - n_grp);
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  __shared__ uint32_t s_edge[kEdgeWords];
+  const bool fits = iv.n_chrom <= kLdsChroms;
+  chrom_tab_stage(s_start, iv.start_index, chrom_tab_of(iv.n_chrom));
+  const bool has_edge = iv.edge_bits != nullptr;
+  if (has_edge)
+    for (uint32_t i = threadIdx.x; i < kEdgeWords; i += blockDim.x) s_edge[i] = iv.edge_bits[i];
+  __syncthreads();
+  const uint32_t n_chrom = iv.n_chrom, top_step = top_step_of(n_chrom);
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  uint32_t n_verified = 0;
+  if (wave < n_units) {
+  uint32_t* const cursor = &sh.ctl[2];
+  // the deal of item_stream: a first batch per wavefront dealt statically, the rest in batches from the cursor
+  const bool many = n_units >= 32 * n_waves;
+  uint32_t batch = many ? n_units / (4 * n_waves) : 2u;
+  batch = batch > kVerifyBatchMax ? kVerifyBatchMax : batch;
+  const uint32_t first_batch = many ? batch : (uint32_t)((3ull * n_units + 4ull * n_waves - 1) / (4ull * n_waves));
+  const uint32_t dealt = n_waves * first_batch;
+  auto grab = [&]() {
+    uint32_t v = 0;
+    if (lane == 0) v = dealt + atomicAdd(cursor, batch);
+    return v;
+  };
+  uint32_t b0 = wave, t = 0, stride = n_waves, cur_batch = first_batch, nb_v = 0;
+  uint32_t deal = 0;  // bit 0: a batch has been asked for, bit 1: no unit is left
+  if (cur_batch == 1 && dealt < n_units) {
+    nb_v = grab();
+    deal = 1u;
+  }
+  auto advance = [&]() __attribute__((always_inline)) -> uint32_t {  // the unit after the last one handed out; 0xFFFFFFFF: none
+    if (deal & 2u) return 0xFFFFFFFFu;
+    uint32_t ni;
+    if (t + 1 < cur_batch) {
+      ++t;
+      ni = b0 + t * stride;
+    } else {
+      b0 = (deal & 1u) ? bcast(nb_v, 0) : 0xFFFFFFFFu;
+      deal = 0u;
+      t = 0;
+      ni = b0;
+      cur_batch = batch;
+      stride = 1;
+    }
+    if (ni >= n_units) {
+      deal = 2u;
+      return 0xFFFFFFFFu;
+    }
+    if (t + 1 == cur_batch && dealt < n_units) {
+      nb_v = grab();
+      deal = 1u;
+    }
+    return ni;
+  };
+  auto unit_entry = [&](uint32_t i) __attribute__((always_inline)) -> uint2 {  // {an item's number or the first place in `order`, items}
+    const bool on = i < nu;
+    const uint64_t at = !on ? 0ull : (i < nbu ? (uint64_t)i : (uint64_t)sh.cap - 1u - (i - nbu));
+    uint2 e = load_global(sh.units + at);
+    if (!on) e = make_uint2(i < n_units ? sh.cap + (i - nu) : 0u, i < n_units ? 1u : 0u);
+    e.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x);
+    e.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
+    e.y = e.y < (uint32_t)R ? e.y : (uint32_t)R;
+    return e;
+  };
+  const uint32_t rr = lane >> 3, qq = lane & 7u;
+  auto headers = [&](const uint2& e) __attribute__((always_inline)) -> uint4 {  // lane 8 r + q: quad q of the unit's r-th item
+    uint32_t item = e.x;
+    if (e.y > 1u) {  // (uniform)
+      const uint32_t p = e.x + (rr < e.y ? rr : 0u);
+      item = sh.order[p < sh.cap ? p : 0u];
+    }
+    item = item < n_all ? item : 0u;
+    return load_global(share_item<NW>(hs, item, n_big) + ((rr < e.y && qq < Q) ? qq : 0u));
+  };
+  auto chrom_bounds_of = [&](uint32_t pos, uint32_t& c_lo, uint32_t& c_hi) {
+    if (has_edge && !((s_edge[pos >> (kEdgeBlockShift + 5)] >> ((pos >> kEdgeBlockShift) & 31u)) & 1u)) {
+      c_lo = 0; c_hi = 0xFFFFFFFFu;
+      return;
+    }
+    if (fits) {
+      const uint32_t chr = chrom_id_steps(s_start, n_chrom, top_step, pos);
+      c_lo = s_start[chr]; c_hi = s_start[chr + 1];
+    } else {
+      walt::chrom_bounds(s_start, iv.start_index, chrom_tab_of(n_chrom), pos, c_lo, c_hi);
+    }
+  };
+  struct Buf { uint4 a, c, e; };
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  Buf bx, by;
+  bx.a = bx.c = bx.e = by.a = by.c = by.e = zero;
+  auto issue = [&](uint32_t fi, uint32_t r0, uint32_t sz, uint32_t base, Buf& y) {
+    fi = (uint32_t)__builtin_amdgcn_readfirstlane((int)fi);
+    r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r0);
+    sz = (uint32_t)__builtin_amdgcn_readfirstlane((int)sz);
+    const StrandView& sv = iv.s[strand_base + fi];
+    const uint32_t k = base + lane;
+    const uint64_t rec = (uint64_t)r0 + (k < sz ? k : sz - 1);
+    const uint4* rp = reinterpret_cast<const uint4*>(sv.win) + 2 * rec;
+    y.a = load_global(rp);
+    y.c = load_global(rp + 1);
+    if constexpr (NW > 7) y.e = load_global(reinterpret_cast<const uint4*>(sv.win2) + rec);
+  };
+  // the current unit, the one after it (entry and headers), and the entry of the one after that
+  uint2 ue = unit_entry(wave);
+  uint4 hv = headers(ue);
+  uint32_t i1 = advance();
+  uint2 ue1 = unit_entry(i1);
+  uint4 hv1 = headers(ue1);  // (no unit: item 0's first quad, unused)
+  uint32_t i2 = advance();
+  uint2 ue2 = unit_entry(i2);
+  LaneBest acc[R];
+  uint32_t strand = 0, size = 1, rec0 = 0, base = 0;
+  auto begin = [&]() {
+    strand = bcast(hv.x, 0) >> 31; size = bcast(hv.z, 0); rec0 = bcast(hv.w, 0);
+    size = size ? size : 1u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = {0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+    base = 0;
+  };
+  bool done = false;
+  auto step = [&](Buf& x, Buf& y) {
+    const bool last = base + 64 >= size;
+    const bool hn = i1 != 0xFFFFFFFFu;
+    uint32_t n_fi = strand, n_rec0 = rec0, n_size = size;
+    const uint32_t n_base = last ? 0u : base + 64;
+    if (last && hn) {
+      n_fi = bcast(hv1.x, 0) >> 31; n_size = bcast(hv1.z, 0); n_rec0 = bcast(hv1.w, 0);
+      n_size = n_size ? n_size : 1u;
+    }
+    issue(n_fi, n_rec0, n_size, n_base, y);
+    const uint32_t k = base + lane;
+    const uint32_t pos = x.a.x;
+    uint32_t c_lo, c_hi;
+    chrom_bounds_of(pos, c_lo, c_hi);
+    uint32_t wv[NW + 1];
+    const uint32_t first[11] = {x.a.y, x.a.z, x.a.w, x.c.x, x.c.y, x.c.z, x.c.w, NW > 7 ? x.e.x : 0u, NW > 7 ? x.e.y : 0u,
+                                NW > 7 ? x.e.z : 0u, NW > 7 ? x.e.w : 0u};
+#pragma unroll
+    for (int w = 0; w <= NW; ++w) wv[w] = first[w];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if ((uint32_t)r < ue.y) {  // (uniform)
+        const uint32_t len = bcast(hv.x, 8 * r + 1), seed_i = bcast(hv.y, 8 * r + 1);
+        uint32_t rd[NW], mk[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          const int a = 8 + w, c = 8 + NW + w;
+          const uint32_t va = (a & 3) == 0 ? hv.x : (a & 3) == 1 ? hv.y : (a & 3) == 2 ? hv.z : hv.w;
+          const uint32_t vc = (c & 3) == 0 ? hv.x : (c & 3) == 1 ? hv.y : (c & 3) == 2 ? hv.z : hv.w;
+          rd[w] = bcast(va, 8 * r + (a >> 2));
+          mk[w] = bcast(vc, 8 * r + (c >> 2));
+        }
+        const uint32_t g = pos - seed_i;
+        const bool ok = k < size && (pos - c_lo >= seed_i) && (g + len < c_hi);
+        const uint32_t m = count_mismatch_regs<NW>(wv, 2 * (kWinLead - seed_i), rd, mk);
+        n_verified += ok ? 1u : 0u;
+        lane_best_add(acc[r], k, ok ? g : 0u, ok ? m : 0xFFFFFFFFu);
+      }
+    }
+    if (last) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((uint32_t)r < ue.y) {  // (uniform) SummarySink::end for the unit's r-th item
+          const uint32_t id = bcast(hv.x, 8 * r), seed_i = bcast(hv.y, 8 * r + 1), tail = bcast(hv.z, 8 * r + 1);
+          uint4 res = lane_best_reduce(acc[r]);
+          if (tail && size > b) res = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);  // (every slot of these instances' regions belongs to it)
+          if (lane == 0) hs.sums[(uint64_t)((id >> 31) ? 1u + seed_i : 0u) * hs.hcap + (id & 0x7FFFFFFFu)] = res;
+        }
+      }
+      if (hn) {
+        ue = ue1; hv = hv1;
+        i1 = i2; ue1 = ue2;
+        hv1 = headers(ue1);
+        i2 = advance();
+        ue2 = unit_entry(i2);
+        begin();
+      } else {
+        done = true;
+      }
+    } else {
+      base += 64;
+    }
+  };
+  begin();
+  issue(strand, rec0, size, 0u, bx);
+  for (;;) {
+    step(bx, by);
+    if (done) break;
+    step(by, bx);
+    if (done) break;
+  }
+  }
+  flush_counters({0u, n_verified, 0u}, 0u, stats);
+}
+
 #ifndef WALT_LIT_OCC
 #define WALT_LIT_OCC 5  // wavefronts per SIMD the literal kernel's registers are capped for (measured: see DESIGN.md section 12b)
 #endif
@@ -1724,6 +2104,33 @@ static SeGeometry se_geometry(uint32_t n, int nw, const walt_options& opt) {
 }
 // what pass 1 hands to the staged rounds (SeCarry): kPat 16-byte words per read of the batch
 static uint64_t se_carry_bytes(uint32_t n) { return (uint64_t)kPat * se_stride(n) * 16; }
+// The grouping of the dense items (SeShare), behind the carry area.  Per state slot [bucket cursors][order][units] for
+// 2 x hcap + hcap / 8 items of the DEFAULT geometry (another geometry groups what fits: se_share_cap_for); then, at the
+// END of the workspace walt_se_workspace_bytes promises, a block of fixed size: [2 x bucket cursors] and, cleared by
+// every call, [2 x bucket counts][4 control words per (chunk, round)][2 x 64-bit record counters per (chunk, round)].
+constexpr uint64_t kShareCtlWords = 4 * kShareRounds;
+constexpr uint64_t kShareZeroBytes = 2ull * kGroupBuckets * 4 + kShareCtlWords * 4 + kShareRounds * 2 * 8;
+constexpr uint64_t kShareCursorBytes = 2ull * kGroupBuckets * 4;
+static uint64_t se_share_slot_bytes(uint64_t cap_items) { return align_up((cap_items & ~1ull) * 12, 16); }
+static uint64_t se_share_big_bytes(uint32_t n, int nw) {
+  if (nw > 8) return 0;
+  uint64_t most = 0;
+  for (int pipe = 0; pipe < 2; ++pipe) {
+    const SeGeometry g = se_geometry_for(n, nw, pipe != 0, 0);
+    const uint64_t v = (g.piped ? 2 : 1) * se_share_slot_bytes(2ull * g.hcap + g.hcap / 8);
+    most = v > most ? v : most;
+  }
+  return most;
+}
+static uint64_t se_share_bytes(uint32_t n, int nw) { return 32 + se_share_big_bytes(n, nw) + kShareCursorBytes + kShareZeroBytes; }
+// items a slot of `slot_bytes` bytes groups under geometry g (even; option se_share_cap: fewer)
+static uint32_t se_share_cap_for(const SeGeometry& g, uint64_t slot_bytes, long long hook) {
+  const uint64_t full = 2ull * g.hcap + g.hcap / 8;
+  uint64_t cap = slot_bytes / 12;
+  cap = (cap < full ? cap : full) & ~1ull;
+  if (hook > 0 && (uint64_t)hook < cap) cap = (uint64_t)hook;
+  return (uint32_t)cap;
+}
 
 constexpr unsigned kLiteralGrid = 2048;  // blocks of the deferred-read pass (grid-stride)
 
@@ -1748,11 +2155,25 @@ unsigned persistent_grid(const walt_index* idx) {
   return idx->opt.grid > 0 ? (unsigned)idx->opt.grid : (unsigned)idx->n_cu * 8u;
 }
 
+// where the grouping's arrays lie in the workspace (se_workspace)
+struct SeShareArea {
+  uint8_t* big = nullptr;     // the state slots' arrays
+  uint64_t big_bytes = 0;
+  uint32_t* zero = nullptr;   // the block a call clears (kShareZeroBytes); the two slots' bucket cursors lie in front of it
+};
+
+template <class K>
+static int occupancy_blocks(K kernel) {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, 0) != hipSuccess || nb < 1) nb = 4;
+  return nb;
+}
+
 template <int NW>
 static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t* codes2, const uint64_t* offsets, uint32_t* err,
                          uint32_t n, uint32_t strand_base, uint32_t max_mm, uint32_t b, BestMatch* out,
                          unsigned long long* stats, uint32_t* defer_count, uint32_t* defer_list, uint64_t stride,
-                         uint32_t* heavy_area, uint4* carry_area, hipStream_t stream) {
+                         uint32_t* heavy_area, uint4* carry_area, const SeShareArea& share_area, hipStream_t stream) {
   const walt_options& opt = idx->opt;
   const unsigned pg = persistent_grid(idx);
   const unsigned g1 = grid_for(n) < pg ? grid_for(n) : pg;
@@ -1827,6 +2248,15 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
     hs.hcap = hcap;
     hs.even = piped ? 1u : 0u;
     const uint64_t slot_words = geo.slot_bytes / 4;
+    // option se_verify_share: the dense items grouped by region (SeShare) -- 1: and verified a group at a time
+    // (k_se_verify_shared), 2: grouped and counted only, verified one by one as with 0 (measurement)
+    SeShare sh = {};
+    const uint64_t share_slot = (share_area.big_bytes / (geo.piped ? 2 : 1)) & ~15ull;
+    const uint32_t share_alloc = se_share_cap_for(geo, share_slot, 0);
+    sh.cap = se_share_cap_for(geo, share_slot, opt.se_share_cap);
+    int share_mode = (share_nw<NW>() && !diag && share_area.zero != nullptr && sh.cap > 0) ? opt.se_verify_share : 0;
+    // (se_share_r: another unit size for the count-only mode, tools/verify_share_bench.py; the verifier is built for kShareR)
+    sh.r = (share_mode == 2 && opt.se_share_r > 0) ? (uint32_t)opt.se_share_r : (uint32_t)kShareR;
     auto use_slot = [&](uint32_t k, uint32_t*& lists) {
       lists = heavy_area + kHeavyCtlWords + k * slot_words;  // [kPat][hcap]: what round k hands to round k + 1
       hs.st = reinterpret_cast<uint4*>(lists + (uint64_t)kPat * hcap);
@@ -1834,6 +2264,12 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
       hs.sums = hs.rdq + (uint64_t)rd_quads<NW>() * hcap;
       hs.items = hs.sums + (uint64_t)(kPat + 1) * hcap;  // 2 * hcap items of item_quads<NW>() quads
       hs.giants = hs.items + (uint64_t)2 * hcap * item_quads<NW>();
+      if (share_mode) {
+        sh.count = share_area.zero + k * kGroupBuckets;
+        sh.cursor = share_area.zero - (2 - k) * kGroupBuckets;
+        sh.order = reinterpret_cast<uint32_t*>(share_area.big + k * share_slot);
+        sh.units = reinterpret_cast<uint2*>(sh.order + share_alloc);
+      }
     };
     // long seeds: key-equal ranges of more slots than this go to the verifier unnarrowed (option se_defer_min: 0 = never
     // (A/B: every range narrowed by lit_region in the stage kernel); measured 4 / 8 / 16 -> 32.5 / 33.2 / 34.2 ms per 25 M 150-base reads)
@@ -1852,6 +2288,14 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_se_verify<NW, false>, kBlock, 0) != hipSuccess || nb < 1) nb = 2;
       return nb;
     }();
+    auto share_blocks = []() -> int {  // blocks per compute unit of k_se_verify_shared<NW, kShareR>
+      if constexpr (share_nw<NW>()) {
+        static const int nb = occupancy_blocks(k_se_verify_shared<NW, kShareR>);
+        return nb;
+      } else {
+        return 4;
+      }
+    };
     const unsigned vg_dense = (unsigned)vb_dense * (unsigned)idx->n_cu, vg_gather = (unsigned)vb_gather * (unsigned)idx->n_cu;
     // The reads with a truly dangerous probe.  Default: the strand-major kernel (k_map_se_literal, the reference's search
     // inferred: core.h lit_region_inferred) on a low-priority side stream: after the last look-up round of the first chunk
@@ -1954,8 +2398,26 @@ static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t*
         }
         if constexpr (NW <= 10 && long_seed_nw<NW>())
           hipLaunchKernelGGL((k_se_tail_narrow<NW>), dim3(pg), dim3(kBlock), 0, cs, view, strand_base, hs, b);
+        bool shared_done = false;
+        if constexpr (share_nw<NW>()) {
+          if (share_mode && !lit && c_side < 8u) {
+            sh.ctl = share_area.zero + 2 * kGroupBuckets + 4 * (c_side * kPat + round);
+            sh.recs = reinterpret_cast<unsigned long long*>(share_area.zero + 2 * kGroupBuckets + kShareCtlWords) + 2 * (c_side * kPat + round);
+            const unsigned gs = (unsigned)idx->n_cu;  // small launches: about one block per compute unit
+            hipLaunchKernelGGL((k_se_share_bin<NW, false>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+            hipLaunchKernelGGL(k_se_share_scan, dim3(1), dim3(kShareScanThreads), 0, cs, sh);
+            hipLaunchKernelGGL((k_se_share_bin<NW, true>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+            hipLaunchKernelGGL((k_se_share_cut<NW>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+            if (share_mode == 1) {
+              const unsigned vgs = (opt.se_verify_blocks > 0 ? (unsigned)opt.se_verify_blocks : (unsigned)share_blocks()) * (unsigned)idx->n_cu;
+              hipLaunchKernelGGL((k_se_verify_shared<NW, kShareR>), dim3(vgs), dim3(kBlock), 0, cs, view, strand_base, stats, hs, sh, b, err);
+              shared_done = true;
+            }
+          }
+        }
         if constexpr (NW <= 10) {
-          hipLaunchKernelGGL((k_se_verify<NW, true>), dim3(vgd), dim3(kBlock), 0, cs, view, strand_base, stats, hs, b, err);
+          if (!shared_done)
+            hipLaunchKernelGGL((k_se_verify<NW, true>), dim3(vgd), dim3(kBlock), 0, cs, view, strand_base, stats, hs, b, err);
         }
         hipLaunchKernelGGL((k_se_verify<NW, false>), dim3(vg_gather), dim3(kBlock), 0, cs, view, strand_base, stats, hs, b, err);
         if (marks) mark(lit ? 3 : 2);
@@ -2061,6 +2523,7 @@ struct SeWorkspace {
   uint32_t* codes2;             // deferred list, its sorted copy, heavy list, then the dense reads
   uint32_t* heavy_area;         // state of the staged heavy pass behind the dense reads, 16-byte aligned
   uint4* carry_area;
+  SeShareArea share;            // the grouping of the dense items (se_share_bytes)
   uint64_t stride;
   uint64_t end;                 // first byte behind the layout (walt_se_workspace_bytes bytes from the start at most)
 };
@@ -2075,7 +2538,11 @@ static SeWorkspace se_workspace(void* d_workspace, uint32_t n, uint32_t max_read
   w.heavy_area = reinterpret_cast<uint32_t*>(
       align_up(reinterpret_cast<uint64_t>(w.codes2 + codes2_words((uint64_t)n * max_read_len)), 16));
   w.carry_area = reinterpret_cast<uint4*>(align_up(reinterpret_cast<uint64_t>(w.heavy_area) + se_heavy_bytes(n, nw), 16));
-  w.end = reinterpret_cast<uint64_t>(w.carry_area) + se_carry_bytes(n);
+  w.share.big = reinterpret_cast<uint8_t*>(align_up(reinterpret_cast<uint64_t>(w.carry_area) + se_carry_bytes(n), 16));
+  w.share.big_bytes = se_share_big_bytes(n, nw);
+  // the cleared block ends with the workspace's promised size: its counters are read at a fixed distance from there
+  w.end = (reinterpret_cast<uint64_t>(d_workspace) + walt_se_workspace_bytes(n, max_read_len)) & ~15ull;
+  w.share.zero = reinterpret_cast<uint32_t*>(w.end - kShareZeroBytes);
   return w;
 }
 
@@ -2085,7 +2552,7 @@ static int se_map_pass(walt_index* idx, const IndexView& view, const SeWorkspace
                        int nw, uint32_t sb, uint32_t max_mm, uint32_t b, BestMatch* out, hipStream_t stream) {
   return dispatch_nw(nw, [&](auto NW) {
     return launch_map_se<decltype(NW)::value>(idx, view, w.codes2, offsets, w.err, n, sb, max_mm, b, out, w.shards, w.defer_count,
-                                              w.defer_list, w.stride, w.heavy_area, w.carry_area, stream);
+                                              w.defer_list, w.stride, w.heavy_area, w.carry_area, w.share, stream);
   });
 }
 
@@ -2117,6 +2584,7 @@ static int se_begin(walt_index* idx, bool rp, bool locked, const void* d_bases, 
   c.w = se_workspace(d_workspace, n, max_read_len, c.nw);
   WALT_HIP(hipMemsetAsync(c.w.err, 0, 64 * sizeof(uint32_t) + kStatShardBytes, stream));
   WALT_HIP(hipMemsetAsync(c.w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  if (idx->opt.se_verify_share) WALT_HIP(hipMemsetAsync(c.w.share.zero, 0, kShareZeroBytes, stream));
   c.offsets = reinterpret_cast<const uint64_t*>(d_offsets);
   if (idx->profile) WALT_HIP(hipEventRecord(idx->ev[0], stream));
   c.view = idx->view;  // this launch's copy: the limits lane_load_read enforces
@@ -2226,6 +2694,7 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
   // staged pass's control words.  err[0..2] stay: they report what either pass met.
   WALT_HIP_FORKED(hipMemsetAsync(w.err + 3, 0, 61 * sizeof(uint32_t), stream));
   WALT_HIP_FORKED(hipMemsetAsync(w.heavy_area, 0, kHeavyCtlWords * sizeof(uint32_t), stream));
+  if (idx->opt.se_verify_share) WALT_HIP_FORKED(hipMemsetAsync(w.share.zero, 0, kShareZeroBytes, stream));
   // G->A pass into the workspace's record array; it starts from (0, 0, '+', max_mm) like the first, never from the
   // first pass's result (a cap taken from it would stop the seed loop before equally good hits are found)
   rc = se_map_pass(idx, c.view, w, c.offsets, n, c.nw, 2u, max_mm, b, reinterpret_cast<BestMatch*>(ga), stream);
@@ -2338,7 +2807,8 @@ size_t walt_se_workspace_bytes(uint32_t n, uint32_t max_read_len) {
   int nw = nw_for_len(max_read_len);
   if (!nw) nw = 64;
   return 64 * sizeof(uint32_t) + kStatShardBytes + 3 * se_stride(n) * sizeof(uint32_t) +
-         codes2_words((uint64_t)n * max_read_len) * sizeof(uint32_t) + 16 + se_heavy_bytes(n, nw) + 16 + se_carry_bytes(n);
+         codes2_words((uint64_t)n * max_read_len) * sizeof(uint32_t) + 16 + se_heavy_bytes(n, nw) + 16 + se_carry_bytes(n) +
+         se_share_bytes(n, nw);
 }
 
 int walt_map_se_batch_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,

@@ -425,6 +425,49 @@ int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_m
 int walt_pileup_extract_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_sites, uint64_t cap,
                                void* d_n_sites, void* d_offref, void* stream);
 
+/* ---- methylation levels: the genome-wide summary of a pile-up, per context and over CpG pairs -------------------
+ * The reference has no such mode (MethPipe users run symmetric-cpgs and levels over the counts file and the FASTA,
+ * Bismark users read the report); the contract is defined here.  One pass over the counters and the '+' reference R
+ * of the pile-up's index gives, over the forward positions [pos_lo, pos_hi), five rows of integers.
+ *
+ * Rows 0..3 (CpG, CHG, CHH, unknown).  A site is a position f of the range whose R[f] is C or G, classified exactly as
+ * the extraction classifies it; uncovered sites count in `sites`.  covered, meth, unmeth and max_depth equal what the
+ * records of walt_pileup_extract over the same range add up to, and offref equals the extraction's.
+ *
+ * Row 4 (CpG pairs, both strands merged).  f with R[f] == C, R[f + 1] == G and f + 1 in f's chromosome; its counts are
+ * meth[f] + meth[f + 1] and unmeth[f] + unmeth[f + 1] (up to 2^33 - 2 each: the << 30 of level_sum keeps the numerator
+ * below 2^63).  A pair belongs to the range that holds f: f + 1 may lie at or beyond pos_hi and is still read.  A C on a
+ * chromosome's last base in front of a G on the next one's first is no pair (that C is `unknown`).
+ *
+ * Every field except max_depth is additive over a partition of a range, max_depth is the maximum; all are integers and
+ * all folds commutative, so the result does not depend on the launch shape (the test hook pile_extract_blocks).
+ *
+ * Errors and ordering as walt_pileup_extract[_device]: WALT_EINVAL for a null pile-up, a null out, pos_lo > pos_hi or
+ * pos_hi > genome_len, and d_out not 8-byte aligned; the host forms wait for all work on the device first; the device
+ * form is asynchronous on `stream` (d_out: 656 bytes of HBM).  A summary counts as an extraction under "one at a time
+ * per pile-up": its accumulator lives in free words of the extraction's table, and walt_pileup_device_bytes is as before.
+ *
+ * Raw counters.  walt_pileup_read copies the counters of [pos_lo, pos_hi) to two host arrays (either may be NULL);
+ * walt_pileup_add adds two host arrays into them, wrapping as the counters do (either may be NULL: zeros; an empty
+ * range is a no-op).  Maxima and covered sites are not additive across pile-ups: the counters of several devices are
+ * folded with these two before one summary is taken. */
+typedef struct {            /* 128 bytes */
+  uint64_t sites;           /* sites of the class in the range, covered or not */
+  uint64_t covered;         /* of those, with meth + unmeth > 0 */
+  uint64_t meth, unmeth;    /* calls on them */
+  uint64_t max_depth;       /* largest meth + unmeth of one site */
+  uint64_t level_sum;       /* sum over covered sites of floor((meth << 30) / (meth + unmeth)) */
+  uint64_t hist[10];        /* covered sites by min(9, 10 * meth / (meth + unmeth)), integer division */
+} walt_level_row;
+typedef struct {
+  walt_level_row row[5];    /* 0 CpG, 1 CHG, 2 CHH, 3 unknown (the contexts of walt_meth_site), 4 CpG pairs */
+  uint64_t offref[2];       /* as walt_pileup_extract returns them */
+} walt_levels;              /* 656 bytes */
+int walt_pileup_levels(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_levels* out);
+int walt_pileup_levels_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_out /*8-byte aligned*/, void* stream);
+int walt_pileup_read(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint32_t* meth, uint32_t* unmeth);
+int walt_pileup_add(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, const uint32_t* meth, const uint32_t* unmeth);
+
 /* ---- duplicates: PCR duplicates marked from the mapped records, and kept out of the methylation counts ---------
  * The reference has no such mode (its users sort the mapped records and run a second program, MethPipe's
  * duplicate-remover, before they count; Bismark users run deduplicate_bismark); the contract is defined here.  It needs

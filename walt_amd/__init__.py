@@ -85,6 +85,13 @@ METH_CONTEXTS = ("CpG", "CHG", "CHH", "unknown")
 meth_site_dtype = np.dtype([("pos", "<u4"), ("meth", "<u4"), ("unmeth", "<u4"), ("strand", "u1"), ("context", "u1"),
                             ("reserved", "<u2")])
 assert meth_site_dtype.itemsize == 16
+# walt_levels: the genome-wide summary of a pile-up (include/walt_amd.h, "methylation levels"); rows CpG, CHG, CHH,
+# unknown (METH_CONTEXTS) and CpG pairs
+level_row_dtype = np.dtype([("sites", "<u8"), ("covered", "<u8"), ("meth", "<u8"), ("unmeth", "<u8"), ("max_depth", "<u8"),
+                            ("level_sum", "<u8"), ("hist", "<u8", (10,))])
+levels_dtype = np.dtype([("row", level_row_dtype, (5,)), ("offref", "<u8", (2,))])
+LEVEL_ROWS = METH_CONTEXTS + ("CpG_symmetric",)
+assert level_row_dtype.itemsize == 128 and levels_dtype.itemsize == 656
 # walt_nonconv_tally / walt_nonconv_rule (include/walt_amd.h, "non-converted reads")
 nonconv_tally_dtype = np.dtype([("meth", "<u2"), ("total", "<u2"), ("run", "<u2"), ("reserved", "<u2")])
 nonconv_rule_dtype = np.dtype([("min_meth", "<u4"), ("min_run", "<u4"), ("min_percent", "<u4"), ("min_total", "<u4")])
@@ -218,6 +225,10 @@ def lib(pattern=None):
     L.walt_meth_pileup_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp]
     L.walt_pileup_extract.argtypes = [vp, u32, u32, vp, u64, c.POINTER(u64), vp]
     L.walt_pileup_extract_device.argtypes = [vp, u32, u32, vp, u64, vp, vp, vp]
+    L.walt_pileup_levels.argtypes = [vp, u32, u32, vp]
+    L.walt_pileup_levels_device.argtypes = [vp, u32, u32, vp, vp]
+    L.walt_pileup_read.argtypes = [vp, u32, u32, vp, vp]
+    L.walt_pileup_add.argtypes = [vp, u32, u32, vp, vp]
     L.walt_dedup_create.argtypes = [ci, u64, c.POINTER(vp)]
     L.walt_dedup_destroy.argtypes = [vp]
     L.walt_dedup_destroy.restype = None
@@ -962,6 +973,36 @@ class Pileup:
         """Device-pointer form (walt_pileup_extract_device); asynchronous."""
         self._index._ck(self._L.walt_pileup_extract_device(self._h, int(pos_lo), int(pos_hi), d_sites, int(cap), d_n_sites,
                                                            d_offref, stream))
+
+    def levels(self, pos_lo=0, pos_hi=None):
+        """The summary of the forward positions [pos_lo, pos_hi) (walt_pileup_levels): one levels_dtype record."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        out = np.zeros(1, dtype=levels_dtype)
+        self._index._ck(self._L.walt_pileup_levels(self._h, int(pos_lo), int(pos_hi), _ptr(out)))
+        return out[0]
+
+    def levels_device(self, pos_lo, pos_hi, d_out, stream=0):
+        """Device-pointer form (walt_pileup_levels_device): 656 bytes at d_out; asynchronous."""
+        self._index._ck(self._L.walt_pileup_levels_device(self._h, int(pos_lo), int(pos_hi), d_out, stream))
+
+    def read(self, pos_lo=0, pos_hi=None):
+        """(meth, unmeth) uint32 arrays: the raw counters of [pos_lo, pos_hi) (walt_pileup_read)."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        n = max(0, int(pos_hi) - int(pos_lo))
+        meth, unmeth = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._index._ck(self._L.walt_pileup_read(self._h, int(pos_lo), int(pos_hi), _ptr(meth), _ptr(unmeth)))
+        return meth, unmeth
+
+    def add(self, pos_lo, pos_hi, meth=None, unmeth=None):
+        """Adds two uint32 arrays of pos_hi - pos_lo counts into the counters (walt_pileup_add); None: zeros."""
+        arrs = []
+        for a in (meth, unmeth):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.uint32)
+                if a.size != int(pos_hi) - int(pos_lo):
+                    raise ValueError("Pileup.add wants pos_hi - pos_lo counts per array")
+            arrs.append(a)
+        self._index._ck(self._L.walt_pileup_add(self._h, int(pos_lo), int(pos_hi), *[None if a is None else _ptr(a) for a in arrs]))
 
     def clear(self):
         self._index._ck(self._L.walt_pileup_clear(self._h))

@@ -470,6 +470,43 @@ inline void put_mbias_block(Sink& out, const uint64_t* count) {
     }
 }
 
+// ---------------------------------------------------------------- <out>.levels (bin/walt -ML)
+// One read file's block (include/walt_amd.h, "methylation levels"): a header line and six lines, tab-separated:
+//   context sites covered meth unmeth max_depth mean_depth covered_fraction mean_meth weighted_meth h0 .. h9
+// for cytosines (rows 0..3 folded: sums, the maximum for max_depth), CpG, CHG, CHH, unknown and CpG_symmetric (row 4).
+// mean_depth = (meth + unmeth) / sites, covered_fraction = covered / sites, mean_meth = level_sum / (covered * 2^30),
+// weighted_meth = meth / (meth + unmeth); each %.6f, or NA on a zero denominator.
+inline void put_levels_block(Sink& out, const walt_levels& lv) {
+  static const char* name[6] = {"cytosines", "CpG", "CHG", "CHH", "unknown", "CpG_symmetric"};
+  walt_level_row all;
+  memset(&all, 0, sizeof all);
+  for (int r = 0; r < 4; ++r) {
+    const walt_level_row& x = lv.row[r];
+    all.sites += x.sites; all.covered += x.covered; all.meth += x.meth; all.unmeth += x.unmeth; all.level_sum += x.level_sum;
+    all.max_depth = std::max(all.max_depth, x.max_depth);
+    for (int b = 0; b < 10; ++b) all.hist[b] += x.hist[b];
+  }
+  out.lit("context\tsites\tcovered\tmeth\tunmeth\tmax_depth\tmean_depth\tcovered_fraction\tmean_meth\tweighted_meth"
+          "\th0\th1\th2\th3\th4\th5\th6\th7\th8\th9\n");
+  char num[192];
+  auto ratio = [&](double a, double b) {
+    if (b != 0.0) snprintf(num, sizeof num, "\t%.6f", a / b); else snprintf(num, sizeof num, "\tNA");
+    out.lit(num);
+  };
+  for (int k = 0; k < 6; ++k) {
+    const walt_level_row& x = k == 0 ? all : lv.row[k - 1];
+    snprintf(num, sizeof num, "%s\t%llu\t%llu\t%llu\t%llu\t%llu", name[k], (unsigned long long)x.sites, (unsigned long long)x.covered,
+             (unsigned long long)x.meth, (unsigned long long)x.unmeth, (unsigned long long)x.max_depth);
+    out.lit(num);
+    ratio((double)(x.meth + x.unmeth), (double)x.sites);
+    ratio((double)x.covered, (double)x.sites);
+    ratio((double)x.level_sum, (double)x.covered * 1073741824.0);
+    ratio((double)x.meth, (double)(x.meth + x.unmeth));
+    for (int b = 0; b < 10; ++b) { snprintf(num, sizeof num, "\t%llu", (unsigned long long)x.hist[b]); out.lit(num); }
+    out.ch('\n');
+  }
+}
+
 // ---------------------------------------------------------------- ignored read ends (bin/walt -I5 -I3 -I5R2 -I3R2)
 // The value of one of the four options (include/walt_amd.h, "ignored read ends"): a decimal integer from 0 to 1024
 // (no read is longer), nothing in front of or behind the digits.

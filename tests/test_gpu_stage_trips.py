@@ -220,8 +220,9 @@ def batch_of(p, n_heavy):
     return np.sort(np.concatenate([hv[:n_heavy], lt[:n_light]]))
 
 
-def device_heavy_count(wa, idx, bases, offsets, ag, max_mm):
-    """reads pass 1 handed to the heavy pass in one call of the device form"""
+def device_control_words(wa, idx, bases, offsets, ag, max_mm):
+    """the 64 control words at the start of the workspace after one call of the device form: [56] the reads pass 1
+    handed to the heavy pass, [32] the length of the deferred list at the end of the call"""
     import torch
     dev = torch.device("cuda:0")
     n = offsets.size - 1
@@ -235,7 +236,12 @@ def device_heavy_count(wa, idx, bases, offsets, ag, max_mm):
     idx.map_se_batch_device(d_bases.data_ptr(), d_off.data_ptr(), n, max_len, d_out.data_ptr(), d_stats.data_ptr(), d_ws.data_ptr(),
                             d_ws.numel(), stream=stream, ag_wildcard=ag, max_mismatches=max_mm, b=5000)
     torch.cuda.synchronize()
-    return int(d_ws[:64 * 4].view(torch.int32).cpu().numpy()[56])
+    return d_ws[:64 * 4].view(torch.int32).cpu().numpy()
+
+
+def device_heavy_count(wa, idx, bases, offsets, ag, max_mm):
+    """reads pass 1 handed to the heavy pass in one call of the device form"""
+    return int(device_control_words(wa, idx, bases, offsets, ag, max_mm)[56])
 
 
 @pytest.mark.parametrize("ag", [False, True], ids=["CT", "GA"])
@@ -277,6 +283,75 @@ def test_stage_records_equal_oracle_under_every_schedule(wa, ladder, index_optio
         if first is None:
             first = st
         assert st == first, "statistics differ under %s: %s, default schedule %s" % (sched, st, first)
+
+
+DEFER_SCHEDULES = [{}, {"se_heavy_chunk": 64}, {"se_pipe": 0, "se_heavy_chunk": 64}, {"se_lit_side": 0, "se_heavy_chunk": 64},
+                   {"se_carry": 0, "se_heavy_chunk": 64}]
+
+
+@pytest.fixture(scope="module")
+def crowded(wa, scratch):
+    """The "crowded" genome of tests/test_gpu_parity.py::test_gpu_pe_small_heaps_with_overflow_list -- 300 short
+    sequences cut from one 600-base unit plus the unit three times over: chromosome ends everywhere make probes
+    dangerous, the repeats make slots long -- and 512 converted 100-base reads of it per conversion, with the oracle's
+    records."""
+    rng = random.Random(4242)
+    unit = _rand(rng, 600)
+    seqs = []
+    for i in range(300):
+        a = rng.randrange(0, 300)
+        L = rng.choice([60, 90, 131, 150, 200, 260])
+        s = list(unit[a:a + L])
+        for _ in range(rng.randrange(0, 3)):
+            s[rng.randrange(len(s))] = rng.choice("ACGT")
+        seqs.append(("u%d" % i, "".join(s)))
+    seqs.append(("long", unit * 3))
+    fa = os.path.join(scratch, "crowded_se.fa")
+    with open(fa, "w") as f:
+        for nm, s in seqs:
+            f.write(">%s\n%s\n" % (nm, s))
+    path = os.path.join(scratch, "crowded_se.dbindex")
+    wa.makedb(fa, path, threads=4)
+    db = refio.DbIndex(path)
+    idx = wa.Index.open(path, device=0, strands=wa.STRANDS_ALL)
+    big = unit * 3
+    sets = {}
+    for ag in (False, True):
+        reads = []
+        for _ in range(512):
+            a = rng.randrange(0, len(big) - 100)
+            frag = big[a:a + 100]
+            if rng.random() < 0.5:
+                frag = refio.revcomp(frag)
+            reads.append(substitute(rng, convert(rng, frag, ag), rng.choice([0, 1, 2])))
+        want, work = refio.oracle_se(db, reads, ag=ag, max_mm=6, b=5000, threads=8)
+        sets[ag] = {"reads": reads, "want": want, "too_short": int(work["too_short"])}
+    yield {"idx": idx, "sets": sets}
+    idx.close()
+
+
+@pytest.mark.parametrize("ag", [False, True], ids=["CT", "GA"])
+def test_side_launch_and_later_chunks_on_a_genome_that_defers(wa, crowded, index_options, ag):
+    """Nothing that appends to the deferred list may run while the side launch's share of it is fixed (map_se.hip
+    se_fork_literal): 512 reads that are heavy AND deferred, in eight chunks of the heavy list (se_heavy_chunk = 64 is
+    applied up to 512 reads: four chunks per half when piped, eight in a row with se_pipe = 0), so that chunks behind
+    the first pair still append when the snapshot is taken.  Records equal the oracle's under every schedule.
+    Observed on the device (one call of the device form, default schedule): C->T reads 480 heavy and 393 deferred of 512,
+    G->A reads 470 heavy and 393 deferred."""
+    idx, p = crowded["idx"], crowded["sets"][ag]
+    bases, offsets = wa.pack_reads(p["reads"])
+    ctl = device_control_words(wa, idx, bases, offsets, ag, 6)
+    heavy, deferred = int(ctl[56]), int(ctl[32])
+    print("crowded %s: heavy %d, deferred %d of %d reads" % ("GA" if ag else "CT", heavy, deferred, len(p["reads"])))
+    assert heavy >= 64, "pass 1 handed %d reads to the heavy pass: not every chunk holds reads" % heavy
+    assert deferred >= 64, "%d reads were deferred" % deferred
+    names = ("se_heavy_chunk", "se_pipe", "se_lit_side", "se_carry")
+    defaults = {name: idx.get_option(name) for name in names}
+    for sched in DEFER_SCHEDULES:
+        index_options(idx, **{name: sched.get(name, defaults[name]) for name in names})
+        got, stats = idx.map_se_batch(bases, offsets, ag_wildcard=ag, max_mismatches=6, b=5000)
+        assert_best_equal(got, p["want"], "crowded %s %s" % ("GA" if ag else "CT", sched))
+        assert int(stats["too_short"]) == p["too_short"], sched
 
 
 @pytest.mark.parametrize("top_k", [5, 50])

@@ -34,19 +34,14 @@
     }                                                                                        \
   } while (0)
 
-// Tuning values and test hooks of the mapping calls (walt_index_set_option; names in options.h).  The mapping calls
+// Tuning values and test hooks of the mapping calls (walt_index_set_option; the names: kOptions in device_index.hip, described in include/walt_amd.h).  The mapping calls
 // read NO environment variable: an index maps the same way whatever the process environment holds.  None of these
 // values can make a call need MORE workspace than walt_se_workspace_bytes / walt_pe_workspace_bytes promise.
 struct walt_options {
   // single-end
   int se_pipe = 1;            // the staged heavy pass in two halves on two streams
   long long se_heavy_chunk = 0;  // reads per chunk of the heavy list (0: the default; test hook: several chunks on a small batch)
-  int se_stage_blocks = 0;    // blocks per compute unit of the stage launches (0: fill the device)
-  int se_verify_blocks = 0;   // ... of the dense verifier launches (0: its occupancy)
-  int se_stagger = 0;         // the second half of the heavy pass starts one look-up stage behind the first
-  int se_lit_ablate = 0;      // measurement only (results wrong when set)
-  int se_lit_side = 1;        // the literal pass on a side stream beside the end of the heavy pass (2: pass 1's share right after pass 1)
-  int se_lit_staged = 0;      // the deferred reads through staged rounds with the reference's search on instead of the strand-major kernel
+  int se_lit_side = 1;        // the literal pass on a side stream beside the end of the heavy pass (0: on the call's stream, after it)
   long long se_defer_min = -1;   // long seeds: key-equal ranges of more slots go to the verifier (-1: default, 0: never)
   int se_stage_occ = 0;       // wavefronts per SIMD the stage kernel is built for (0: default)
   int se_carry = 1;           // pass 1 hands its state to the staged rounds (0: they start over at seed 0)

@@ -352,7 +352,6 @@ struct HeavyStage {
   uint32_t even;     // this is chunk number `chunk` of them (heavy_chunk_span; the list's length is known on the device only)
   uint32_t round;    // 0 .. kPat
   uint32_t defer_min;  // long seeds: key-equal ranges of more slots than this are narrowed by the verifier (0xFFFFFFFF: never)
-  uint32_t lit_ablate; // (measurement only, option se_lit_ablate; results are WRONG when set) bit 0: the literal rounds skip the reference's search
 };
 // What pass 1 hands to round 0 for a read it gives up (arrays indexed by the read's number in the batch, nullptr: the
 // heavy pass starts over at seed 0): the heavy-list entry carries the seed shift and best.strand (heavy_entry), st the
@@ -895,26 +894,8 @@ static __global__ void k_lit_snapshot(const uint32_t* __restrict__ count, uint32
   if (threadIdx.x == 0) { ctl2[0] = *count; rng[0] = *count; }
   if (threadIdx.x >= 8 && threadIdx.x < 24) ctl2[threadIdx.x] = 0;
 }
-// the second share of the side launches: the entries behind the first share (rng[0]) up to the list's length now --
-// ctl3 = {their number, .., [8..23] = 0 (bins), [24..25] = their range}; rng[0] = the length now (what the last launch starts at)
-static __global__ void k_lit_snapshot_rest(const uint32_t* __restrict__ count, uint32_t* __restrict__ ctl3, uint32_t* __restrict__ rng) {
-  if (threadIdx.x == 0) {
-    const uint32_t first = rng[0], c = *count;
-    ctl3[0] = c > first ? c - first : 0u;
-    ctl3[1] = first;
-    ctl3[24] = first;
-    ctl3[25] = c > first ? c : first;
-    rng[0] = c > first ? c : first;
-  }
-  if (threadIdx.x >= 8 && threadIdx.x < 24) ctl3[threadIdx.x] = 0;
-}
+// rng[1] = the list's final length: with rng[0], what was deferred after the side launch took its share
 static __global__ void k_lit_end(const uint32_t* __restrict__ count, uint32_t* __restrict__ rng) { rng[1] = *count; }
-// rng = {first, end}: the entries of the deferred list behind the `done` the literal rounds have mapped
-static __global__ void k_lit_rest(const uint32_t* __restrict__ count, uint32_t* __restrict__ rng, uint32_t done) {
-  const uint32_t c = *count;
-  rng[0] = done < c ? done : c;
-  rng[1] = c;
-}
 // (first != nullptr: the ctl[0] entries from *first on, sorted into the same places of `sorted`)
 static __global__ void k_bin_count(uint32_t* __restrict__ ctl, const uint32_t* __restrict__ list, const uint32_t* __restrict__ first) {
   __shared__ uint32_t bins[8];
@@ -1072,15 +1053,8 @@ __device__ uint32_t g_stage_stamps_on;
 // or the read is finished.  What the seed loop does per seed is what pass 1 does, with long slots searched (both
 // strands together: map_common.h probe_resolve_dual) and regions of up to kMidRegion candidates verified in the lane.
 // ---------------------------------------------------------------------------
-// LIT (the literal rounds, launch_map_se): the rounds over the reads the ordinary rounds gave up at a truly dangerous probe;
-// here such a probe's region comes from the reference's own search (core.h seed_lookup_ex -> lit_region_inferred: a few
-// key searches, hardly an entry load) and the read goes on like any other.  Until round 4 these reads were mapped from
-// scratch by the strand-major kernel of round 1 (k_map_se_literal: ~12 ns a read whatever its probes cost -- 120 ms for
-// the 9.5 M such reads of an hg19-scale assembly of 3,000 contigs).
-// MIDS = false (measured in round 4, not instantiated): regions of 5 .. 16 candidates become (gather) work items like the
-// larger ones instead of being verified by their lane: 4 spilled registers fewer, 41.5 -> 43.7 ms per 50 M reads.
-template <int NW, int OCC = 0, bool LIT = false, bool MIDS = true>  // OCC: wavefronts per SIMD the registers are capped for (0: the default)
-__global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10 ? 2 : 1)) : (NW <= 8 ? 4 : (NW <= 10 ? 3 : 1)))) void k_se_stage(
+template <int NW, int OCC = 0>  // OCC: wavefronts per SIMD the registers are capped for (0: the default)
+__global__ __launch_bounds__(kBlock, OCC ? OCC : (NW <= 8 ? 4 : (NW <= 10 ? 3 : 1))) void k_se_stage(
     IndexView iv, const uint32_t* __restrict__ codes2, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ err,
     uint32_t strand_base, uint32_t max_mm, uint32_t b, const uint32_t* __restrict__ mask_table, BestMatch* __restrict__ out,
     unsigned long long* __restrict__ stats, uint32_t* __restrict__ defer_count, uint32_t* __restrict__ defer_list,
@@ -1309,14 +1283,10 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
       const bool bad_p = need_p && bw_p && danger_filter_hit(bw_p, care);
       const bool bad_m = need_m && bw_m && danger_filter_hit(bw_m, care);
       STG(1);
-      bool lit_p = false, lit_m = false;  // LIT: this strand's region comes from the reference's search
       if (bad_p || bad_m) {  // a filter hit is a superset of the dangerous probes: the exact test
         const bool dng_p = bad_p && probe_is_dangerous(svp, care, seed_len);
         const bool dng_m = bad_m && probe_is_dangerous(svm, care, seed_len);
-        if constexpr (LIT) {
-          lit_p = dng_p;
-          lit_m = dng_m;
-        } else if (dng_p || dng_m) {  // the literal rounds take the read up again
+        if (dng_p || dng_m) {  // the literal pass maps the read (k_map_se_literal)
           deferred = true;
           active = false;
           need_p = need_m = false;
@@ -1325,8 +1295,8 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
         }
       }
       STG(2);
-      pp.ne = (need_p && !lit_p && hi_p > pp.lo) ? hi_p - pp.lo : 0u;
-      pm.ne = (need_m && !lit_m && hi_m > pm.lo) ? hi_m - pm.lo : 0u;
+      pp.ne = (need_p && hi_p > pp.lo) ? hi_p - pp.lo : 0u;
+      pm.ne = (need_m && hi_m > pm.lo) ? hi_m - pm.lo : 0u;
 #if defined(WALT_DIAG)
       if (WALT_DIAG_TWICE(3)) {  // the slot's four loads once more, on other lines: a long slot without its first 48 entries
         SlotProbe p2 = pp, m2 = pm;  // (still inside the slot and still long: the A pivot keys of that range's first plan)
@@ -1348,10 +1318,6 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
       } else {
         probe_resolve_dual<kLong>(svp, svm, pp, pm, care, seed_len, lp, lm, tail_p, tail_m);
       }
-      if constexpr (LIT) {  // IndexRegion as the reference runs it (positions are fetched with the candidates)
-        if (lit_p && need_p && !(hs.lit_ablate & 1u)) { seed_lookup_ex(iv, svp, care, slot, span, seed_len, lp, false); tail_p = false; defer_p = false; }
-        if (lit_m && need_m && !(hs.lit_ablate & 1u)) { seed_lookup_ex(iv, svm, care, slot, span, seed_len, lm, false); tail_m = false; defer_m = false; }
-      }
       uint32_t size_p = lp.reg.l <= lp.reg.u ? lp.reg.u - lp.reg.l + 1 : 0;
       uint32_t size_m = lm.reg.l <= lm.reg.u ? lm.reg.u - lm.reg.l + 1 : 0;
       STG(3);
@@ -1367,7 +1333,7 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
       const uint32_t tail_cut = tail_care_cut(sd, seed_len);
 
       constexpr bool kCoop = kPat == 3;  // the lanes' own regions as one list over the wavefront (coop_lane_regions)
-      constexpr uint32_t kLaneMax = kCoop ? kCoopRegion : ((MIDS || kMulti) ? kMidRegion : kSmallRegion);  // largest region a lane verifies itself
+      constexpr uint32_t kLaneMax = kCoop ? kCoopRegion : kMidRegion;  // largest region a lane verifies itself
       const bool big_p = size_p > kLaneMax || defer_p, big_m = size_m > kLaneMax || defer_m;
       if constexpr (kCoop) {
         const uint32_t own_p = big_p ? 0u : size_p, own_m = big_m ? 0u : size_m;
@@ -1430,7 +1396,7 @@ __global__ __launch_bounds__(kBlock, OCC ? OCC : (LIT ? (NW <= 8 ? 3 : (NW <= 10
       {
         const uint32_t nmid_p = (!kCoop && size_p > kSmallRegion && !big_p) ? size_p : 0u;
         const uint32_t nmid_m = (!kCoop && size_m > kSmallRegion && !big_m) ? size_m : 0u;
-        if constexpr ((MIDS || kMulti) && !kCoop)
+        if constexpr (!kCoop)
         if (__ballot(nmid_p | nmid_m))
           se_mid_regions<NW, kMulti>(iv, sh, svp, svm, nmid_p, nmid_m, lp.reg.l, lm.reg.l, sd, lr.len, lr.rd, mk, n_chrom, top_step,
                                      tail_cut, mt, sum_p, sum_m, ctr.verified);
@@ -2067,8 +2033,11 @@ uint64_t se_stride(uint32_t n) { return align_up(n ? n : 1, 64); }
 // The geometry a call uses follows from (n, read length, the index's options); the workspace a caller must provide
 // (walt_se_workspace_bytes, which knows no index) is that of the DEFAULT options, and no option may need more: an
 // option value that would is not applied (se_geometry).
-constexpr uint32_t kLitChunks = 2;  // chunks of the deferred list the literal rounds take (launch_map_se)
-constexpr uint32_t kHeavyCtlWords = 64 * kPat + 8 * kPat * kLitChunks + 32 + 8;  // 8 words per (chunk, round): up to 8 chunks x kPat rounds, the literal rounds' chunks, the side launch's second share, the rest launch's range
+// the side launch of the literal kernel (se_fork_literal): [0] the count of its share, [8..23] its bins
+// (launch_bin_deferred: 32 words), [32] [33] {entries it took, the list's final length}; a multiple of 4 words
+constexpr uint32_t kSideCtlWords = 36;
+constexpr uint32_t kHeavyCtlWords = 64 * kPat + kSideCtlWords;  // 8 words per (chunk, round): up to 8 chunks x kPat rounds; then the side launch's
+static_assert(kHeavyCtlWords % 4 == 0, "the state slots behind the control words are 16-byte aligned");
 struct SeGeometry {
   uint32_t hcap;     // reads per chunk
   uint32_t chunks;   // launched chunks (<= 8; even when piped)
@@ -2162,332 +2131,345 @@ struct SeShareArea {
   uint32_t* zero = nullptr;   // the block a call clears (kShareZeroBytes); the two slots' bucket cursors lie in front of it
 };
 
+// workspace of a single-end call: [64 words: read errors, deferral control] [statistic shards] [deferred list] [sorted
+// deferred list] [heavy list] [dense 2-bit reads] [state of the staged heavy pass] [what pass 1 hands over]
+struct SeWorkspace {
+  uint32_t* err;                // [0] non-ACGT words, [1] over-long reads, [2] dropped work items
+  unsigned long long* shards;   // statistic shards
+  uint32_t* defer_count;        // control block: [0] count, [8..15] bin counts, [16..23] bin cursors, [24] heavy count
+  uint32_t* defer_list;
+  uint32_t* codes2;             // deferred list, its sorted copy, heavy list, then the dense reads
+  uint32_t* heavy_area;         // state of the staged heavy pass behind the dense reads, 16-byte aligned
+  uint4* carry_area;
+  SeShareArea share;            // the grouping of the dense items (se_share_bytes)
+  uint64_t stride;
+  uint64_t end;                 // first byte behind the layout (walt_se_workspace_bytes bytes from the start at most)
+};
+
 template <class K>
-static int occupancy_blocks(K kernel) {
+static int occupancy_blocks(K kernel, int fallback = 4) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, 0) != hipSuccess || nb < 1) nb = 4;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, 0) != hipSuccess || nb < 1) nb = fallback;
   return nb;
 }
 
+// One mapping pass of a single-end call (se_map_pass): one conversion's two strands of the packed reads in w.codes2.
+struct SePass {
+  walt_index* idx;
+  const IndexView& view;
+  const SeWorkspace& w;
+  const uint64_t* offsets;
+  uint32_t n;
+  uint32_t strand_base;  // 0: C->T strands _CT00/_CT01, 2: G->A strands _GA10/_GA11
+  uint32_t max_mm, b;
+  BestMatch* out;
+  hipStream_t stream;
+  uint32_t* heavy_count() const { return w.defer_count + 24; }  // control block word (zeroed with it)
+  uint32_t* heavy_list() const { return w.defer_list + 2 * w.stride; }
+  uint32_t* side_ctl() const { return w.heavy_area + 64 * kPat; }  // the side launch's control words (kSideCtlWords)
+  uint32_t* side_rng() const { return side_ctl() + 32; }
+};
+
+// walt_profile_detail: an event on the call's stream after every kernel group (profiling on: bench.py)
+static void se_mark(const SePass& p, unsigned char kind) {
+  walt_index* idx = p.idx;
+  if (!idx->profile || idx->n_detail >= walt_index::kDetailEvents) return;
+  hipEvent_t& e = idx->ev_detail[idx->n_detail];
+  if (!e && hipEventCreate(&e) != hipSuccess) return;
+  if (hipEventRecord(e, p.stream) != hipSuccess) return;
+  idx->ev_kind[idx->n_detail++] = kind;
+}
+
+// ORDERING RULE 2.  Once a pass has forked onto the index's own streams (se_pipe: the second half of the staged pass,
+// se_side: the literal kernel), an error return must not leave work running on the caller's workspace: from the
+// first fork on, every HIP call is checked with WALT_HIP_FORKED, which waits here before it returns.  (A stream nothing
+// was queued on is idle, so the wait needs no record of whether the fork has happened.)
+static void se_unwind(const walt_index* idx) {
+  if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
+  if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
+}
+
+// k_map_se over the whole batch: pass 1 (carry: what it hands to the staged rounds), or with HEAVY the one-kernel heavy
+// pass over the heavy list.  diag (diagnostic build only): the instance with phase stamps / ablation.
+template <int NW, bool HEAVY>
+static void launch_k_map_se(const SePass& p, bool diag, const SeCarry& carry) {
+  const unsigned pg = persistent_grid(p.idx);
+  const unsigned g1 = grid_for(p.n) < pg ? grid_for(p.n) : pg;
+  auto kernel = k_map_se<NW, false, HEAVY>;
+  uint32_t ablate = 0;
+  unsigned long long* stamps = nullptr;
+#if defined(WALT_DIAG)
+  if (diag) {
+    kernel = k_map_se<NW, true, HEAVY>;
+    ablate = g_ablate;
+    stamps = g_stamps;
+  }
+#endif
+  hipLaunchKernelGGL(kernel, dim3(g1), dim3(kBlock), 0, p.stream, p.view, p.w.codes2, p.offsets, p.w.err, p.n, p.strand_base,
+                     p.max_mm, p.b, p.idx->d_mask_table, p.out, p.w.shards, p.w.defer_count, p.w.defer_list, p.heavy_count(),
+                     p.heavy_list(), ablate, stamps, carry);
+}
+
+// k_map_se_literal on stream s over `list`: all of it (count: the device word that holds its length), or with `range`
+// the entries [range[0], range[1]) only
 template <int NW>
-static int launch_map_se(walt_index* idx, const IndexView& view, const uint32_t* codes2, const uint64_t* offsets, uint32_t* err,
-                         uint32_t n, uint32_t strand_base, uint32_t max_mm, uint32_t b, BestMatch* out,
-                         unsigned long long* stats, uint32_t* defer_count, uint32_t* defer_list, uint64_t stride,
-                         uint32_t* heavy_area, uint4* carry_area, const SeShareArea& share_area, hipStream_t stream) {
+static void launch_literal(const SePass& p, hipStream_t s, uint32_t* count, uint32_t* list, const uint32_t* range = nullptr) {
+  const unsigned g = grid_for(p.n) < kLiteralGrid ? grid_for(p.n) : kLiteralGrid;
+  hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g), dim3(kBlock), 0, s, p.view, p.w.codes2, p.offsets, p.w.err, p.strand_base,
+                     p.max_mm, p.b, p.idx->d_mask_table, p.out, p.w.shards, count, list, 0u, range);
+}
+
+// k_se_stage on stream s: one round (hs) of one chunk.  The instance built for one wavefront per SIMD fewer spills no
+// registers (reads of up to 128 bases: 3 instead of 4; measured after the read hand-out and the candidate list went in:
+// 38.6 against 39.6 ms per 50 M reads) -- unless the genome has more sequences than the LDS table of chromosome starts
+// holds (chrom_core.h ChromTab): then every look-up bisects in HBM and the extra wavefront is worth more than the
+// registers (3,000 contigs: 106.7 against 109.8 ms).  Option se_stage_occ chooses explicitly (A/B).
+template <int NW>
+static void launch_stage(const SePass& p, hipStream_t s, unsigned grid, const HeavyStage& hs, const SeCarry& carry) {
+  constexpr int kFewer = NW <= 8 ? 3 : 2;
+  const int occ = p.idx->opt.se_stage_occ;
+  const bool fewer = NW <= 10 && (occ ? occ == kFewer : (NW <= 8 && p.view.n_chrom <= 1023u));
+  auto kernel = fewer ? k_se_stage<NW, kFewer> : k_se_stage<NW>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, p.view, p.w.codes2, p.offsets, p.w.err, p.strand_base, p.max_mm,
+                     p.b, p.idx->d_mask_table, p.out, p.w.shards, p.w.defer_count, p.w.defer_list, p.heavy_count(),
+                     p.heavy_list(), hs, carry);
+}
+
+// The staged heavy pass of one call: what the launches of all its chunks share (se_staged_plan)
+struct SeStaged {
+  SeGeometry geo;
+  bool piped;      // two halves on two streams: odd chunks on idx->se_pipe with the second state slot
+  bool lit_side;   // the literal kernel runs on idx->se_side beside the end of the heavy pass (se_fork_literal)
+  HeavyStage hs;   // what holds for every chunk; se_chunk_rounds adds the chunk's slot and the round
+  SeCarry carry;
+  SeShare sh;      // option se_verify_share: the dense items grouped by region
+  int share_mode;  // 0: off, 1: grouped and verified a group at a time, 2: grouped and counted only (measurement)
+  uint64_t share_slot;
+  uint32_t share_alloc;
+  unsigned g_stage, g_narrow, g_dense, g_gather, g_shared;  // grids of a round's launches
+};
+
+template <int NW>
+static int se_staged_plan(const SePass& p, bool diag, const SeCarry& carry, SeStaged& st) {
+  walt_index* idx = p.idx;
   const walt_options& opt = idx->opt;
-  const unsigned pg = persistent_grid(idx);
-  const unsigned g1 = grid_for(n) < pg ? grid_for(n) : pg;
-  uint32_t* heavy_count = defer_count + 24;   // control block word (zeroed with it)
-  uint32_t* heavy_list = defer_list + 2 * stride;
+  st.geo = se_geometry(p.n, NW, opt);
+  // two halves on two streams.  Every launch is a set of persistent blocks that fill the device by their registers, so
+  // two launches do not share a SIMD for long; what the second stream buys is that one half's launch starts into the
+  // other's tail.  Diagnostic runs keep one stream.
+  st.piped = st.geo.piped && !diag;
+  st.carry = carry;
+  st.hs = {};
+  st.hs.hcap = st.geo.hcap;
+  st.hs.even = st.piped ? 1u : 0u;
+  // long seeds: key-equal ranges of more slots than this go to the verifier unnarrowed (option se_defer_min: 0 = never
+  // (A/B: every range narrowed by lit_region in the stage kernel); measured 4 / 8 / 16 -> 32.5 / 33.2 / 34.2 ms per 25 M 150-base reads)
+  st.hs.defer_min = opt.se_defer_min < 0 ? (uint32_t)kSmallRegion
+                  : opt.se_defer_min == 0 ? 0xFFFFFFFFu
+                  : (uint32_t)(opt.se_defer_min < (long long)kSmallRegion ? (long long)kSmallRegion : opt.se_defer_min);
+  // option se_verify_share: the dense items grouped by region (SeShare) -- 1: and verified a group at a time
+  // (k_se_verify_shared), 2: grouped and counted only, verified one by one as with 0 (measurement)
+  const SeShareArea& area = p.w.share;
+  st.sh = {};
+  st.share_slot = (area.big_bytes / (st.geo.piped ? 2 : 1)) & ~15ull;
+  st.share_alloc = se_share_cap_for(st.geo, st.share_slot, 0);
+  st.sh.cap = se_share_cap_for(st.geo, st.share_slot, opt.se_share_cap);
+  st.share_mode = (share_nw<NW>() && !diag && area.zero != nullptr && st.sh.cap > 0) ? opt.se_verify_share : 0;
+  // (se_share_r: another unit size for the count-only mode, tools/verify_share_bench.py; the verifier is built for kShareR)
+  st.sh.r = (st.share_mode == 2 && opt.se_share_r > 0) ? (uint32_t)opt.se_share_r : (uint32_t)kShareR;
+  static const int vb_dense = occupancy_blocks(k_se_verify<NW, NW <= 10>, 4);
+  static const int vb_gather = occupancy_blocks(k_se_verify<NW, false>, 2);
+  const unsigned pg = persistent_grid(idx), n_cu = (unsigned)idx->n_cu;
+  st.g_stage = grid_for(st.geo.hcap) < pg ? grid_for(st.geo.hcap) : pg;
+  st.g_narrow = pg;
+  st.g_dense = (unsigned)vb_dense * n_cu;
+  st.g_gather = (unsigned)vb_gather * n_cu;
+  st.g_shared = 4 * n_cu;
+  if constexpr (share_nw<NW>()) {
+    if (st.share_mode == 1) {
+      static const int vb_shared = occupancy_blocks(k_se_verify_shared<NW, kShareR>);
+      st.g_shared = (unsigned)vb_shared * n_cu;
+    }
+  }
+  // The reads with a truly dangerous probe: the strand-major kernel (k_map_se_literal, the reference's search inferred:
+  // core.h lit_region_inferred) on a low-priority side stream (option se_lit_side = 0: on the call's stream, at the end)
+  st.lit_side = opt.se_lit_side != 0 && !diag && p.n <= kDeferMask;
+  if (st.lit_side && !idx->se_side) {
+    int lo_pri = 0, hi_pri = 0;
+    WALT_HIP(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
+    WALT_HIP(create_stream_set(&idx->se_side, &lo_pri, {&idx->se_fork, &idx->se_join}));
+  }
+  if (st.piped && !idx->se_pipe)
+    WALT_HIP(create_stream_set(&idx->se_pipe, nullptr, {&idx->se_pipe_ev[0], &idx->se_pipe_ev[1], &idx->se_pipe_ev[2]}));
+  return WALT_OK;
+}
+
+// ORDERING RULE 1.  Nothing that appends to the deferred list may run while the side launch's share of it is fixed
+// (k_lit_snapshot): the appenders are pass 1 and the stage kernels of any chunk.  So the snapshot is enqueued behind the
+// last look-up round of the FIRST chunk of each half -- on the stream of the last of them (cs), which waits for the
+// other's (se_pipe_ev[1]); round kPat probes nothing, and the later chunks of cs follow in stream order -- and the first
+// chunk behind the first pair, on the other stream, waits for se_fork (launch_map_se).  After the snapshot the list is
+// complete but for what later chunks add (nothing, when the heavy list fits the first chunks): the share is sorted and
+// mapped on se_side while the main streams run the last verifier launches and the last round, and what later chunks
+// defer is mapped at the end (se_finish).
+template <int NW>
+static int se_fork_literal(const SePass& p, const SeStaged& st, hipStream_t cs) {
+  walt_index* idx = p.idx;
+  const auto unwind = [&] { se_unwind(idx); };
+  if (st.piped) WALT_HIP_FORKED(hipStreamWaitEvent(cs, idx->se_pipe_ev[1], 0));
+  hipLaunchKernelGGL(k_lit_snapshot, dim3(1), dim3(64), 0, cs, p.w.defer_count, p.side_ctl(), p.side_rng());
+  WALT_HIP_FORKED(hipEventRecord(idx->se_fork, cs));
+  WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_side, idx->se_fork, 0));
+  uint32_t* const sorted = p.w.defer_list + p.w.stride;
+  launch_bin_deferred(p.side_ctl(), p.w.defer_list, sorted, idx->se_side);
+  launch_literal<NW>(p, idx->se_side, p.side_ctl(), sorted);
+  WALT_HIP_FORKED(hipEventRecord(idx->se_join, idx->se_side));
+  return WALT_OK;
+}
+
+// the rounds of chunk c: look-up stage, then the verifiers of its items, kPat times, and the final fold
+template <int NW>
+static int se_chunk_rounds(const SePass& p, const SeStaged& st, uint32_t c) {
+  walt_index* idx = p.idx;
+  const auto unwind = [&] { se_unwind(idx); };
+  const bool odd = st.piped && (c & 1u);
+  const hipStream_t cs = odd ? idx->se_pipe : p.stream;
+  const uint32_t hcap = st.geo.hcap, slot = odd ? 1u : 0u;
+  const SeShareArea& area = p.w.share;
+  uint32_t* const ctl_base = p.w.heavy_area + 8 * kPat * c;
+  uint32_t* const lists = p.w.heavy_area + kHeavyCtlWords + slot * (st.geo.slot_bytes / 4);  // [kPat][hcap]: what round k hands to round k + 1
+  HeavyStage hs = st.hs;
+  hs.st = reinterpret_cast<uint4*>(lists + (uint64_t)kPat * hcap);
+  hs.rdq = hs.st + hcap;
+  hs.sums = hs.rdq + (uint64_t)rd_quads<NW>() * hcap;
+  hs.items = hs.sums + (uint64_t)(kPat + 1) * hcap;  // 2 * hcap items of item_quads<NW>() quads
+  hs.giants = hs.items + (uint64_t)2 * hcap * item_quads<NW>();
+  hs.first = c * hcap;
+  hs.chunk = c;
+  SeShare sh = st.sh;
+  if (st.share_mode) {
+    sh.count = area.zero + slot * kGroupBuckets;
+    sh.cursor = area.zero - (2 - slot) * kGroupBuckets;
+    sh.order = reinterpret_cast<uint32_t*>(area.big + slot * st.share_slot);
+    sh.units = reinterpret_cast<uint2*>(sh.order + st.share_alloc);
+  }
+  for (uint32_t round = 0; round <= kPat; ++round) {
+    hs.round = round;
+    hs.ctl = ctl_base + 8 * (round < kPat ? round : 0);
+    hs.list_in = round ? lists + (uint64_t)(round - 1) * hcap : nullptr;
+    hs.count_in = round ? ctl_base + 8 * (round - 1) : nullptr;
+    hs.list_out = round < kPat ? lists + (uint64_t)round * hcap : nullptr;
+    launch_stage<NW>(p, cs, st.g_stage, hs, st.carry);
+    if (!odd) se_mark(p, 1);
+    if (round == kPat) break;
+    if (round == kPat - 1) {  // (round kPat probes nothing: this chunk has made its last deferrals)
+      if (st.piped && c == 0) WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[1], p.stream));
+      if (st.lit_side && c == (st.piped ? 1u : 0u))
+        if (const int rc = se_fork_literal<NW>(p, st, cs)) return rc;
+    }
+    if constexpr (NW <= 10 && long_seed_nw<NW>())
+      hipLaunchKernelGGL((k_se_tail_narrow<NW>), dim3(st.g_narrow), dim3(kBlock), 0, cs, p.view, p.strand_base, hs, p.b);
+    bool shared_done = false;
+    if constexpr (share_nw<NW>()) {
+      if (st.share_mode) {
+        sh.ctl = area.zero + 2 * kGroupBuckets + 4 * (c * kPat + round);
+        sh.recs = reinterpret_cast<unsigned long long*>(area.zero + 2 * kGroupBuckets + kShareCtlWords) + 2 * (c * kPat + round);
+        const unsigned gs = (unsigned)idx->n_cu;  // small launches: about one block per compute unit
+        hipLaunchKernelGGL((k_se_share_bin<NW, false>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+        hipLaunchKernelGGL(k_se_share_scan, dim3(1), dim3(kShareScanThreads), 0, cs, sh);
+        hipLaunchKernelGGL((k_se_share_bin<NW, true>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+        hipLaunchKernelGGL((k_se_share_cut<NW>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
+        if (st.share_mode == 1) {
+          hipLaunchKernelGGL((k_se_verify_shared<NW, kShareR>), dim3(st.g_shared), dim3(kBlock), 0, cs, p.view, p.strand_base, p.w.shards, hs, sh, p.b, p.w.err);
+          shared_done = true;
+        }
+      }
+    }
+    if constexpr (NW <= 10) {
+      if (!shared_done)
+        hipLaunchKernelGGL((k_se_verify<NW, true>), dim3(st.g_dense), dim3(kBlock), 0, cs, p.view, p.strand_base, p.w.shards, hs, p.b, p.w.err);
+    }
+    hipLaunchKernelGGL((k_se_verify<NW, false>), dim3(st.g_gather), dim3(kBlock), 0, cs, p.view, p.strand_base, p.w.shards, hs, p.b, p.w.err);
+    if (!odd) se_mark(p, 2);
+  }
+  return WALT_OK;
+}
+
+// the end of a pass: the deferred reads that no side launch has taken
+template <int NW>
+static int se_finish(const SePass& p, bool lit_side) {
+  walt_index* idx = p.idx;
+  const auto unwind = [&] { se_unwind(idx); };
+  if (lit_side) {  // what the chunks behind the first one deferred (usually nothing), then the side launch ends the call
+    hipLaunchKernelGGL(k_lit_end, dim3(1), dim3(1), 0, p.stream, p.w.defer_count, p.side_rng());
+    launch_literal<NW>(p, p.stream, p.w.defer_count, p.w.defer_list, p.side_rng());
+    WALT_HIP_FORKED(hipStreamWaitEvent(p.stream, idx->se_join, 0));
+    se_mark(p, 3);
+    return WALT_OK;
+  }
+  uint32_t* defer_sorted = p.w.defer_list + p.w.stride;
+  if (p.n <= kDeferMask) launch_bin_deferred(p.w.defer_count, p.w.defer_list, defer_sorted, p.stream);
+  else defer_sorted = p.w.defer_list;
+  debug_sync("bin", p.stream);
+  launch_literal<NW>(p, p.stream, p.w.defer_count, defer_sorted);
+  debug_sync("literal pass", p.stream);
+  se_mark(p, 3);
+  return WALT_OK;
+}
+
+// One single-end mapping pass, as the schedule it enqueues: pass 1 over every read; the heavy reads it set aside in
+// chunks of staged rounds (two halves on two streams when piped); the deferred reads through the strand-major kernel,
+// on a side stream beside the end of the heavy pass or behind it.
+template <int NW>
+static int launch_map_se(const SePass& p) {
+  walt_index* idx = p.idx;
+  const walt_options& opt = idx->opt;
+  const auto unwind = [&] { se_unwind(idx); };
   const bool mono = opt.se_heavy_mono != 0;
   SeCarry carry;
-  carry.st = (opt.se_carry && !mono) ? carry_area : nullptr;
-  carry.neg = carry_area + stride;
-  carry.stride = stride;
-  // walt_profile_detail: an event after every kernel group (profiling on: bench.py)
-  idx->n_detail = 0;
-  auto mark = [&](unsigned char kind) {
-    if (!idx->profile || idx->n_detail >= walt_index::kDetailEvents) return;
-    hipEvent_t& e = idx->ev_detail[idx->n_detail];
-    if (!e && hipEventCreate(&e) != hipSuccess) return;
-    if (hipEventRecord(e, stream) != hipSuccess) return;
-    idx->ev_kind[idx->n_detail++] = kind;
-  };
-  mark(255);  // start
+  carry.st = (opt.se_carry && !mono) ? p.w.carry_area : nullptr;
+  carry.neg = p.w.carry_area + p.w.stride;
+  carry.stride = p.w.stride;
 #if defined(WALT_DIAG)
   const bool diag = g_ablate != 0 || g_stamps != nullptr;  // diagnostic instantiation (stamps / ablation)
   // WALT_AMD_STAMPS=2: phase stamps of the (one-kernel) heavy pass only, 3: of pass 1 only (1: both, summed)
   const char* sm = getenv("WALT_AMD_STAMPS");
   const int stamp_mode = sm ? atoi(sm) : 0;
   const bool diag1 = diag && stamp_mode != 2, diag2 = diag && stamp_mode != 3;
-  if (diag1)
-    hipLaunchKernelGGL((k_map_se<NW, true, false>), dim3(g1), dim3(kBlock), 0, stream, view, codes2, offsets, err, n,
-                       strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, heavy_count,
-                       heavy_list, g_ablate, g_stamps, carry);
-  else
 #else
-  const bool diag = false;
+  const bool diag = false, diag1 = false, diag2 = false;
 #endif
-    hipLaunchKernelGGL((k_map_se<NW, false, false>), dim3(g1), dim3(kBlock), 0, stream, view, codes2, offsets, err, n,
-                       strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, heavy_count,
-                       heavy_list, 0u, nullptr, carry);
-  debug_sync("pass 1", stream);
-  mark(0);
-  bool lit_done = false;  // the literal rounds have mapped the deferred reads (all but what the rest launch below takes)
-  bool lit_side = false;  // the strand-major literal kernel runs on a side stream beside the end of the heavy pass
-  bool forked = false;  // work is queued on the index's own streams: an error return must not leave it running
-  auto unwind = [&]() {
-    if (!forked) return;
-    if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
-    if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
-  };
-  uint32_t* const rng = heavy_area + kHeavyCtlWords - 8;  // {first entry, end} of the deferred list the rest launch maps
+  idx->n_detail = 0;
+  se_mark(p, 255);  // start
+  launch_k_map_se<NW, false>(p, diag1, carry);
+  debug_sync("pass 1", p.stream);
+  se_mark(p, 0);
+  bool lit_side = false;
   if (mono) {
     // the one-kernel heavy pass (large regions verified by the whole wavefront of their read's lane) instead of the
     // staged one (large regions streamed by k_se_verify); same results, kept for comparison
-#if defined(WALT_DIAG)
-    if (diag2)
-      hipLaunchKernelGGL((k_map_se<NW, true, true>), dim3(g1), dim3(kBlock), 0, stream, view, codes2, offsets, err, n,
-                         strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, heavy_count,
-                         heavy_list, g_ablate, g_stamps, SeCarry());
-    else
-#endif
-      hipLaunchKernelGGL((k_map_se<NW, false, true>), dim3(g1), dim3(kBlock), 0, stream, view, codes2, offsets, err, n,
-                         strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, heavy_count,
-                         heavy_list, 0u, nullptr, SeCarry());
+    launch_k_map_se<NW, true>(p, diag2, SeCarry());
   } else {
-    const SeGeometry geo = se_geometry(n, NW, opt);
-    const uint32_t hcap = geo.hcap;
-    // two halves on two streams: odd chunks on idx->se_pipe with the second state slot.  Every launch is a set of
-    // persistent blocks that fill the device by their registers, so two launches do not share a SIMD for long; what
-    // the second stream buys is that one half's launch starts into the other's tail.  Diagnostic runs keep one stream.
-    const bool piped = geo.piped && !diag;
-    const uint32_t chunks = geo.chunks;  // <= 8
-    HeavyStage hs;
-    hs.ctl = heavy_area;
-    hs.hcap = hcap;
-    hs.even = piped ? 1u : 0u;
-    const uint64_t slot_words = geo.slot_bytes / 4;
-    // option se_verify_share: the dense items grouped by region (SeShare) -- 1: and verified a group at a time
-    // (k_se_verify_shared), 2: grouped and counted only, verified one by one as with 0 (measurement)
-    SeShare sh = {};
-    const uint64_t share_slot = (share_area.big_bytes / (geo.piped ? 2 : 1)) & ~15ull;
-    const uint32_t share_alloc = se_share_cap_for(geo, share_slot, 0);
-    sh.cap = se_share_cap_for(geo, share_slot, opt.se_share_cap);
-    int share_mode = (share_nw<NW>() && !diag && share_area.zero != nullptr && sh.cap > 0) ? opt.se_verify_share : 0;
-    // (se_share_r: another unit size for the count-only mode, tools/verify_share_bench.py; the verifier is built for kShareR)
-    sh.r = (share_mode == 2 && opt.se_share_r > 0) ? (uint32_t)opt.se_share_r : (uint32_t)kShareR;
-    auto use_slot = [&](uint32_t k, uint32_t*& lists) {
-      lists = heavy_area + kHeavyCtlWords + k * slot_words;  // [kPat][hcap]: what round k hands to round k + 1
-      hs.st = reinterpret_cast<uint4*>(lists + (uint64_t)kPat * hcap);
-      hs.rdq = hs.st + hcap;
-      hs.sums = hs.rdq + (uint64_t)rd_quads<NW>() * hcap;
-      hs.items = hs.sums + (uint64_t)(kPat + 1) * hcap;  // 2 * hcap items of item_quads<NW>() quads
-      hs.giants = hs.items + (uint64_t)2 * hcap * item_quads<NW>();
-      if (share_mode) {
-        sh.count = share_area.zero + k * kGroupBuckets;
-        sh.cursor = share_area.zero - (2 - k) * kGroupBuckets;
-        sh.order = reinterpret_cast<uint32_t*>(share_area.big + k * share_slot);
-        sh.units = reinterpret_cast<uint2*>(sh.order + share_alloc);
-      }
-    };
-    // long seeds: key-equal ranges of more slots than this go to the verifier unnarrowed (option se_defer_min: 0 = never
-    // (A/B: every range narrowed by lit_region in the stage kernel); measured 4 / 8 / 16 -> 32.5 / 33.2 / 34.2 ms per 25 M 150-base reads)
-    hs.defer_min = opt.se_defer_min < 0 ? (uint32_t)kSmallRegion
-                 : opt.se_defer_min == 0 ? 0xFFFFFFFFu
-                 : (uint32_t)(opt.se_defer_min < (long long)kSmallRegion ? (long long)kSmallRegion : opt.se_defer_min);
-    hs.lit_ablate = (uint32_t)opt.se_lit_ablate;
-    uint32_t* const ctl0 = heavy_area;
-    static const int vb_dense = [] {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_se_verify<NW, NW <= 10>, kBlock, 0) != hipSuccess || nb < 1) nb = 4;
-      return nb;
-    }();
-    static const int vb_gather = [] {
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_se_verify<NW, false>, kBlock, 0) != hipSuccess || nb < 1) nb = 2;
-      return nb;
-    }();
-    auto share_blocks = []() -> int {  // blocks per compute unit of k_se_verify_shared<NW, kShareR>
-      if constexpr (share_nw<NW>()) {
-        static const int nb = occupancy_blocks(k_se_verify_shared<NW, kShareR>);
-        return nb;
-      } else {
-        return 4;
-      }
-    };
-    const unsigned vg_dense = (unsigned)vb_dense * (unsigned)idx->n_cu, vg_gather = (unsigned)vb_gather * (unsigned)idx->n_cu;
-    // The reads with a truly dangerous probe.  Default: the strand-major kernel (k_map_se_literal, the reference's search
-    // inferred: core.h lit_region_inferred) on a low-priority side stream: after the last look-up round of the first chunk
-    // (of each half) the list is complete but for what later chunks add (nothing, when the heavy list fits these
-    // chunks); it is sorted and mapped while the main streams run the last verifier launches and the last round; what
-    // later chunks defer is mapped at the end.  Option se_lit_staged = 1: through staged rounds instead (below).
-    const bool lit_staged = opt.se_lit_staged != 0 && !diag;
-    lit_side = !lit_staged && opt.se_lit_side != 0 && !diag && n <= kDeferMask;
-    uint32_t* const ctl2 = ctl0 + 64 * kPat;  // [0] count of the side launch, [8..23] its bins (the literal rounds' words: one or the other)
-    uint32_t* const rng_side = ctl2 + 32;     // {entries the side launch took, the list's final length}
-    static_assert(8 * kPat * kLitChunks >= 34, "the side launch's control words fit the literal rounds' area");
-    if (lit_side && !idx->se_side) {
-      int lo_pri = 0, hi_pri = 0;
-      WALT_HIP(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
-      WALT_HIP(create_stream_set(&idx->se_side, &lo_pri, {&idx->se_fork, &idx->se_join}));
-    }
-    if (piped && !idx->se_pipe)
-      WALT_HIP(create_stream_set(&idx->se_pipe, nullptr, {&idx->se_pipe_ev[0], &idx->se_pipe_ev[1], &idx->se_pipe_ev[2]}));
-    // se_lit_side = 2 (default): the side launch starts HERE, on what pass 1 deferred (most of the list: pass 1 sees every
-    // read, the staged rounds the heavy sixth), and runs beside the whole heavy pass -- a chain of dependent look-ups in
-    // few wavefronts that fills a fraction of the device; what the staged rounds defer is mapped at the end.  The
-    // snapshot is taken before any staged kernel of either half can append to the list.
-    const bool lit_early = lit_side && opt.se_lit_side >= 2;
-    if (lit_early) {
-      hipLaunchKernelGGL(k_lit_snapshot, dim3(1), dim3(64), 0, stream, defer_count, ctl2, rng_side);
-      WALT_HIP(hipEventRecord(idx->se_fork, stream));
-      WALT_HIP(hipStreamWaitEvent(idx->se_side, idx->se_fork, 0));
-      forked = true;
-      launch_bin_deferred(ctl2, defer_list, defer_list + stride, idx->se_side);
-      const unsigned g_lit = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-      hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g_lit), dim3(kBlock), 0, idx->se_side, view, codes2, offsets, err,
-                         strand_base, max_mm, b, idx->d_mask_table, out, stats, ctl2, defer_list + stride, 0u);
-      WALT_HIP_FORKED(hipEventRecord(idx->se_join, idx->se_side));
-    }
-    if (piped) {  // (pass 1 done)
-      WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[0], stream));
+    SeStaged st;
+    if (const int rc = se_staged_plan<NW>(p, diag, carry, st)) return rc;
+    lit_side = st.lit_side;
+    if (st.piped) {  // the second half starts behind pass 1
+      WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[0], p.stream));
       WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_pipe, idx->se_pipe_ev[0], 0));
     }
-    // the rounds of one chunk: look-up stage, then the verifiers of its items, kPat times, and the final fold
-    auto run_chunk = [&](hipStream_t cs, uint32_t* ctl_base, uint32_t* lists, bool lit, const uint32_t* count, const uint32_t* list,
-                         const SeCarry& cy, bool marks, uint32_t c_side) -> int {
-      // (options se_stage_blocks / se_verify_blocks: blocks per compute unit of these launches -- a launch that leaves
-      // wavefront slots free lets the other half's launch of the other kind run beside it; A/B)
-      const unsigned pgs = opt.se_stage_blocks > 0 ? (unsigned)opt.se_stage_blocks * (unsigned)idx->n_cu : pg;
-      const unsigned gh = grid_for(hcap) < pgs ? grid_for(hcap) : pgs;
-      const unsigned vgd = opt.se_verify_blocks > 0 ? (unsigned)opt.se_verify_blocks * (unsigned)idx->n_cu : vg_dense;
-      for (uint32_t round = 0; round <= kPat; ++round) {
-        hs.round = round;
-        hs.ctl = ctl_base + 8 * (round < kPat ? round : 0);
-        hs.list_in = round ? lists + (uint64_t)(round - 1) * hcap : nullptr;
-        hs.count_in = round ? ctl_base + 8 * (round - 1) : nullptr;
-        hs.list_out = round < kPat ? lists + (uint64_t)round * hcap : nullptr;
-        if (lit)
-          hipLaunchKernelGGL((k_se_stage<NW, 0, true>), dim3(gh), dim3(kBlock), 0, cs, view, codes2, offsets, err,
-                             strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, count, list, hs, cy);
-
-        // One wavefront per SIMD fewer and no spilled registers (reads of up to 128 bases: 3 instead of 4; measured after
-        // the read hand-out and the candidate list went in: 38.6 against 39.6 ms per 50 M reads) -- unless the genome has
-        // more sequences than the LDS table of chromosome starts holds (chrom_core.h ChromTab): then every look-up
-        // bisects in HBM and the extra wavefront is worth more than the registers (3,000 contigs: 106.7 against 109.8 ms).
-        // Option se_stage_occ chooses explicitly (A/B).
-        else if (NW <= 10 && (opt.se_stage_occ ? opt.se_stage_occ == (NW <= 8 ? 3 : 2) : (NW <= 8 && view.n_chrom <= 1023u)))
-          hipLaunchKernelGGL((k_se_stage<NW, (NW <= 8 ? 3 : 2)>), dim3(gh), dim3(kBlock), 0, cs, view, codes2, offsets, err,
-                             strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, count, list, hs, cy);
-        else
-          hipLaunchKernelGGL((k_se_stage<NW>), dim3(gh), dim3(kBlock), 0, cs, view, codes2, offsets, err,
-                             strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, count, list, hs, cy);
-        if (marks) mark(lit ? 3 : 1);
-        if (round == kPat) break;
-        if (!lit && round == 0 && piped && c_side == 0 && opt.se_stagger != 0) {  // the other half starts one stage behind (A/B)
-          WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[0], stream));
-          WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_pipe, idx->se_pipe_ev[0], 0));
-        }
-        if (!lit && round == kPat - 1) {  // (round kPat probes nothing: this chunk has made its last deferrals)
-          if (piped && c_side == 0) WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[1], stream));
-          if (lit_early && c_side == (piped ? 1u : 0u)) {  // the second share: what the staged rounds deferred
-            if (piped) WALT_HIP_FORKED(hipStreamWaitEvent(cs, idx->se_pipe_ev[1], 0));
-            uint32_t* const ctl3 = ctl0 + 64 * kPat + 8 * kPat * kLitChunks;
-            hipLaunchKernelGGL(k_lit_snapshot_rest, dim3(1), dim3(64), 0, cs, defer_count, ctl3, rng_side);
-            WALT_HIP_FORKED(hipEventRecord(idx->se_fork, cs));
-            WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_side, idx->se_fork, 0));
-            launch_bin_deferred(ctl3, defer_list, defer_list + stride, idx->se_side, ctl3 + 1);
-            const unsigned g_lit = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-            hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g_lit), dim3(kBlock), 0, idx->se_side, view, codes2, offsets, err,
-                               strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list + stride, 0u, ctl3 + 24);
-            WALT_HIP_FORKED(hipEventRecord(idx->se_join, idx->se_side));
-          }
-          if (lit_side && !lit_early && c_side == (piped ? 1u : 0u)) {
-            if (piped) WALT_HIP_FORKED(hipStreamWaitEvent(cs, idx->se_pipe_ev[1], 0));
-            hipLaunchKernelGGL(k_lit_snapshot, dim3(1), dim3(64), 0, cs, defer_count, ctl2, rng_side);
-            WALT_HIP_FORKED(hipEventRecord(idx->se_fork, cs));
-            WALT_HIP_FORKED(hipStreamWaitEvent(idx->se_side, idx->se_fork, 0));
-            forked = true;
-            launch_bin_deferred(ctl2, defer_list, defer_list + stride, idx->se_side);
-            const unsigned g_lit = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-            hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g_lit), dim3(kBlock), 0, idx->se_side, view, codes2, offsets, err,
-                               strand_base, max_mm, b, idx->d_mask_table, out, stats, ctl2, defer_list + stride, 0u);
-            WALT_HIP_FORKED(hipEventRecord(idx->se_join, idx->se_side));
-          }
-        }
-        if constexpr (NW <= 10 && long_seed_nw<NW>())
-          hipLaunchKernelGGL((k_se_tail_narrow<NW>), dim3(pg), dim3(kBlock), 0, cs, view, strand_base, hs, b);
-        bool shared_done = false;
-        if constexpr (share_nw<NW>()) {
-          if (share_mode && !lit && c_side < 8u) {
-            sh.ctl = share_area.zero + 2 * kGroupBuckets + 4 * (c_side * kPat + round);
-            sh.recs = reinterpret_cast<unsigned long long*>(share_area.zero + 2 * kGroupBuckets + kShareCtlWords) + 2 * (c_side * kPat + round);
-            const unsigned gs = (unsigned)idx->n_cu;  // small launches: about one block per compute unit
-            hipLaunchKernelGGL((k_se_share_bin<NW, false>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
-            hipLaunchKernelGGL(k_se_share_scan, dim3(1), dim3(kShareScanThreads), 0, cs, sh);
-            hipLaunchKernelGGL((k_se_share_bin<NW, true>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
-            hipLaunchKernelGGL((k_se_share_cut<NW>), dim3(gs), dim3(kBlock), 0, cs, hs, sh);
-            if (share_mode == 1) {
-              const unsigned vgs = (opt.se_verify_blocks > 0 ? (unsigned)opt.se_verify_blocks : (unsigned)share_blocks()) * (unsigned)idx->n_cu;
-              hipLaunchKernelGGL((k_se_verify_shared<NW, kShareR>), dim3(vgs), dim3(kBlock), 0, cs, view, strand_base, stats, hs, sh, b, err);
-              shared_done = true;
-            }
-          }
-        }
-        if constexpr (NW <= 10) {
-          if (!shared_done)
-            hipLaunchKernelGGL((k_se_verify<NW, true>), dim3(vgd), dim3(kBlock), 0, cs, view, strand_base, stats, hs, b, err);
-        }
-        hipLaunchKernelGGL((k_se_verify<NW, false>), dim3(vg_gather), dim3(kBlock), 0, cs, view, strand_base, stats, hs, b, err);
-        if (marks) mark(lit ? 3 : 2);
-      }
-      return WALT_OK;
-    };
-    for (uint32_t c = 0; c < chunks; ++c) {
-      const bool odd = piped && (c & 1u);
-      forked = forked || odd;
-      uint32_t* lists = nullptr;
-      use_slot(odd ? 1u : 0u, lists);
-      hs.first = c * hcap;
-      hs.chunk = c;
-      // chunks behind the first pair append to the deferred list: not while the side launch's share is being fixed
-      if (piped && lit_side && !lit_early && c == 2) WALT_HIP_FORKED(hipStreamWaitEvent(stream, idx->se_fork, 0));
-      const int rc_chunk = run_chunk(odd ? idx->se_pipe : stream, ctl0 + 8 * kPat * c, lists, false, heavy_count, heavy_list, carry, !odd, c);
-      if (rc_chunk) return rc_chunk;
+    for (uint32_t c = 0; c < st.geo.chunks; ++c) {  // <= 8
+      // rule 1 (se_fork_literal): chunk 2 is the first whose stream does not hold the snapshot
+      if (st.piped && st.lit_side && c == 2) WALT_HIP_FORKED(hipStreamWaitEvent(p.stream, idx->se_fork, 0));
+      if (const int rc = se_chunk_rounds<NW>(p, st, c)) return rc;
     }
-    if (piped) {  // the second half joins
+    if (st.piped) {  // the second half joins
       WALT_HIP_FORKED(hipEventRecord(idx->se_pipe_ev[2], idx->se_pipe));
-      WALT_HIP_FORKED(hipStreamWaitEvent(stream, idx->se_pipe_ev[2], 0));
-    }
-    // ---- the literal rounds: the reads the rounds above gave up at a truly dangerous probe (0.9 % of the reads of a
-    // 93-sequence genome, a fifth of those of a 3,000-contig assembly) go through the same rounds once more with the
-    // reference's search switched on (k_se_stage<.., LIT>), kLitChunks chunks of the deferred list; what lies behind
-    // them -- nothing, unless more than 2 x hcap reads were deferred -- is left to the strand-major kernel below.
-    if (lit_staged) {
-      hs.even = 0;
-      for (uint32_t c = 0; c < kLitChunks && c < chunks; ++c) {
-        uint32_t* lists = nullptr;
-        use_slot(geo.piped ? (c & 1u) : 0u, lists);
-        hs.first = c * hcap;
-        hs.chunk = c;
-        const int rc_chunk = run_chunk(stream, ctl0 + 64 * kPat + 8 * kPat * c, lists, true, defer_count, defer_list, SeCarry(), true, 0xFFFFFFFFu);
-        if (rc_chunk) return rc_chunk;
-      }
-      hipLaunchKernelGGL(k_lit_rest, dim3(1), dim3(1), 0, stream, defer_count, rng,
-                         (kLitChunks < chunks ? kLitChunks : chunks) * hcap);
-      lit_done = true;
+      WALT_HIP_FORKED(hipStreamWaitEvent(p.stream, idx->se_pipe_ev[2], 0));
     }
   }
-  debug_sync("heavy pass", stream);
-  mark(1);  // (the one-kernel heavy pass, when that is what ran)
-  if (lit_side) {  // what the chunks behind the first one deferred (usually nothing), then the side launch ends the call
-    uint32_t* const rng_side = heavy_area + 64 * kPat + 32;
-    hipLaunchKernelGGL(k_lit_end, dim3(1), dim3(1), 0, stream, defer_count, rng_side);
-    unsigned g3 = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-    hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g3), dim3(kBlock), 0, stream, view, codes2, offsets, err,
-                       strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, 0u, rng_side);
-    WALT_HIP_FORKED(hipStreamWaitEvent(stream, idx->se_join, 0));
-    mark(3);
-    return WALT_OK;
-  }
-  if (lit_done) {  // deferred reads behind the literal rounds' chunks (usually none)
-    unsigned g3 = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-    hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g3), dim3(kBlock), 0, stream, view, codes2, offsets, err,
-                       strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_list, 0u, rng);
-    mark(3);
-    return WALT_OK;
-  }
-  uint32_t* defer_sorted = defer_list + stride;
-  if (n <= kDeferMask) launch_bin_deferred(defer_count, defer_list, defer_sorted, stream);
-  else defer_sorted = defer_list;
-  debug_sync("bin", stream);
-  unsigned g2 = grid_for(n) < kLiteralGrid ? grid_for(n) : kLiteralGrid;
-  hipLaunchKernelGGL(k_map_se_literal<NW>, dim3(g2), dim3(kBlock), 0, stream, view, codes2, offsets, err,
-                     strand_base, max_mm, b, idx->d_mask_table, out, stats, defer_count, defer_sorted, 0u);
-  debug_sync("literal pass", stream);
-  mark(3);
-  return WALT_OK;
+  debug_sync("heavy pass", p.stream);
+  se_mark(p, 1);  // (the one-kernel heavy pass, when that is what ran)
+  return se_finish<NW>(p, lit_side);
 }
 
 #if defined(WALT_DIAG)
@@ -2513,20 +2495,6 @@ static int se_check_len(uint32_t max_read_len, int& nw) {
   return WALT_OK;
 }
 
-// workspace of a single-end call: [64 words: read errors, deferral control] [statistic shards] [deferred list] [sorted
-// deferred list] [heavy list] [dense 2-bit reads] [state of the staged heavy pass] [what pass 1 hands over]
-struct SeWorkspace {
-  uint32_t* err;                // [0] non-ACGT words, [1] over-long reads, [2] dropped work items
-  unsigned long long* shards;   // statistic shards
-  uint32_t* defer_count;        // control block: [0] count, [8..15] bin counts, [16..23] bin cursors, [24] heavy count
-  uint32_t* defer_list;
-  uint32_t* codes2;             // deferred list, its sorted copy, heavy list, then the dense reads
-  uint32_t* heavy_area;         // state of the staged heavy pass behind the dense reads, 16-byte aligned
-  uint4* carry_area;
-  SeShareArea share;            // the grouping of the dense items (se_share_bytes)
-  uint64_t stride;
-  uint64_t end;                 // first byte behind the layout (walt_se_workspace_bytes bytes from the start at most)
-};
 static SeWorkspace se_workspace(void* d_workspace, uint32_t n, uint32_t max_read_len, int nw) {
   SeWorkspace w;
   w.stride = se_stride(n);
@@ -2550,10 +2518,8 @@ static SeWorkspace se_workspace(void* d_workspace, uint32_t n, uint32_t max_read
 // strands _CT00/_CT01, 2: G->A strands _GA10/_GA11)
 static int se_map_pass(walt_index* idx, const IndexView& view, const SeWorkspace& w, const uint64_t* offsets, uint32_t n,
                        int nw, uint32_t sb, uint32_t max_mm, uint32_t b, BestMatch* out, hipStream_t stream) {
-  return dispatch_nw(nw, [&](auto NW) {
-    return launch_map_se<decltype(NW)::value>(idx, view, w.codes2, offsets, w.err, n, sb, max_mm, b, out, w.shards, w.defer_count,
-                                              w.defer_list, w.stride, w.heavy_area, w.carry_area, w.share, stream);
-  });
+  const SePass p = {idx, view, w, offsets, n, sb, max_mm, b, out, stream};
+  return dispatch_nw(nw, [&](auto NW) { return launch_map_se<decltype(NW)::value>(p); });
 }
 
 // What map_se_device and map_se_rpbat_device (rp) share up to their first mapping pass: the batch-size and length
@@ -2681,10 +2647,7 @@ int map_se_rpbat_device(walt_index* idx, const void* d_bases, const void* d_offs
   if (rc) return rc;
   // From here the index's side streams may still run the first pass's work on this workspace: an error return waits
   // for them first.
-  auto unwind = [&]() {
-    if (idx->se_pipe) (void)hipStreamSynchronize(idx->se_pipe);
-    if (idx->se_side) (void)hipStreamSynchronize(idx->se_side);
-  };
+  const auto unwind = [&] { se_unwind(idx); };
   // Statistics: the shards are reduced once per pass.  The first pass adds all four counters (and clears the shards);
   // the second adds probes / candidates / big_regions only, so too_short is counted once, as a single-conversion call
   // counts it (a read is short under both conversions).

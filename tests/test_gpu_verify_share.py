@@ -120,9 +120,11 @@ def batch_of(pool, m):
 LAST = {}  # the last device_run's control words
 
 
-def device_run(wa, idx, reads, max_mm):
+def device_run(wa, idx, reads, max_mm, pat=3, ag=False, b=5000, rpbat=False):
     """one call of the device form -> (records as raw bytes, statistics, control word 7 summed over (chunk, round),
-    [records of all items, records of all units] summed)"""
+    [records of all items, records of all units] summed).  pat: the seed pattern of the library idx was opened with --
+    the staged pass has 8 * pat (chunk, round) pairs (map_se.hip kShareRounds); ag: the G->A strands; rpbat:
+    map_se_rpbat_batch_device, the conversion bytes behind the records, the control words those of its second pass"""
     import torch
     dev = torch.device("cuda:0")
     bases, offsets = wa.pack_reads(reads)
@@ -131,24 +133,32 @@ def device_run(wa, idx, reads, max_mm):
     d_bases = torch.from_numpy(bases).to(dev)
     d_off = torch.from_numpy(offsets.astype(np.int64)).to(dev)
     d_out = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    d_conv = torch.zeros(n, dtype=torch.uint8, device=dev)
     d_stats = torch.zeros(4, dtype=torch.int64, device=dev)
-    ws = wa.lib().walt_se_workspace_bytes(n, max_len)
+    se_ws = wa.lib(pat).walt_se_workspace_bytes(n, max_len)  # (a random-PBAT call lays the same workspace out in front of its second record array)
+    ws = wa.lib(pat).walt_se_rpbat_workspace_bytes(n, max_len) if rpbat else se_ws
     d_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
-    idx.map_se_batch_device(d_bases.data_ptr(), d_off.data_ptr(), n, max_len, d_out.data_ptr(), d_stats.data_ptr(), d_ws.data_ptr(), ws,
-                            stream=stream, ag_wildcard=False, max_mismatches=max_mm, b=5000)
+    if rpbat:
+        idx.map_se_rpbat_batch_device(d_bases.data_ptr(), d_off.data_ptr(), n, max_len, d_out.data_ptr(), d_conv.data_ptr(), d_stats.data_ptr(),
+                                      d_ws.data_ptr(), ws, stream=stream, max_mismatches=max_mm, b=b)
+    else:
+        idx.map_se_batch_device(d_bases.data_ptr(), d_off.data_ptr(), n, max_len, d_out.data_ptr(), d_stats.data_ptr(), d_ws.data_ptr(), ws,
+                                stream=stream, ag_wildcard=ag, max_mismatches=max_mm, b=b)
     torch.cuda.synchronize()
     wa.Index.check_batch(d_ws.data_ptr(), stream)
+    rounds = 8 * pat
     stride = (n + 63) // 64 * 64  # (bench.py's offset of the staged pass's control words)
     h_off = (64 * 4 + 256 * 16 * 8 + 3 * stride * 4 + ((n * max_len) // 16 + 10) * 4 + 15) // 16 * 16
-    hctl = d_ws[h_off:h_off + 4 * 64 * 3].view(torch.int32).cpu().numpy().reshape(8, 3, 8)
+    hctl = d_ws[h_off:h_off + 4 * 8 * rounds].view(torch.int32).cpu().numpy().reshape(8, pat, 8)
     LAST.update(hctl=hctl.copy(), dense=int(hctl[:, :, 0].sum()), giants=int(hctl[:, :, 5].sum()))
-    end = ws // 16 * 16
-    recs = d_ws[end - 8 * 3 * 16:end].view(torch.int64).cpu().numpy().reshape(24, 2).sum(axis=0)
-    print("%d reads, se_verify_share = %d: dense items %d, giants %d, gather items %d, rode along %d, records of items / of units %s" % (
-        n, idx.get_option("se_verify_share"), int(hctl[:, :, 0].sum()), int(hctl[:, :, 5].sum()), int(hctl[:, :, 1].sum()), int(hctl[:, :, 7].sum()),
-        recs.tolist()))
-    return d_out.cpu().numpy().tobytes(), d_stats.cpu().numpy().tolist(), int(hctl[:, :, 7].sum()), recs.tolist()
+    end = se_ws // 16 * 16
+    recs = d_ws[end - rounds * 16:end].view(torch.int64).cpu().numpy().reshape(rounds, 2).sum(axis=0)
+    print("%d reads of up to %d bases%s, se_verify_share = %d: dense items %d, giants %d, gather items %d, rode along %d, records of items / of units %s" % (
+        n, max_len, ", random PBAT" if rpbat else ", G->A" if ag else "", idx.get_option("se_verify_share"), int(hctl[:, :, 0].sum()),
+        int(hctl[:, :, 5].sum()), int(hctl[:, :, 1].sum()), int(hctl[:, :, 7].sum()), recs.tolist()))
+    out = d_out.cpu().numpy().tobytes() + (d_conv.cpu().numpy().tobytes() if rpbat else b"")
+    return out, d_stats.cpu().numpy().tolist(), int(hctl[:, :, 7].sum()), recs.tolist()
 
 
 @pytest.mark.parametrize("m", SHARED)

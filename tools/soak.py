@@ -81,6 +81,32 @@ def main():
         sys.exit(1)
 
 
+def rode_along(walt_amd, idx, reads, ag, m, b, pattern):
+    """Items of the grouped dense verifier that rode along in a unit (map_se.hip k_se_share_cut: control word 7 of every
+    (chunk, round) of the staged pass, summed): one more call of the batch through the device form, whose workspace the
+    caller owns and can read.  The records are not compared again."""
+    import torch
+    dev = torch.device("cuda:0")
+    bases, offsets = walt_amd.pack_reads(reads)
+    n = offsets.size - 1
+    max_len = int((offsets[1:] - offsets[:-1]).max())
+    d_bases = torch.from_numpy(bases).to(dev)
+    d_off = torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    d_out = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    d_stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    ws = walt_amd.lib(pattern).walt_se_workspace_bytes(n, max_len)
+    d_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    idx.map_se_batch_device(d_bases.data_ptr(), d_off.data_ptr(), n, max_len, d_out.data_ptr(), d_stats.data_ptr(), d_ws.data_ptr(), ws,
+                            stream=stream, ag_wildcard=ag, max_mismatches=m, b=b)
+    torch.cuda.synchronize()
+    walt_amd.Index.check_batch(d_ws.data_ptr(), stream)
+    stride = (n + 63) // 64 * 64  # (bench.py's offset of the staged pass's control words; 8 words per (chunk, round), 8 x pattern of them)
+    h_off = (64 * 4 + 256 * 16 * 8 + 3 * stride * 4 + ((n * max_len) // 16 + 10) * 4 + 15) // 16 * 16
+    hctl = d_ws[h_off:h_off + 4 * 64 * pattern].view(torch.int32).cpu().numpy().reshape(8 * pattern, 8)
+    return int(hctl[:, 7].sum())
+
+
 def run_soak(seconds, seed0=1, pattern=3, max_genomes=None):
     """Genomes seed0, seed0 + 1, ... until `seconds` are used up or `max_genomes` are done; returns the summary line,
     raises SoakMismatch at the first difference (tests/test_gpu_soak.py runs a fixed set of seeds this way)."""
@@ -128,7 +154,9 @@ def run_soak(seconds, seed0=1, pattern=3, max_genomes=None):
                 idx.set_option("pe_lit_fuse", 0)
             # the dense items grouped by region (default) or verified one by one (map_se.hip k_se_verify_shared); a
             # generator of its own again
-            idx.set_option("se_verify_share", random.Random(seed * 104729 + 7).choice([1, 1, 0]))
+            share = random.Random(seed * 104729 + 7).choice([1, 1, 0])
+            idx.set_option("se_verify_share", share)
+            rode = 0
             lengths = [lo + 2, lo + 3, 40, 45, 60, 100, 100, 100, 131, 140, min(150, hi), min(200, hi), hi]
             # the kernels are instantiated per read-length class (up to 112, 128, 160 ... bases: the batch's longest read
             # selects the instance): some genomes get batches that stop at 112 or 128 bases
@@ -147,6 +175,10 @@ def run_soak(seconds, seed0=1, pattern=3, max_genomes=None):
                         bad = int(np.nonzero(got[f] != want[f])[0][0])
                         raise SoakMismatch("MISMATCH seed %d %s field %s read %d (%s) D=%d m=%d b=%d" % (seed, conv, f, bad, reads[bad], D, m, b))
                 reads_total += len(reads)
+                if share == 1:
+                    rode += rode_along(walt_amd, idx, reads, ag, m, b, args.pattern)
+            if share == 1:  # whether grouping happened at all on this genome (none on the routes of reads above 128 bases)
+                print("soak: seed %d, se_verify_share = 1: %d items rode along in a unit (%s)" % (seed, rode, cls), file=sys.stderr, flush=True)
             s1 = sample(rng, seqs, 500, "CT", lengths, refio)
             s2 = sample(rng, seqs, 500, "GA", lengths, refio)
             L = rng.choice([200, 1000])

@@ -468,6 +468,41 @@ int walt_pileup_levels_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, 
 int walt_pileup_read(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint32_t* meth, uint32_t* unmeth);
 int walt_pileup_add(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, const uint32_t* meth, const uint32_t* unmeth);
 
+/* ---- methylation levels per region: the summary of many ranges of a pile-up in one call ------------------------
+ * The reference has no such mode (MethPipe users run roimethstat over the counts file, Bismark users methylKit's
+ * tiling over the coverage file; neither has the denominators without the FASTA); the contract is defined here.
+ *
+ * Equivalence.  out[i] equals what walt_pileup_levels(p, regions[i].lo, regions[i].hi, ..) returns in the fields of
+ * the same name: rows 0..3 are the C/G positions of the range by the extraction's class, uncovered ones included in
+ * `sites`; row 4 is the CpG pairs whose C lies in the range -- the G is read wherever it lies, and a C that ends a
+ * chromosome in front of a G that starts the next is no pair; level_sum is floor((meth << 30) / (meth + unmeth))
+ * summed over covered sites.  max_depth, the histogram and offref are left out on purpose: 160 bytes per region keep
+ * 30 million tiles at 4.8 GB.  sites and covered are 32-bit: a region holds fewer than 2^32 positions.
+ *
+ * Regions are independent: in any order, overlapping, nested, repeated, empty (lo == hi: all zeros), and across
+ * chromosome starts (the class of a position does not depend on the range).  All fields are integers and all folds
+ * commutative, so the launch shape (the test hook pile_extract_blocks) cannot change a bit.
+ *
+ * Errors.  WALT_EINVAL for a null pile-up, null `regions` or `out` with n > 0, and any lo > hi or hi > genome_len: the
+ * host form names the first such index and writes nothing.  The device form cannot see the regions before it
+ * returns: there such a region yields an all-zero record and the others are as ever.  The device form also refuses
+ * n above WALT_REGIONS_MAX (2^22) per call and d_regions, d_out or d_work that are null or not 8-byte aligned.
+ * n == 0 succeeds and does nothing.  The host form takes any n (it runs windows of WALT_REGIONS_MAX itself with a
+ * workspace of its own, which it frees) and waits for all work on the device first; the device form is asynchronous
+ * on `stream`: d_regions n walt_region, d_out n walt_region_levels, d_work walt_pileup_regions_workspace_bytes(n)
+ * bytes, all in HBM and the caller's.  A regions call counts as an extraction under "one at a time per pile-up";
+ * walt_pileup_device_bytes is as before. */
+#define WALT_REGIONS_MAX 4194304u
+typedef struct { uint32_t lo, hi; } walt_region;      /* forward positions [lo, hi), 8 bytes */
+typedef struct {                                       /* 32 bytes */
+  uint32_t sites, covered;    /* as walt_level_row's */
+  uint64_t meth, unmeth, level_sum;
+} walt_region_row;
+typedef struct { walt_region_row row[5]; } walt_region_levels;   /* 160 bytes; rows as walt_levels */
+uint64_t walt_pileup_regions_workspace_bytes(uint32_t n);
+int walt_pileup_regions(walt_pileup* p, const walt_region* regions, uint64_t n, walt_region_levels* out);
+int walt_pileup_regions_device(walt_pileup* p, const void* d_regions, uint32_t n, void* d_out, void* d_work, void* stream);
+
 /* ---- duplicates: PCR duplicates marked from the mapped records, and kept out of the methylation counts ---------
  * The reference has no such mode (its users sort the mapped records and run a second program, MethPipe's
  * duplicate-remover, before they count; Bismark users run deduplicate_bismark); the contract is defined here.  It needs

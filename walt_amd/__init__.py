@@ -92,6 +92,12 @@ level_row_dtype = np.dtype([("sites", "<u8"), ("covered", "<u8"), ("meth", "<u8"
 levels_dtype = np.dtype([("row", level_row_dtype, (5,)), ("offref", "<u8", (2,))])
 LEVEL_ROWS = METH_CONTEXTS + ("CpG_symmetric",)
 assert level_row_dtype.itemsize == 128 and levels_dtype.itemsize == 656
+# walt_region / walt_region_levels (include/walt_amd.h, "methylation levels per region"); rows as levels_dtype's
+region_dtype = np.dtype([("lo", "<u4"), ("hi", "<u4")])
+region_row_dtype = np.dtype([("sites", "<u4"), ("covered", "<u4"), ("meth", "<u8"), ("unmeth", "<u8"), ("level_sum", "<u8")])
+region_levels_dtype = np.dtype([("row", region_row_dtype, (5,))])
+REGIONS_MAX = 1 << 22  # regions of one Pileup.regions_device call at most (WALT_REGIONS_MAX)
+assert region_dtype.itemsize == 8 and region_row_dtype.itemsize == 32 and region_levels_dtype.itemsize == 160
 # walt_nonconv_tally / walt_nonconv_rule (include/walt_amd.h, "non-converted reads")
 nonconv_tally_dtype = np.dtype([("meth", "<u2"), ("total", "<u2"), ("run", "<u2"), ("reserved", "<u2")])
 nonconv_rule_dtype = np.dtype([("min_meth", "<u4"), ("min_run", "<u4"), ("min_percent", "<u4"), ("min_total", "<u4")])
@@ -229,6 +235,10 @@ def lib(pattern=None):
     L.walt_pileup_levels_device.argtypes = [vp, u32, u32, vp, vp]
     L.walt_pileup_read.argtypes = [vp, u32, u32, vp, vp]
     L.walt_pileup_add.argtypes = [vp, u32, u32, vp, vp]
+    L.walt_pileup_regions_workspace_bytes.argtypes = [u32]
+    L.walt_pileup_regions_workspace_bytes.restype = u64
+    L.walt_pileup_regions.argtypes = [vp, vp, u64, vp]
+    L.walt_pileup_regions_device.argtypes = [vp, vp, u32, vp, vp, vp]
     L.walt_dedup_create.argtypes = [ci, u64, c.POINTER(vp)]
     L.walt_dedup_destroy.argtypes = [vp]
     L.walt_dedup_destroy.restype = None
@@ -415,6 +425,11 @@ def pack_reads(seqs):
 def se_rpbat_workspace_bytes(n, max_read_len):
     """Bytes of the workspace Index.map_se_rpbat_batch_device needs (walt_se_rpbat_workspace_bytes)."""
     return lib().walt_se_rpbat_workspace_bytes(int(n), int(max_read_len))
+
+
+def regions_workspace_bytes(n):
+    """Bytes of the workspace Pileup.regions_device needs for n regions (walt_pileup_regions_workspace_bytes)."""
+    return lib().walt_pileup_regions_workspace_bytes(int(n))
 
 
 def pe_rpbat_workspace_bytes(n, max_read_len, top_k):
@@ -984,6 +999,30 @@ class Pileup:
     def levels_device(self, pos_lo, pos_hi, d_out, stream=0):
         """Device-pointer form (walt_pileup_levels_device): 656 bytes at d_out; asynchronous."""
         self._index._ck(self._L.walt_pileup_levels_device(self._h, int(pos_lo), int(pos_hi), d_out, stream))
+
+    def regions(self, regions):
+        """The summaries of many ranges in one call (walt_pileup_regions): `regions` is an (n, 2) integer array of
+        [lo, hi) or a region_dtype array; returns n region_levels_dtype records, record i equal to levels(lo, hi) of
+        region i in the fields it has."""
+        if isinstance(regions, np.ndarray) and regions.dtype == region_dtype:
+            regs = np.ascontiguousarray(regions).reshape(-1)
+        else:
+            arr = np.asarray(regions)
+            if arr.size == 0:
+                arr = np.zeros((0, 2), dtype=np.uint32)
+            if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype.kind not in "iu":
+                raise ValueError("Pileup.regions wants an (n, 2) integer array or a region_dtype array")
+            if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 0xFFFFFFFF):
+                raise ValueError("Pileup.regions: positions are 32-bit and not negative")
+            regs = np.ascontiguousarray(arr.astype(np.uint32)).view(region_dtype).reshape(-1)
+        out = np.zeros(regs.size, dtype=region_levels_dtype)
+        self._index._ck(self._L.walt_pileup_regions(self._h, _ptr(regs), regs.size, _ptr(out)))
+        return out
+
+    def regions_device(self, d_regions, n, d_out, d_work, stream=0):
+        """Device-pointer form (walt_pileup_regions_device): n region_dtype records at d_regions, 160 * n bytes at d_out,
+        regions_workspace_bytes(n) bytes at d_work; asynchronous.  A region outside the genome gives a zero record."""
+        self._index._ck(self._L.walt_pileup_regions_device(self._h, d_regions, int(n), d_out, d_work, stream))
 
     def read(self, pos_lo=0, pos_hi=None):
         """(meth, unmeth) uint32 arrays: the raw counters of [pos_lo, pos_hi) (walt_pileup_read)."""

@@ -507,6 +507,141 @@ inline void put_levels_block(Sink& out, const walt_levels& lv) {
   }
 }
 
+// ---------------------------------------------------------------- <out>.regions (bin/walt -MR)
+// The BED file of -MR (include/walt_amd.h, "methylation levels per region"): `chrom start end [name ...]`, 0-based and
+// half-open, columns separated by tabs or blanks.  Empty lines and lines that start with '#', "track" or "browser"
+// are skipped; a missing name is "."; further columns are ignored (a strand column restricts nothing).  Lines end in
+// LF or CRLF; the last one needs neither.
+struct BedRegion {
+  std::string chrom, name;
+  uint64_t start = 0, end = 0;
+  uint32_t line = 0;  // 1-based line of the file
+};
+// digits only, below 2^63
+inline bool parse_bed_number(const char* p, size_t len, uint64_t& out) {
+  if (!len || len > 18) return false;
+  uint64_t v = 0;
+  for (size_t i = 0; i < len; ++i) {
+    if (p[i] < '0' || p[i] > '9') return false;
+    v = v * 10 + (uint64_t)(p[i] - '0');
+  }
+  out = v;
+  return true;
+}
+// The regions of a BED text in the file's order.  false: `err` is "<file>:<line>: <what>" (line 0 for a text without
+// any region).
+inline bool parse_bed_text(const char* text, size_t len, const std::string& file, std::vector<BedRegion>& out, std::string& err) {
+  out.clear();
+  uint32_t line = 0;
+  auto bad = [&](const std::string& what) { err = file + ":" + std::to_string(line) + ": " + what; out.clear(); return false; };
+  for (size_t at = 0; at < len;) {
+    size_t end = at;
+    while (end < len && text[end] != '\n') ++end;
+    size_t stop = end;
+    if (stop > at && text[stop - 1] == '\r') --stop;
+    const char* p = text + at;
+    const size_t n = stop - at;
+    at = end + 1;
+    ++line;
+    auto blank = [](char c) { return c == ' ' || c == '\t'; };
+    auto starts = [&](const char* w) { const size_t k = strlen(w); return n >= k && !memcmp(p, w, k) && (n == k || blank(p[k])); };
+    size_t i = 0;
+    while (i < n && blank(p[i])) ++i;
+    if (i == n || p[0] == '#' || starts("track") || starts("browser")) continue;
+    View col[4];
+    int n_col = 0;
+    while (i < n && n_col < 4) {
+      const size_t c0 = i;
+      while (i < n && !blank(p[i])) ++i;
+      col[n_col].p = p + c0; col[n_col].len = (uint32_t)(i - c0);
+      ++n_col;
+      while (i < n && blank(p[i])) ++i;
+    }
+    if (n_col < 3) return bad("a region needs three columns (chrom start end), this line has " + std::to_string(n_col));
+    BedRegion r;
+    if (!parse_bed_number(col[1].p, col[1].len, r.start)) return bad("start '" + std::string(col[1].p, col[1].len) + "' is not a number");
+    if (!parse_bed_number(col[2].p, col[2].len, r.end)) return bad("end '" + std::string(col[2].p, col[2].len) + "' is not a number");
+    if (r.start > r.end) return bad("start " + std::to_string(r.start) + " lies behind end " + std::to_string(r.end));
+    r.chrom.assign(col[0].p, col[0].len);
+    r.name = n_col > 3 ? std::string(col[3].p, col[3].len) : std::string(".");
+    r.line = line;
+    out.push_back(r);
+  }
+  line = 0;
+  if (out.empty()) return bad("the file holds no region");
+  return true;
+}
+inline bool read_bed_file(const std::string& file, std::vector<BedRegion>& out, std::string& err) {
+  FILE* f = fopen(file.c_str(), "rb");
+  if (!f) { err = file + ":0: cannot open the regions file"; return false; }
+  std::string text;
+  char buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+  const bool failed = ferror(f) != 0;
+  fclose(f);
+  if (failed) { err = file + ":0: cannot read the regions file"; return false; }
+  return parse_bed_text(text.data(), text.size(), file, out, err);
+}
+// The forward ranges of the regions in a genome of n_chrom chromosomes (name[c], start[c] .. start[c + 1]).  A region
+// on a chromosome the genome does not have becomes the empty range [0, 0) and is counted: it keeps its output line.
+// false: a region ends beyond its chromosome, `err` as above.
+inline bool resolve_bed(const std::vector<BedRegion>& bed, const std::vector<std::string>& name, const std::vector<uint32_t>& start,
+                        const std::string& file, std::vector<walt_region>& regions, uint64_t& n_unknown, std::string& err) {
+  std::vector<std::pair<std::string, uint32_t> > by_name;
+  for (uint32_t c = 0; c < (uint32_t)name.size(); ++c) by_name.push_back(std::make_pair(name[c], c));
+  std::sort(by_name.begin(), by_name.end());
+  regions.assign(bed.size(), walt_region{0u, 0u});
+  n_unknown = 0;
+  for (size_t i = 0; i < bed.size(); ++i) {
+    const BedRegion& r = bed[i];
+    auto it = std::lower_bound(by_name.begin(), by_name.end(), std::make_pair(r.chrom, 0u));
+    if (it == by_name.end() || it->first != r.chrom) { ++n_unknown; continue; }
+    const uint32_t c = it->second;
+    const uint64_t length = (uint64_t)start[c + 1] - start[c];
+    if (r.end > length) {
+      err = file + ":" + std::to_string(r.line) + ": end " + std::to_string(r.end) + " lies beyond the " + std::to_string(length) +
+            " bases of " + r.chrom;
+      return false;
+    }
+    regions[i].lo = start[c] + (uint32_t)r.start;
+    regions[i].hi = start[c] + (uint32_t)r.end;
+  }
+  return true;
+}
+// One read file's block: a header line, then one line per region in the file's order, tab-separated:
+//   chrom start end name, then for CpG, CHG, CHH, unknown and CpG_symmetric (rows 0..4):
+//   <ctx>_sites <ctx>_covered <ctx>_meth <ctx>_unmeth <ctx>_mean_meth <ctx>_weighted_meth
+// mean_meth = level_sum / (covered * 2^30) and weighted_meth = meth / (meth + unmeth) as put_levels_block computes
+// them: %.6f, or NA on a zero denominator (every ratio of a region on an unknown chromosome).
+inline void put_regions_block(Sink& out, const std::vector<BedRegion>& bed, const walt_region_levels* lv) {
+  static const char* ctx[5] = {"CpG", "CHG", "CHH", "unknown", "CpG_symmetric"};
+  static const char* col[6] = {"sites", "covered", "meth", "unmeth", "mean_meth", "weighted_meth"};
+  out.lit("chrom\tstart\tend\tname");
+  for (int r = 0; r < 5; ++r)
+    for (int k = 0; k < 6; ++k) { out.ch('\t'); out.lit(ctx[r]); out.ch('_'); out.lit(col[k]); }
+  out.ch('\n');
+  char num[192];
+  auto ratio = [&](double a, double b) {
+    if (b != 0.0) snprintf(num, sizeof num, "\t%.6f", a / b); else snprintf(num, sizeof num, "\tNA");
+    out.lit(num);
+  };
+  for (size_t i = 0; i < bed.size(); ++i) {
+    out.put(bed[i].chrom);
+    snprintf(num, sizeof num, "\t%llu\t%llu\t", (unsigned long long)bed[i].start, (unsigned long long)bed[i].end);
+    out.lit(num);
+    out.put(bed[i].name);
+    for (int r = 0; r < 5; ++r) {
+      const walt_region_row& x = lv[i].row[r];
+      snprintf(num, sizeof num, "\t%u\t%u\t%llu\t%llu", x.sites, x.covered, (unsigned long long)x.meth, (unsigned long long)x.unmeth);
+      out.lit(num);
+      ratio((double)x.level_sum, (double)x.covered * 1073741824.0);
+      ratio((double)x.meth, (double)(x.meth + x.unmeth));
+    }
+    out.ch('\n');
+  }
+}
+
 // ---------------------------------------------------------------- ignored read ends (bin/walt -I5 -I3 -I5R2 -I3R2)
 // The value of one of the four options (include/walt_amd.h, "ignored read ends"): a decimal integer from 0 to 1024
 // (no read is longer), nothing in front of or behind the digits.

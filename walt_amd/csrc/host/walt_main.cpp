@@ -53,8 +53,10 @@ struct Options {
   bool meth = false;  // -M: per-read methylation calls (walt_meth_call_batch): XM:Z: on SAM lines, <out>.methstats
   bool methcounts = false;  // -MC: per-cytosine pile-up on the device (walt_meth_pileup_batch): <out>.methcounts
   bool levels = false;  // -ML: genome-wide methylation levels of the pile-up (walt_pileup_levels): <out>.levels
-  bool piling() const { return methcounts || levels; }               // the run keeps pile-ups
-  bool consumer() const { return meth || methcounts || mbias || levels; }  // something takes the methylation calls
+  string regions_file;  // -MR: methylation levels per region of a BED file (walt_pileup_regions): <out>.regions
+  bool regions() const { return !regions_file.empty(); }
+  bool piling() const { return methcounts || levels || regions(); }  // the run keeps pile-ups
+  bool consumer() const { return meth || methcounts || mbias || levels || regions(); }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
@@ -108,6 +110,10 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "M", "meth") || a == "--meth-calls") o.meth = true;  // extension: methylation calls per read
     else if (is_opt(a, "MC", "methcounts") || a == "--meth-counts") o.methcounts = true;  // extension: methylation counts per cytosine
     else if (is_opt(a, "ML", "levels") || a == "--meth-levels") o.levels = true;  // extension: genome-wide methylation levels
+    else if (is_opt(a, "MR", "regions") || a == "--meth-regions") {  // extension: methylation levels per region of a BED file
+      o.regions_file = val();
+      if (o.regions_file.empty()) die(a + " (methylation levels per region) wants the name of a BED file");
+    }
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
@@ -160,15 +166,15 @@ static Options parse(int argc, const char** argv) {
   if (o.no_overlap && !o.se_csv.empty())
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
   if (o.no_overlap && !o.consumer())
-    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML) there is nothing for it to do");
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML, -MR) there is nothing for it to do");
   if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.consumer())
-    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB or -ML there is nothing for them to do");
+    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB, -ML or -MR there is nothing for them to do");
   if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
     die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
   if (o.filter_given[3] && !o.filter_given[2])
     die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
   if ((o.filtering() || o.filter_given[3]) && !o.consumer())
-    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB or -ML there is nothing for them to do");
+    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML or -MR there is nothing for them to do");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -429,21 +435,23 @@ static void write_methcounts(const string& out_file, PileSet& ps, const GenomeIn
 
 // ---------------------------------------------------------------- -ML: genome-wide methylation levels
 // Maxima and covered sites are not additive across devices: the other devices' counters are folded into the first
-// device's pile-up, window by window, and one summary runs there over the whole genome.
+// device's pile-up, window by window (once per read file, shared with -MR), and one summary runs there over the whole
+// genome.
+static void fold_pileups(PileSet& ps, uint64_t genome_len) {
+  if (ps.p.size() < 2) return;
+  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+  vector<uint32_t> m((size_t)window), u((size_t)window);
+  for (size_t d = 1; d < ps.p.size(); ++d)
+    for (uint64_t lo = 0; lo < genome_len; lo += window) {
+      const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
+      check(walt_pileup_read(ps.p[d], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
+      check(walt_pileup_add(ps.p[0], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
+    }
+}
+// (the counters are folded by now)
 static void write_levels(const string& out_file, PileSet& ps, const GenomeInfo& g, bool verbose) {
-  const uint64_t genome_len = g.start.back();
-  if (ps.p.size() > 1) {
-    const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
-    vector<uint32_t> m((size_t)window), u((size_t)window);
-    for (size_t d = 1; d < ps.p.size(); ++d)
-      for (uint64_t lo = 0; lo < genome_len; lo += window) {
-        const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
-        check(walt_pileup_read(ps.p[d], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
-        check(walt_pileup_add(ps.p[0], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
-      }
-  }
   walt_levels lv;
-  check(walt_pileup_levels(ps.p[0], 0, (uint32_t)genome_len, &lv));
+  check(walt_pileup_levels(ps.p[0], 0, (uint32_t)g.start.back(), &lv));
   Sink out;
   hostio::put_levels_block(out, lv);
   OutFile mf;
@@ -453,10 +461,50 @@ static void write_levels(const string& out_file, PileSet& ps, const GenomeInfo& 
   if (verbose) fwrite(out.p, 1, out.n, stderr);
 }
 
-// the end of a read file: <out>.methcounts (-MC) as ever, then <out>.levels (-ML), then the counters cleared
+// ---------------------------------------------------------------- -MR: methylation levels per region
+// The BED file is read once, before anything is opened; its regions become forward ranges with the first index that is
+// opened (every read file maps against the same one).  At the end of a read file one call on the first device's
+// folded pile-up gives every region's record, and one block goes to <out>.regions.
+struct RegionSet {
+  string file;
+  vector<hostio::BedRegion> bed;
+  vector<walt_region> regions;
+  bool resolved = false;
+  void read(const string& f) {
+    file = f;
+    string err;
+    if (!hostio::read_bed_file(f, bed, err)) die("-MR (methylation levels per region): " + err);
+  }
+  void resolve(const GenomeInfo& g, bool verbose) {
+    if (resolved) return;
+    string err;
+    uint64_t n_unknown = 0;
+    if (!hostio::resolve_bed(bed, g.name, g.start, file, regions, n_unknown, err)) die("-MR (methylation levels per region): " + err);
+    resolved = true;
+    if (verbose)
+      fprintf(stderr, "[walt_amd regions: %zu regions of %s, %llu on chromosomes the index does not have]\n", bed.size(), file.c_str(),
+              (unsigned long long)n_unknown);
+  }
+};
+static RegionSet g_regions;
+static void write_regions(const string& out_file, PileSet& ps) {
+  vector<walt_region_levels> lv(g_regions.regions.size());
+  check(walt_pileup_regions(ps.p[0], g_regions.regions.data(), g_regions.regions.size(), lv.data()));
+  Sink out;
+  hostio::put_regions_block(out, g_regions.bed, lv.data());
+  OutFile mf;
+  if (!mf.open_append(out_file + ".regions")) die("cannot open input file " + out_file + ".regions");
+  mf.write(out.p, out.n);
+  mf.close();
+}
+
+// the end of a read file: <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the
+// counters cleared
 static void end_of_file_pileups(const Options& o, const string& out_file, PileSet& ps, const GenomeInfo& g) {
   if (o.methcounts) write_methcounts(out_file, ps, g, o.verbose);
+  if (o.levels || o.regions()) fold_pileups(ps, g.start.back());
   if (o.levels) write_levels(out_file, ps, g, o.verbose);
+  if (o.regions()) write_regions(out_file, ps);
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
 }
 
@@ -740,6 +788,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
   flt.open(o);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
+  if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
   OutFile fout;
   if (!fout.open_append(out_file)) die("cannot open input file " + out_file);
   SideFiles side;
@@ -1064,6 +1113,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   flt.open(o);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
+  if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
   hostio::FastqReader rd[2];
   rd[0].open(f1, T);
   rd[1].open(f2, T);
@@ -1351,10 +1401,11 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
+    if (o.regions()) g_regions.read(o.regions_file);  // refused before anything is opened or truncated
     setenv("GPU_MAX_HW_QUEUES", "8", 0);  // paired-end keeps several streams busy; read by the HIP runtime at start-up
     static const char* sfx[5] = {"", "_CT00", "_CT01", "_GA10", "_GA11"};  // validate_index_file, walt.cpp:67-85
     for (const char* s : sfx) if (!exists(o.index_file + s)) die("index file missing: " + o.index_file + s);
@@ -1370,6 +1421,7 @@ int main(int argc, const char** argv) {
     if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
     if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
     if (o.levels) for (auto& f : outs) { std::ofstream levels(f + ".levels"); }
+    if (o.regions()) for (auto& f : outs) { std::ofstream regions(f + ".regions"); }
     if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }

@@ -8,6 +8,7 @@
 #include "map_common.h"
 #include "levels_core.h"
 #include "pileup_core.h"
+#include "regions_core.h"
 
 namespace walt {
 
@@ -24,6 +25,10 @@ static_assert(kPileMaxBlocks + 1 <= kPileLevels && kPileLevels + kLevelWords <= 
 static_assert(sizeof(walt_level_row) == 8 * kLevelRowWords && sizeof(walt_levels) == 8 * kLevelWords, "walt_levels is 656 bytes");
 static_assert(kLevelWords <= kBlock && kLevelRows * kLevelBins <= kBlock, "one thread per word of a block's summary");
 static_assert(sizeof(walt_meth_site) == 16, "walt_meth_site is 16 bytes");
+static_assert(sizeof(walt_region) == 8 && sizeof(walt_region_row) == 32 && sizeof(walt_region_levels) == 32 * kLevelRows,
+              "walt_region is 8 bytes, walt_region_levels 160");
+static_assert(kRegionUnit == kPileTile, "a unit of a region is a tile of the extraction");
+static_assert((WALT_REGIONS_MAX + kBlock - 1) / kBlock <= kPileMaxBlocks, "the table holds the sums of a regions call");
 
 struct PileArgs {
   const uint32_t* plane[2];
@@ -277,6 +282,174 @@ __global__ __launch_bounds__(kBlock) void k_pile_levels(const PileArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- levels per region (regions_core.h)
+struct RegionArgs {
+  const uint32_t* plane[2];
+  const uint32_t* ref;
+  uint32_t ref_last;
+  const uint32_t* start_index;
+  uint32_t n_chrom, genome_len;
+  const walt_region* regions;  // n of them
+  uint32_t n;
+  unsigned long long* prefix;  // n + 1: the exclusive prefix of the regions' units, the total behind it
+  unsigned long long* table;   // the pile-up's: sums of kBlock regions each, scanned by k_pile_scan
+  walt_region_levels* out;
+};
+
+__device__ __forceinline__ unsigned long long region_units_at(const RegionArgs& a, uint64_t i) {
+  if (i >= a.n) return 0ull;
+  const uint2 r = reinterpret_cast<const uint2*>(a.regions)[i];
+  return region_units(r.x, r.y, a.genome_len);
+}
+
+// scan, launch 1 of 3: units of kBlock neighbouring regions -> table[block]  (launch 2 is k_pile_scan over those sums)
+__global__ __launch_bounds__(kBlock) void k_region_sums(const RegionArgs a) {
+  __shared__ unsigned long long s_red[kBlock / 64];
+  unsigned long long v = region_units_at(a, (uint64_t)blockIdx.x * kBlock + threadIdx.x);
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_red[w];
+    a.table[blockIdx.x] = t;
+  }
+}
+
+// scan, launch 3 of 3: prefix[i] = the block's scanned sum + the units of the block's regions in front of i
+__global__ __launch_bounds__(kBlock) void k_region_apply(const RegionArgs a) {
+  __shared__ unsigned long long s_wave[kBlock / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long v = region_units_at(a, i);
+  unsigned long long incl = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long o = __shfl_up(incl, d);
+    incl += lane >= (uint32_t)d ? o : 0ull;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  unsigned long long before = a.table[blockIdx.x];
+  for (uint32_t w = 0; w < kBlock / 64; ++w) before += w < wave ? s_wave[w] : 0ull;
+  if (i < a.n) {
+    a.prefix[i] = before + incl - v;
+    if (i + 1 == a.n) a.prefix[a.n] = before + incl;
+  }
+}
+
+// One wavefront's sums of the units of one region: counts are uniform (ballots), sums per lane.
+struct RegionAcc {
+  uint32_t n_sites[kLevelRows], n_cov[kLevelRows];
+  unsigned long long sm[kLevelRows], su[kLevelRows], ls[kLevelRows];
+};
+__device__ __forceinline__ void region_acc_clear(RegionAcc& c) {
+#pragma unroll
+  for (uint32_t r = 0; r < kLevelRows; ++r) { c.n_sites[r] = c.n_cov[r] = 0u; c.sm[r] = c.su[r] = c.ls[r] = 0ull; }
+}
+// folds the lanes' sums and adds the wavefront's non-zero words into the region's record; a row no lane has a call in
+// is not folded at all (an uncovered row has only `sites`)
+__device__ __forceinline__ void region_acc_flush(RegionAcc& c, walt_region_levels* rec, uint32_t lane) {
+#pragma unroll
+  for (uint32_t r = 0; r < kLevelRows; ++r) {
+    walt_region_row* row = rec->row + r;
+    if (c.n_cov[r]) {  // (uniform)
+      for (int s = 32; s > 0; s >>= 1) {
+        c.sm[r] += __shfl_down(c.sm[r], s);
+        c.su[r] += __shfl_down(c.su[r], s);
+        c.ls[r] += __shfl_down(c.ls[r], s);
+      }
+    }
+    if (lane == 0) {
+      if (c.n_sites[r]) atomicAdd(&row->sites, c.n_sites[r]);
+      if (c.n_cov[r]) {
+        atomicAdd(&row->covered, c.n_cov[r]);
+        if (c.sm[r]) atomicAdd(reinterpret_cast<unsigned long long*>(&row->meth), c.sm[r]);
+        if (c.su[r]) atomicAdd(reinterpret_cast<unsigned long long*>(&row->unmeth), c.su[r]);
+        if (c.ls[r]) atomicAdd(reinterpret_cast<unsigned long long*>(&row->level_sum), c.ls[r]);
+      }
+    }
+  }
+  region_acc_clear(c);
+}
+
+// The regions' records (include/walt_amd.h, "methylation levels per region").  The call's units are numbered through
+// all its regions (prefix); a wavefront takes runs of neighbouring units by stride over a fixed grid -- the total is
+// read from device memory, no block waits for another -- and walks a unit as k_pile_levels walks a step: 64
+// neighbouring positions, the partner's counters from the next lane, the chromosome bounds kept while the wavefront
+// stays inside them.  A run finds its first region by one search and the following ones by looking at the next
+// prefix; the sums of a run's units of one region stay in registers and reach the record once.
+__global__ __launch_bounds__(kBlock) void k_pile_regions(const RegionArgs a) {
+  __shared__ uint32_t s_start[kLdsChroms + 1];
+  const ChromTab tab = chrom_tab_of(a.n_chrom);
+  chrom_tab_stage(s_start, a.start_index, tab);
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned long long total = a.prefix[a.n];
+  const unsigned long long n_waves = (unsigned long long)gridDim.x * (kBlock / 64);
+  const unsigned long long me = (unsigned long long)blockIdx.x * (kBlock / 64) + wave;
+  unsigned long long run = total / n_waves;  // runs as long as every wavefront still gets one
+  run = run < 1ull ? 1ull : run > kRegionRun ? (unsigned long long)kRegionRun : run;
+  RegionAcc acc;
+  region_acc_clear(acc);
+  uint32_t w_lo = 1, w_hi = 0;  // the chromosome the wavefront is in (none yet)
+  for (unsigned long long u0 = me * run; u0 < total; u0 += n_waves * run) {
+    const unsigned long long u_end = u0 + run < total ? u0 + run : total;
+    uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)region_of_unit(a.prefix, 0u, a.n, u0));
+    for (unsigned long long unit = u0; unit < u_end; ++unit) {
+      if (unit != u0) {
+        const uint32_t r1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)region_next(a.prefix, a.n, r, unit));
+        if (r1 != r) region_acc_flush(acc, a.out + r, lane);
+        r = r1;
+      }
+      const uint2 reg = reinterpret_cast<const uint2*>(a.regions)[r];
+      unsigned long long lo, hi;
+      region_unit_range(reg.x, reg.y, (uint32_t)(unit - a.prefix[r]), lo, hi);
+      for (unsigned long long wf = lo; wf < hi; wf += 64) {  // (uniform) the wavefront's first position of this step
+        const unsigned long long wl = wf + 63 < hi - 1 ? wf + 63 : hi - 1;
+        if (wf < w_lo || wf >= w_hi) {
+          chrom_bounds(s_start, a.start_index, tab, (uint32_t)wf, w_lo, w_hi);
+          w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_lo);
+          w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_hi);
+        }
+        const bool one_chrom = wl < w_hi;  // (uniform)
+        const unsigned long long f = wf + lane;
+        uint32_t m = 0, u = 0, cls = kLevelNone, c_hi = w_hi;
+        bool pair = false;
+        if (f < hi) {
+          m = a.plane[0][f]; u = a.plane[1][f];
+          uint32_t c_lo = w_lo;
+          if (!one_chrom) chrom_bounds(s_start, a.start_index, tab, (uint32_t)f, c_lo, c_hi);
+          const unsigned long long ext = meth_ref_ext(a.ref, (long long)f - 2, a.ref_last);
+          cls = levels_class(ext, (uint32_t)f, c_lo, c_hi);
+          pair = levels_pair(ext, (uint32_t)f, c_hi);
+        }
+        uint32_t m1 = __shfl_down(m, 1), u1 = __shfl_down(u, 1);
+        if (pair && (lane == 63 || f + 1 >= hi)) {  // (f + 1 < c_hi <= genome_len: inside the planes)
+          m1 = a.plane[0][f + 1]; u1 = a.plane[1][f + 1];
+        }
+        const bool cov = cls != kLevelNone && (m | u) != 0u;
+        const unsigned long long q = cov ? level_q30(m, u) : 0ull;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+          const bool is = cls == k;
+          acc.n_sites[k] += (uint32_t)__popcll(__ballot(is));
+          acc.n_cov[k] += (uint32_t)__popcll(__ballot(is && cov));
+          acc.sm[k] += is ? m : 0u;
+          acc.su[k] += is ? u : 0u;
+          acc.ls[k] += is ? q : 0ull;
+        }
+        const unsigned long long pm = pair ? (unsigned long long)m + m1 : 0ull, pu = pair ? (unsigned long long)u + u1 : 0ull;
+        acc.n_sites[kLevelPair] += (uint32_t)__popcll(__ballot(pair));
+        acc.n_cov[kLevelPair] += (uint32_t)__popcll(__ballot((pm | pu) != 0ull));
+        if (pm | pu) acc.ls[kLevelPair] += level_q30(pm, pu);
+        acc.sm[kLevelPair] += pm;
+        acc.su[kLevelPair] += pu;
+      }
+    }
+    region_acc_flush(acc, a.out + r, lane);
+  }
+}
+
 // counters of [lo, lo + n) += src[0 .. n) (walt_pileup_add; wraps as the counters do)
 __global__ __launch_bounds__(kBlock) void k_pile_window_add(uint32_t* plane, uint64_t lo, uint64_t n, const uint32_t* src) {
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -460,6 +633,87 @@ int walt_pileup_levels(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_le
   WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
   if ((rc = pile_levels_launch(p, pos_lo, pos_hi, nullptr, nullptr))) return rc;
   WALT_HIP(hipMemcpy(out, p->table + kPileLevels, sizeof(walt_levels), hipMemcpyDeviceToHost));
+  return WALT_OK;
+}
+
+uint64_t walt_pileup_regions_workspace_bytes(uint32_t n) { return 8ull * ((uint64_t)n + 1); }
+
+// the records zeroed, the three launches of the scan and the walk, on `stream`
+static int pile_regions_launch(walt_pileup* p, const void* d_regions, uint32_t n, void* d_out, void* d_work, hipStream_t stream) {
+  const walt_index* idx = p->idx;
+  RegionArgs a;
+  a.plane[0] = p->plane[0]; a.plane[1] = p->plane[1];
+  a.ref = idx->ref[0];
+  a.ref_last = (idx->head.genome_len + 15) / 16 + kRefPadWords - 1;
+  a.start_index = idx->view.start_index;
+  a.n_chrom = idx->view.n_chrom;
+  a.genome_len = idx->head.genome_len;
+  a.regions = static_cast<const walt_region*>(d_regions);
+  a.n = n;
+  a.prefix = static_cast<unsigned long long*>(d_work);
+  a.table = p->table;
+  a.out = static_cast<walt_region_levels*>(d_out);
+  PileArgs scan;
+  memset(&scan, 0, sizeof scan);
+  scan.table = p->table;
+  const uint32_t n_sums = (n + kBlock - 1) / kBlock;
+  const uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks : (uint64_t)idx->n_cu * 8;
+  const uint32_t n_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, kPileMaxBlocks));
+  WALT_HIP(hipMemsetAsync(d_out, 0, (uint64_t)n * sizeof(walt_region_levels), stream));
+  hipLaunchKernelGGL(k_region_sums, dim3(n_sums), dim3(kBlock), 0, stream, a);
+  hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, stream, scan, n_sums);
+  hipLaunchKernelGGL(k_region_apply, dim3(n_sums), dim3(kBlock), 0, stream, a);
+  hipLaunchKernelGGL(k_pile_regions, dim3(n_blocks), dim3(kBlock), 0, stream, a);
+  WALT_HIP(hipGetLastError());
+  return WALT_OK;
+}
+
+int walt_pileup_regions_device(walt_pileup* p, const void* d_regions, uint32_t n, void* d_out, void* d_work, void* stream) {
+  if (!p) return fail(WALT_EINVAL, "walt_pileup_regions_device: bad argument (null pile-up)");
+  if (!n) return WALT_OK;
+  if (n > WALT_REGIONS_MAX)
+    return fail(WALT_EINVAL, "walt_pileup_regions_device: " + std::to_string(n) + " regions, a call takes " + std::to_string(WALT_REGIONS_MAX) +
+                                 " at most");
+  if (!d_regions || !d_out || !d_work) return fail(WALT_EINVAL, "walt_pileup_regions_device: bad argument (null regions, out or workspace)");
+  if (((uintptr_t)d_regions & 7u) || ((uintptr_t)d_out & 7u) || ((uintptr_t)d_work & 7u))
+    return fail(WALT_EINVAL, "walt_pileup_regions_device: regions, out and the workspace must be 8-byte aligned");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  return pile_regions_launch(p, d_regions, n, d_out, d_work, reinterpret_cast<hipStream_t>(stream));
+}
+
+int walt_pileup_regions(walt_pileup* p, const walt_region* regions, uint64_t n, walt_region_levels* out) {
+  if (!p) return fail(WALT_EINVAL, "walt_pileup_regions: bad argument (null pile-up)");
+  if (!n) return WALT_OK;
+  if (!regions || !out) return fail(WALT_EINVAL, "walt_pileup_regions: bad argument (null regions or out)");
+  const uint32_t genome_len = p->idx->head.genome_len;
+  for (uint64_t i = 0; i < n; ++i)
+    if (regions[i].lo > regions[i].hi || regions[i].hi > genome_len)
+      return fail(WALT_EINVAL, "walt_pileup_regions: region " + std::to_string(i) + " [" + std::to_string(regions[i].lo) + ", " +
+                                   std::to_string(regions[i].hi) + ") is not inside the genome's " + std::to_string(genome_len) + " positions");
+  WALT_HIP(hipSetDevice(p->idx->device));
+  WALT_HIP(hipDeviceSynchronize());  // adds of any stream come first
+  const uint32_t window = (uint32_t)std::min<uint64_t>(n, WALT_REGIONS_MAX);
+  const uint64_t sizes[3] = {(uint64_t)window * sizeof(walt_region), (uint64_t)window * sizeof(walt_region_levels),
+                             walt_pileup_regions_workspace_bytes(window)};
+  void* got[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i)
+    if (hipMalloc(&got[i], sizes[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      for (void* q : got) if (q) (void)hipFree(q);
+      return fail(WALT_ENOMEM, "walt_pileup_regions: hipMalloc of " + std::to_string(sizes[i]) + " bytes failed");
+    }
+  hipError_t e = hipSuccess;
+  int rc = WALT_OK;
+  for (uint64_t at = 0; at < n && e == hipSuccess && rc == WALT_OK; at += window) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(window, n - at);
+    e = hipMemcpy(got[0], regions + at, (uint64_t)m * sizeof(walt_region), hipMemcpyHostToDevice);
+    if (e != hipSuccess) break;
+    rc = pile_regions_launch(p, got[0], m, got[1], got[2], nullptr);
+    if (rc == WALT_OK) e = hipMemcpy(out + at, got[1], (uint64_t)m * sizeof(walt_region_levels), hipMemcpyDeviceToHost);
+  }
+  for (void* q : got) (void)hipFree(q);
+  if (rc != WALT_OK) return rc;
+  if (e != hipSuccess) return fail(WALT_EHIP, std::string("walt_pileup_regions: ") + hipGetErrorString(e));
   return WALT_OK;
 }
 

@@ -814,6 +814,85 @@ int walt_meth_nonconv_batch_device(walt_index* idx, const void* d_bases, const v
 int walt_nonconv_pairs_batch(walt_index* idx, const walt_pair_result* pairs, uint32_t n, uint8_t* filt /*[2n]*/);
 int walt_nonconv_pairs_batch_device(walt_index* idx, const void* d_pairs, uint32_t n, void* d_filt /*[2n]*/, void* stream);
 
+/* ---- adjacent CpG pairs: which states two neighbouring CpGs had together on one read -------------------------------------
+ * The reference has no such mode (its users run a second program over the sorted mapped reads: MethPipe's allelicmeth and
+ * amrfinder, epipolymorphism and entropy tools); the contract is defined here.  Every other count of this library collapses
+ * a read into independent positions; this table keeps the joint state of neighbouring CpGs of one molecule, which cannot be
+ * rebuilt from per-position counts.
+ *
+ * Pairs.  A pair is a forward position c with R[c] == C, R[c + 1] == G and c + 1 in c's chromosome -- the pairs of
+ * "methylation levels" above, so a C that ends a chromosome in front of a G that starts the next is no pair.  Pairs are
+ * numbered j = 0 .. n_pairs - 1 by ascending c over the whole genome; n_pairs equals row[4].sites of
+ * walt_pileup_levels(p, 0, genome_len, ...).  The table is
+ *   uint32_t count[n_pairs][4]
+ * exact up to 2^32 - 1, wrapping beyond.  Entry j describes the couple (pair j, pair j + 1).  Columns: 0 MM, 1 MU, 2 UM,
+ * 3 UU; the first letter is the state of pair j, the lower forward position.
+ *
+ * What a read adds.  A record counts when times == 1, its skip byte, if given, is 0, its read has 1 to 1024 calls and
+ * genome_pos < genome_len: the records walt_mbias_batch counts, plus the position test.  With [lo, hi) the chromosome of
+ * genome_pos, read position i whose calls byte is z or Z has q = genome_pos + i and is ignored when q >= hi; otherwise its
+ * forward position is f = q for a '+' record and f = lo + hi - 1 - q for a '-' record, and its pair is f if f is a pair,
+ * else f - 1 if that is a pair, else the call is ignored.  R alone decides this, not the conversion, so every read that
+ * reaches f agrees.  (On an N-free genome no call of the calling kernel is ever ignored; hand-made calls and N fills can
+ * be.)  Let the calls that have a pair be (j_1, m_1) .. (j_k, m_k) in read order, m = upper case.  For t = 1 .. k - 1: when
+ * |j_{t+1} - j_t| == 1, add 1 to count[min(j_t, j_{t+1})][2 * u_lo + u_hi], u = 1 for an unmethylated call, lo the call on
+ * the lower pair.  Every other couple adds nothing: an uncalled or mismatched CpG in between, the two calls of one pair in
+ * a made-up string.  Every other byte is skipped, so call_len, excluded intervals and ignored read ends act through the '.'
+ * they leave: a pair whose partner was blanked is not counted.  A '-' record walks the pairs downwards; min and lo / hi
+ * make its entry the reverse-complement read's.  Each mate counts by itself; the two mates are not joined into a fragment.
+ *
+ * Life cycle.  walt_cpgpairs_create builds, on the index's device, one bit per forward position (set where a pair
+ * starts) and the number of pairs in front of every 128 positions -- genome_len / 8 + genome_len / 32 bytes -- and the
+ * zeroed table, 16 bytes per pair.  WALT_EINVAL when the index holds no reference; WALT_ENOMEM, naming the bytes wanted,
+ * when the device has no room, and the index stays usable.  The object must be destroyed before the index is closed.
+ * walt_cpgpairs_clear zeroes the table.  walt_cpgpairs_device_bytes: what the object holds.
+ *
+ * Batch calls.  walt_cpgpairs_batch[_device] add the calls of one batch.  Strides, alignment, the host and the device form,
+ * the refusals and the ordering -- adds are ordered by their stream, two streams may feed one table -- are those of
+ * walt_mbias_batch[_device]; a null object is WALT_EINVAL.
+ *
+ * Extraction.  walt_cpgpairs_extract[_device] return the entries with c_j in [pos_lo, pos_hi) and a non-zero counter,
+ * ascending, as walt_cpgpair_site records: pos = c_j, next = c_{j+1}, n = the four counters.  A non-zero entry has
+ * next < pos + 1024, because one read held both calls (pos + 1024 itself only from a hand-made string that calls the G of
+ * one pair and the C of the other). cap, *n_out, the range errors and "one extraction at a time" are
+ * those of walt_pileup_extract[_device]: the host form returns WALT_EINVAL with *n_out set when the range holds more than
+ * cap entries; the device form writes the count to *d_n_out and nothing else when it exceeds cap.  d_out and d_n_out
+ * 8-byte aligned.  The records do not depend on the launch shape (option pile_extract_blocks).
+ *
+ * With the calling.  walt_meth_pileup_batch_pairs[_device] are walt_meth_pileup_batch_trim[_device] plus ap: the calls of the
+ * batch are added as walt_cpgpairs_batch would add them under the same skip, behind the calling kernel on the same stream.
+ * The host form counts from its device copy of the calls, also when the caller's `calls` is NULL.  ap == NULL is exactly
+ * the trim form.  WALT_EINVAL when ap belongs to another index or (device form) when d_calls is NULL.  Every older entry
+ * point is this call with ap == NULL and launches what it always launched. */
+typedef struct walt_cpgpairs walt_cpgpairs;
+typedef struct {
+  uint32_t pos, next; /* forward positions of the C of pair j and of pair j + 1 */
+  uint32_t n[4];      /* MM, MU, UM, UU */
+} walt_cpgpair_site;  /* 24 bytes */
+int walt_cpgpairs_create(walt_index* idx, walt_cpgpairs** out);
+void walt_cpgpairs_destroy(walt_cpgpairs* ap);
+int walt_cpgpairs_clear(walt_cpgpairs* ap);
+uint64_t walt_cpgpairs_device_bytes(const walt_cpgpairs* ap);
+uint64_t walt_cpgpairs_n_pairs(const walt_cpgpairs* ap);
+int walt_cpgpairs_batch(walt_cpgpairs* ap, const char* calls, const uint64_t* offsets, uint32_t n, const void* records,
+                        size_t record_stride, const uint8_t* skip, size_t skip_stride);
+int walt_cpgpairs_batch_device(walt_cpgpairs* ap, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
+                               size_t record_stride, const void* d_skip, size_t skip_stride, void* stream);
+int walt_cpgpairs_extract(walt_cpgpairs* ap, uint32_t pos_lo, uint32_t pos_hi, walt_cpgpair_site* out, uint64_t cap,
+                          uint64_t* n_out);
+int walt_cpgpairs_extract_device(walt_cpgpairs* ap, uint32_t pos_lo, uint32_t pos_hi, void* d_out, uint64_t cap, void* d_n_out,
+                                 void* stream);
+int walt_meth_pileup_batch_pairs(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                 const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                 int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                 walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                 walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap);
+int walt_meth_pileup_batch_pairs_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                        int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                        const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                        uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -102,6 +102,9 @@ assert region_dtype.itemsize == 8 and region_row_dtype.itemsize == 32 and region
 nonconv_tally_dtype = np.dtype([("meth", "<u2"), ("total", "<u2"), ("run", "<u2"), ("reserved", "<u2")])
 nonconv_rule_dtype = np.dtype([("min_meth", "<u4"), ("min_run", "<u4"), ("min_percent", "<u4"), ("min_total", "<u4")])
 assert nonconv_tally_dtype.itemsize == 8 and nonconv_rule_dtype.itemsize == 16
+# walt_cpgpair_site: one non-zero entry of a pair table (include/walt_amd.h, "adjacent CpG pairs"); n: MM, MU, UM, UU
+cpgpair_site_dtype = np.dtype([("pos", "<u4"), ("next", "<u4"), ("n", "<u4", (4,))])
+assert cpgpair_site_dtype.itemsize == 24
 assert meth_counts_dtype.itemsize == 16 and meth_stats_dtype.itemsize == 72
 assert best_match_dtype.itemsize == 16 and candidate_dtype.itemsize == 12
 assert pair_result_dtype.itemsize == 64 and batch_stats_dtype.itemsize == 32
@@ -287,6 +290,22 @@ def lib(pattern=None):
                                                  vp, vp]
     L.walt_nonconv_pairs_batch.argtypes = [vp, vp, u32, vp]
     L.walt_nonconv_pairs_batch_device.argtypes = [vp, vp, u32, vp, vp]
+    L.walt_cpgpairs_create.argtypes = [vp, c.POINTER(vp)]
+    L.walt_cpgpairs_destroy.argtypes = [vp]
+    L.walt_cpgpairs_destroy.restype = None
+    L.walt_cpgpairs_clear.argtypes = [vp]
+    L.walt_cpgpairs_device_bytes.argtypes = [vp]
+    L.walt_cpgpairs_device_bytes.restype = u64
+    L.walt_cpgpairs_n_pairs.argtypes = [vp]
+    L.walt_cpgpairs_n_pairs.restype = u64
+    L.walt_cpgpairs_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t]
+    L.walt_cpgpairs_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, vp]
+    L.walt_cpgpairs_extract.argtypes = [vp, u32, u32, vp, u64, c.POINTER(u64)]
+    L.walt_cpgpairs_extract_device.argtypes = [vp, u32, u32, vp, u64, vp, vp]
+    L.walt_meth_pileup_batch_pairs.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                               c.c_size_t, vp, vp, u32, u32, u32, vp]
+    L.walt_meth_pileup_batch_pairs_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                      vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -393,22 +412,25 @@ def _rule_arg(rule):
     return rule
 
 
-def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None):
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None):
     """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
-    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), each None when the caller gave none.  The
+    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), each None when the caller
+    gave none.  The
     narrowest form that takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a
     call with skip only.  Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
-    widest = "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    widest = "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
     if widest is None:
         name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
     else:  # (these three take a null pile-up, a null skip and a null excl)
         name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
         if widest != "skip":
             tail += excl or (None,)
-        if widest in ("mbias", "trim"):
+        if widest in ("mbias", "trim", "pairs"):
             tail += mbias or (None, 0)
-        if widest == "trim":
-            tail += trim
+        if widest in ("trim", "pairs"):
+            tail += trim or (0, 0)
+        if widest == "pairs":
+            tail += pairs
     return getattr(L, name + ("_device" if device else "")), head, tail
 
 
@@ -680,7 +702,7 @@ class Index:
         self._ck(self._L.walt_index_enable_reference(self._h))
 
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                        stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                        stats=None, want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
         strided view: read in place).  conv: 'T' / 'A' for the whole batch, or a uint8 array of ord('T') / ord('A') per
         read (any stride, e.g. conv[:, 0] of map_pe_rpbat_batch).  Returns (calls uint8[total bases], counts
@@ -692,9 +714,11 @@ class Index:
         this index's device; the calls of the batch are added to its table mbias_table under the same skip
         (walt_meth_pileup_batch_mbias; only when given; want_calls may be False).  trim5 / trim3: the first trim5 read
         positions and the last trim3 before the clip point get no call (include/walt_amd.h, "ignored read ends":
-        walt_meth_pileup_batch_trim; only when one is non-zero)."""
+        walt_meth_pileup_batch_trim; only when one is non-zero).  pairs: a CpgPairs table of this index; the calls of the
+        batch are folded into it under the same skip (walt_meth_pileup_batch_pairs; only when given; want_calls may be
+        False)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
-                                skip, excl, mbias, mbias_table, trim5, trim3)
+                                skip, excl, mbias, mbias_table, trim5, trim3, pairs)
 
     # -- non-converted reads (include/walt_amd.h states the rules) ------------------------------------------------
     def nonconv_batch(self, calls, offsets, records, rule, want_tally=True):
@@ -801,12 +825,17 @@ class Index:
         form, tail = (self._L.walt_pair_overlap_batch_trim_device, trim) if any(trim) else (self._L.walt_pair_overlap_batch_device, ())
         self._ck(form(self._h, d_pairs, d_offsets1, d_offsets2, int(n), d_call_len1, d_call_len2, d_excl, d_totals, *tail, stream))
 
+    def cpg_pairs(self):
+        """A table of adjacent-CpG state pairs on this index's device (walt_cpgpairs_create); the index must hold the
+        reference."""
+        return CpgPairs(self)
+
     def pileup(self):
         """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
         records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
         positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
@@ -833,30 +862,32 @@ class Index:
                 raise ValueError("excl: a 1-d uint32 array with one word per read")
         form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
                                       excl is not None and (_ptr(excl_arr) if n else None,),
-                                      mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3))
+                                      mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3),
+                                      pairs=pairs is not None and (pairs.handle,))
         self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
                       conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                                conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0,
-                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
         """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  mbias: an MBias set
         whose table mbias_table takes the calls too (walt_meth_pileup_batch_mbias_device with a null pile-up; d_calls
         must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
-        pile-up); trim5 / trim3: as in meth_call_batch (walt_meth_pileup_batch_trim_device)."""
+        pile-up); trim5 / trim3: as in meth_call_batch (walt_meth_pileup_batch_trim_device); pairs: a CpgPairs table of
+        this index that takes the calls too (walt_meth_pileup_batch_pairs_device; d_calls must be given)."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
-        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3)
+        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs)
 
     def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5=0,
-                           trim3=0):
+                           trim3=0, pairs=None):
         """Index.meth_call_batch_device (pile null) and Pileup.add_batch_device.  batch: the C arguments from d_bases to
         d_stats; skip_alone: the form a call with d_skip only goes to (the index's: walt_meth_pileup_batch_excl_device, a
         pile-up's: walt_meth_pileup_batch_skip_device)."""
         form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
                                       d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
-                                      skip_alone, _trim_arg(trim5, trim3))
+                                      skip_alone, _trim_arg(trim5, trim3), pairs is not None and (pairs.handle,))
         self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
@@ -954,20 +985,22 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                  want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3)
+                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
-                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
-        MBias set whose table mbias_table takes the calls too (d_calls must be given)."""
+        MBias set whose table mbias_table takes the calls too (d_calls must be given); pairs: a CpgPairs table of the
+        index that takes them as well."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
-        self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3)
+        self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3,
+                                       pairs)
 
     def extract(self, pos_lo=0, pos_hi=None):
         """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the
@@ -1204,6 +1237,80 @@ class MBias:
     def close(self):
         if self._h:
             self._L.walt_mbias_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CpgPairs:
+    """Adjacent-CpG state pairs of an Index (include/walt_amd.h, "adjacent CpG pairs"): for every two neighbouring CpG
+    pairs of the genome, how often one read called them MM, MU, UM, UU -- exact 32-bit counters on the index's device,
+    keyed by the number of the lower pair.  Close it before the index."""
+
+    def __init__(self, index):
+        self._index = index
+        self._L = index._L
+        self._h = None
+        h = ctypes.c_void_p()
+        index._ck(self._L.walt_cpgpairs_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    def add(self, calls, offsets, records, skip=None):
+        """calls: the uint8 array Index.meth_call_batch returned (indexed from offsets[0]); offsets: n + 1; records: a
+        best_match_dtype array or strided view (e.g. the m2 field of a pair_result_dtype array); skip: a uint8 array per
+        record, any stride.  Waits for the result."""
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
+        calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
+        self._index._ck(self._L.walt_cpgpairs_batch(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
+
+    def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, stream=0):
+        """Device-pointer form (ints are HBM addresses on the index's device, stream a hipStream_t value); asynchronous."""
+        self._index._ck(self._L.walt_cpgpairs_batch_device(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride), d_skip,
+                                                           int(skip_stride), stream))
+
+    def extract(self, pos_lo=0, pos_hi=None):
+        """The non-zero entries whose lower pair starts in the forward positions [pos_lo, pos_hi), ascending:
+        cpgpair_site_dtype[n] (pos, next, n[4] = MM, MU, UM, UU)."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        n = ctypes.c_uint64(0)
+        rc = self._L.walt_cpgpairs_extract(self._h, int(pos_lo), int(pos_hi), None, 0, ctypes.byref(n))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        sites = np.zeros(n.value, dtype=cpgpair_site_dtype)
+        if n.value:
+            self._index._ck(self._L.walt_cpgpairs_extract(self._h, int(pos_lo), int(pos_hi), _ptr(sites), n.value, ctypes.byref(n)))
+        return sites
+
+    def extract_device(self, pos_lo, pos_hi, d_out, cap, d_n_out, stream=0):
+        """Device-pointer form (walt_cpgpairs_extract_device); asynchronous."""
+        self._index._ck(self._L.walt_cpgpairs_extract_device(self._h, int(pos_lo), int(pos_hi), d_out, int(cap), d_n_out, stream))
+
+    @property
+    def n_pairs(self):
+        return int(self._L.walt_cpgpairs_n_pairs(self._h))
+
+    def clear(self):
+        self._index._ck(self._L.walt_cpgpairs_clear(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._L.walt_cpgpairs_device_bytes(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.walt_cpgpairs_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -136,6 +136,20 @@ struct walt_mbias {
   unsigned long long* tabs = nullptr;
 };
 
+// Adjacent CpG pairs (cpgpairs.hip): one bit per forward position that starts a pair (n_words words, the zero padding
+// included), the pairs in front of every block of 128 positions, the table count[n_pairs][4] and the extraction's block
+// offsets.
+struct walt_cpgpairs {
+  walt_index* idx = nullptr;
+  uint32_t* bits = nullptr;
+  uint32_t* dir = nullptr;
+  uint32_t* table = nullptr;
+  unsigned long long* scan = nullptr;
+  uint64_t n_words = 0;
+  uint32_t n_pairs = 0;
+  uint64_t device_bytes = 0;
+};
+
 namespace walt {
 // mbias.hip: one batch of calls as the bias kernel reads it (device arrays), and the kernel on `stream`
 struct MbiasBatch {
@@ -147,6 +161,8 @@ struct MbiasBatch {
   size_t skip_stride;
 };
 int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream);
+// cpgpairs.hip: the pair kernel over the same batch on `stream` of the table's index's device
+int cpgpairs_launch(walt_cpgpairs* ap, const MbiasBatch& b, hipStream_t stream);
 
 // nonconv.hip: one batch of calls as the judging kernel reads it (device arrays; tally null: not wanted), the kernel on
 // `stream` of idx's device, what every form refuses of a rule and a filt array (empty: nothing), and the end of a host

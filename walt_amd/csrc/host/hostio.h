@@ -14,6 +14,7 @@
 #ifndef WALT_AMD_HOSTIO_H_
 #define WALT_AMD_HOSTIO_H_
 #include <fcntl.h>
+#include <math.h>
 #include <omp.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -686,6 +687,48 @@ inline void put_filter_block(Sink& out, uint64_t records, uint64_t filtered, con
   out.lit("rule");
   for (int k = 0; k < 4; ++k) { out.ch('\t'); out.u32(rule[k]); }
   out.ch('\n');
+}
+
+// ---------------------------------------------------------------- <out>.allelic (bin/walt -MA)
+// log(k!) through lgamma; the small arguments, which are nearly all there are, from a table filled once
+inline double log_factorial(uint64_t k) {
+  static const std::vector<double> small = [] {
+    std::vector<double> t(4096);
+    for (size_t i = 0; i < t.size(); ++i) t[i] = lgamma((double)i + 1.0);
+    return t;
+  }();
+  return k < small.size() ? small[(size_t)k] : lgamma((double)k + 1.0);
+}
+// The two-sided Fisher exact test of the table [[a, b], [c, d]]: the sum of the hypergeometric probabilities of all
+// tables with the same margins whose probability is at most P(observed) * (1 + 1e-7) -- the slack takes in the exact
+// ties of a symmetric table, which differ in the last bits here -- capped at 1.  The empty table gives 1.  The work
+// grows with the smaller margin.
+inline double fisher_exact_two_sided(uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+  const uint64_t r1 = a + b, r2 = c + d, c1 = a + c, c2 = b + d, n = r1 + r2;
+  if (!n) return 1.0;
+  const uint64_t lo = r1 + c1 > n ? r1 + c1 - n : 0, hi = std::min(r1, c1);
+  const double margins = log_factorial(r1) + log_factorial(r2) + log_factorial(c1) + log_factorial(c2) - log_factorial(n);
+  auto log_p = [&](uint64_t x) {  // the table whose first cell is x
+    return margins - log_factorial(x) - log_factorial(r1 - x) - log_factorial(c1 - x) - log_factorial(n - r1 - c1 + x);
+  };
+  const double bound = log_p(a) + log1p(1e-7);
+  double sum = 0.0;
+  for (uint64_t x = lo; x <= hi; ++x) {
+    const double lp = log_p(x);
+    if (lp <= bound) sum += exp(lp);
+  }
+  return sum < 1.0 ? sum : 1.0;
+}
+// One entry of a pair table (include/walt_amd.h, "adjacent CpG pairs") as a line, tab-separated:
+//   chrom  pos  next  pval  total  MM  MU  UM  UU
+// pos and next 0-based within the chromosome, total the sum of the four counts, pval fisher_exact_two_sided as %.6g.
+inline void put_allelic_line(Sink& out, const std::string& chrom, uint32_t pos, uint32_t next, const uint64_t n[4]) {
+  char num[192];
+  out.put(chrom);
+  snprintf(num, sizeof num, "\t%u\t%u\t%.6g\t%llu\t%llu\t%llu\t%llu\t%llu\n", pos, next, fisher_exact_two_sided(n[0], n[1], n[2], n[3]),
+           (unsigned long long)(n[0] + n[1] + n[2] + n[3]), (unsigned long long)n[0], (unsigned long long)n[1],
+           (unsigned long long)n[2], (unsigned long long)n[3]);
+  out.lit(num);
 }
 
 }  // namespace hostio

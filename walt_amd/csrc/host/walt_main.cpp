@@ -56,10 +56,11 @@ struct Options {
   string regions_file;  // -MR: methylation levels per region of a BED file (walt_pileup_regions): <out>.regions
   bool regions() const { return !regions_file.empty(); }
   bool piling() const { return methcounts || levels || regions(); }  // the run keeps pile-ups
-  bool consumer() const { return meth || methcounts || mbias || levels || regions(); }  // something takes the methylation calls
+  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic; }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
+  bool allelic = false;  // -MA: adjacent-CpG state pairs per read (walt_meth_pileup_batch_pairs): <out>.allelic
   // -I5 -I3 -I5R2 -I3R2: the first / last bases of a read that get no methylation call (walt_meth_pileup_batch_trim), of
   // the reads of -r or -1 ([0], [1]) and of the reads of -2 ([2], [3]); the user's order, also under -P and -RP
   uint32_t ignore[4] = {0, 0, 0, 0};
@@ -117,6 +118,7 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "D", "dedup") || a == "--remove-duplicates") o.dedup = true;  // extension: mark PCR duplicates
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
+    else if (is_opt(a, "MA", "allelic") || a == "--allelic-meth") o.allelic = true;  // extension: adjacent-CpG state pairs per read
     else if (is_opt(a, "I5", "ignore") || is_opt(a, "I3", "ignore-3prime") || is_opt(a, "I5R2", "ignore-r2") ||
              is_opt(a, "I3R2", "ignore-3prime-r2")) {  // extension: read ends kept out of the methylation calls
       const int k = is_opt(a, "I5", "ignore") ? 0 : is_opt(a, "I3", "ignore-3prime") ? 1 : is_opt(a, "I5R2", "ignore-r2") ? 2 : 3;
@@ -166,15 +168,15 @@ static Options parse(int argc, const char** argv) {
   if (o.no_overlap && !o.se_csv.empty())
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
   if (o.no_overlap && !o.consumer())
-    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML, -MR) there is nothing for it to do");
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML, -MR, -MA) there is nothing for it to do");
   if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.consumer())
-    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB, -ML or -MR there is nothing for them to do");
+    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB, -ML, -MR or -MA there is nothing for them to do");
   if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
     die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
   if (o.filter_given[3] && !o.filter_given[2])
     die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
   if ((o.filtering() || o.filter_given[3]) && !o.consumer())
-    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML or -MR there is nothing for them to do");
+    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML, -MR or -MA there is nothing for them to do");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -543,6 +545,75 @@ struct MbiasSet {
   }
 };
 
+// ---------------------------------------------------------------- -MA: adjacent-CpG state pairs per read
+// One pair table per device of the run; a share's calls are folded on the device that made them.  At the end of a read
+// file the non-zero entries are extracted window by window of forward positions (a bounded buffer per device: pairs do
+// not overlap, so a window holds at most half as many entries as positions), the windows of several devices merged by
+// position with their counts added -- the counters are additive -- and written with the test of each table.
+struct PairSet {
+  vector<walt_cpgpairs*> p;
+  void open(const vector<walt_index*>& idx) {
+    p.assign(idx.size(), nullptr);
+    for (size_t d = 0; d < idx.size(); ++d)
+      if (walt_cpgpairs_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+  }
+  void close() {  // (before the indexes are closed)
+    for (walt_cpgpairs*& q : p) { if (q) walt_cpgpairs_destroy(q); q = nullptr; }
+    p.clear();
+  }
+  bool on() const { return !p.empty(); }
+  walt_cpgpairs* of(size_t d) const { return on() ? p[d] : nullptr; }
+};
+struct AllelicRow {
+  uint32_t pos, next;
+  uint64_t n[4];
+};
+static void write_allelic(const string& out_file, PairSet& ps, const GenomeInfo& g, bool verbose) {
+  OutFile mf;
+  if (!mf.open_append(out_file + ".allelic")) die("cannot open input file " + out_file + ".allelic");
+  const uint64_t genome_len = g.start.back();
+  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+  const uint64_t cap = window / 2 + 1;
+  vector<walt_cpgpair_site> buf((size_t)cap);  // allocated once
+  vector<AllelicRow> rows, other;
+  uint64_t n_total = 0, couples = 0;
+  uint32_t chr = 0;
+  Sink out;
+  for (uint64_t lo = 0; lo < genome_len; lo += window) {
+    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
+    rows.clear();
+    for (size_t d = 0; d < ps.p.size(); ++d) {
+      uint64_t n = 0;
+      check(walt_cpgpairs_extract(ps.p[d], (uint32_t)lo, (uint32_t)hi, buf.data(), cap, &n));
+      other.clear();  // merge by position, adding the counts
+      uint64_t i = 0, j = 0;
+      while (i < rows.size() || j < n) {
+        if (j == n || (i < rows.size() && rows[i].pos < buf[j].pos)) { other.push_back(rows[i++]); continue; }
+        const walt_cpgpair_site& b = buf[j++];
+        AllelicRow r = {b.pos, b.next, {b.n[0], b.n[1], b.n[2], b.n[3]}};
+        if (i < rows.size() && rows[i].pos == b.pos) {
+          for (int k = 0; k < 4; ++k) r.n[k] += rows[i].n[k];
+          ++i;
+        }
+        other.push_back(r);
+      }
+      rows.swap(other);
+    }
+    out.clear();
+    for (const AllelicRow& r : rows) {
+      while (r.pos >= g.start[chr + 1]) ++chr;  // (ascending positions; next lies in the same chromosome)
+      hostio::put_allelic_line(out, g.name[chr], r.pos - g.start[chr], r.next - g.start[chr], r.n);
+      couples += r.n[0] + r.n[1] + r.n[2] + r.n[3];
+    }
+    n_total += rows.size();
+    if (out.n) mf.write(out.p, out.n);
+  }
+  mf.close();
+  if (verbose)
+    fprintf(stderr, "[walt_amd allelic: %llu entries, %llu couples of neighbouring CpGs]\n", (unsigned long long)n_total,
+            (unsigned long long)couples);
+}
+
 // ---------------------------------------------------------------- -D: PCR duplicates
 // One duplicate set per read file, on the first device of the run.  A batch is mapped by all devices first; then the
 // whole batch's records are fed to the set in input order (so the verdict depends neither on -N nor on -g); only then are
@@ -782,6 +853,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.piling()) pile.open(dev.idx);
   MbiasSet mbs;
   if (o.mbias) mbs.open(dev.ids, 1);
+  PairSet pairs;
+  if (o.allelic) pairs.open(dev.idx);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   FilterSet flt;
@@ -846,7 +919,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
       return rc;
     };
     // the calls of a share, on the device that mapped it: one call takes whatever the options give it -- the pile-up (-MC),
-    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB) -- each null without its
+    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB), the pair table (-MA) -- each null without its
     // option (all null: walt_meth_call_batch) -- and the ignored read ends (-I5 / -I3; both 0 without them: the kernels a
     // run always launched)
     // -F -FC -FP: first the share's verdicts (the whole read up to its clip point, whatever -I5 / -I3 say), ORed into the
@@ -863,11 +936,11 @@ static void process_se(const Options& o, const string& reads_file, const string&
         flt.merge(lo, hi, dups.on() ? dups.dup.data() : nullptr);
         skip = flt.skip.data() + lo;
       }
-      return walt_meth_pileup_batch_trim(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+      return walt_meth_pileup_batch_pairs(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
                                          o.meth ? &meth_of[d] : nullptr, skip, 1, nullptr,
-                                         mbs.of(d), 0, o.ignore[0], o.ignore[1]);
+                                         mbs.of(d), 0, o.ignore[0], o.ignore[1], pairs.of(d));
     };
     if (!dups.on()) {
       dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
@@ -951,6 +1024,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     mbs.write(out_file, ms);
     mbs.close();
   }
+  if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   if (flt.on()) flt.write_stats(out_file, o.verbose);
   const double t_c0 = now_s();
@@ -1107,6 +1181,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   if (o.piling()) pile.open(dev.idx);
   MbiasSet mbs;  // -MB: table k takes slot k
   if (o.mbias) mbs.open(dev.ids, 2);
+  PairSet pairs;  // -MA: both mates into the same table, each by itself
+  if (o.allelic) pairs.open(dev.idx);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   FilterSet flt;
@@ -1204,7 +1280,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     // The calls of a share, on the device that mapped it.  -NO: first the share's intervals from the records in user order.
     // Then both slots through one call that takes whatever the options give it -- the pile-up (-MC: both mates into the
     // device's), the verdicts as skip bytes (-D), the interval words for the user's mate 2 (-NO; none for mate 1: the call
-    // it always got), the bias set (-MB: table k takes slot k) -- each null without its option -- and the slot's ignored
+    // it always got), the bias set (-MB: table k takes slot k), the pair table (-MA) -- each null without its option -- and the slot's ignored
     // read ends (0 without -I5 -I3 -I5R2 -I3R2: the kernels a run always launched).  Slot 0 was mapped C->T,
     // slot 1 G->A (-RP: as conv says).
     // -F -FC -FP: before all that the verdicts of the share's two slots (each mate's whole read up to its clip point), the
@@ -1239,13 +1315,13 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                           &overlap_of[2 * d], o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
       }
       for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_trim(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+        rc = walt_meth_pileup_batch_pairs(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
                                          skip ? skip + 2 * (size_t)lo + k : nullptr, 2,
                                          o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k,
-                                         trim_slot[k][0], trim_slot[k][1]);
+                                         trim_slot[k][0], trim_slot[k][1], pairs.of(d));
       return rc;
     };
     if (!dups.on()) {
@@ -1388,6 +1464,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     mbs.write(out_file, ms);
     mbs.close();
   }
+  if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   if (flt.on()) flt.write_stats(out_file, o.verbose);
   dev.close();
@@ -1401,7 +1478,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1423,6 +1500,7 @@ int main(int argc, const char** argv) {
     if (o.levels) for (auto& f : outs) { std::ofstream levels(f + ".levels"); }
     if (o.regions()) for (auto& f : outs) { std::ofstream regions(f + ".regions"); }
     if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
+    if (o.allelic) for (auto& f : outs) { std::ofstream allelic(f + ".allelic"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");

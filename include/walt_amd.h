@@ -893,6 +893,89 @@ int walt_meth_pileup_batch_pairs_device(walt_index* idx, walt_pileup* p, const v
                                         const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
                                         uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, void* stream);
 
+/* ---- four-CpG epialleles: which of the 16 patterns four neighbouring CpGs showed on one read --------------------------------
+ * The reference has no such mode (its users write SAM, sort it and run a second program over every XM:Z: string); the
+ * contract is defined here.  Epipolymorphism (Landan 2012), methylation entropy (Xie 2011), methclone's clonality shift
+ * (Li 2014) and the proportion of discordant reads (Landau 2014) are all defined on this table.  It cannot be rebuilt from
+ * the pair table above, for the reason that table cannot be rebuilt from per-position counts.
+ *
+ * Pairs and numbering are those of "adjacent CpG pairs": j = 0 .. n_pairs - 1 by ascending forward position c_j of the C,
+ * the chromosome rule included.  The table is
+ *   uint32_t count[n_pairs][16]
+ * exact up to 2^32 - 1, wrapping beyond.  Entry j describes the window of pairs j, j + 1, j + 2, j + 3.  Column
+ * p = 8 u0 + 4 u1 + 2 u2 + u3, u_i the state of pair j + i, 1 = unmethylated: 0 is MMMM, 15 is UUUU, and the first letter
+ * belongs to the lowest forward position (this extends the pair table's 2 u_lo + u_hi).  The last three entries never
+ * receive an add.
+ *
+ * What a read adds.  The records that count, the calls that have a pair and how a call finds its pair number are word for
+ * word those of walt_cpgpairs_batch: times == 1, skip byte 0, 1 to 1024 calls, genome_pos < genome_len, the q >= hi rule,
+ * the C or the G of the pair, '-' records mirrored.  Let the calls with a pair be (j_1, u_1) .. (j_k, u_k) in read order.
+ * For every t with t + 3 <= k: when j_{t+i} = j_t + i s for i = 1, 2, 3 with one s in {+1, -1}, the read adds 1 to
+ * count[min(j_t, j_{t+3})][p], p formed from the four states in forward order.  Four calls qualify only if they follow
+ * each other among the calls that have a pair: a '.' where a CpG was blanked (a mismatch, a clip, an ignored end, an
+ * overlap position) makes the pair numbers on its two sides no neighbours, and so does the second call of one pair in a
+ * made-up string; nothing is counted across such a break.  A chain of m neighbouring calls adds m - 3 windows.  A '-'
+ * record and its reverse complement add to the same entry and column.  Each mate counts by itself.
+ *   Every read that adds a window also adds the three couples inside it to a pair table fed the same batch, so for all j,
+ * a, b: the sum over the p with (u0, u1) = (a, b) of count[j][p] is at most pairs[j][2 a + b], and likewise against the
+ * pair table's entries j + 1 and j + 2 for (u1, u2) and (u2, u3).
+ *
+ * Life cycle.  walt_epialleles_create builds, on the index's device, the object's own pair bitmap and rank directory -- by
+ * the code walt_cpgpairs_create builds them with; one rank structure shared between a pair table and a window table is
+ * not offered -- and the zeroed table, 64 bytes per pair (1.8 GB for the 28 M CpGs of a human genome).  WALT_EINVAL when
+ * the index holds no reference; WALT_ENOMEM, naming the bytes wanted, when the device has no room, and the index stays
+ * usable.  The object must be destroyed before the index is closed.  walt_epialleles_clear zeroes the table.
+ *
+ * Batch calls.  walt_epialleles_batch[_device] take the arguments, strides, refusals and stream ordering of
+ * walt_cpgpairs_batch[_device]; two streams may feed one table.
+ *
+ * Extraction.  walt_epialleles_extract[_device] return the entries with c_j in [pos_lo, pos_hi) whose sixteen counters sum
+ * (in 64 bits) to at least min_total, ascending, as walt_epiallele_site records: pos = c_j, last = c_{j+3}, n = the
+ * sixteen counters.  min_total == 0 is WALT_EINVAL.  Membership goes by pos alone: a window that starts inside the range
+ * and ends behind it is returned, one that starts in front of it is not.  last <= pos + 1024: a returned entry got an add,
+ * so one read of at most 1024 calls, which spans positions q .. q + 1023, held a call on each of the four pairs; a call
+ * sits on the C or the G of its pair, so c_j >= q - 1 and c_{j+3} <= q + 1023, and the extreme pos + 1024 needs a
+ * hand-made string that calls the G of the first pair and the C of the last (calls the library made give
+ * last <= pos + 1023).  last is found by three steps along the bitmap, each of which looks at least 1056 positions ahead.  cap,
+ * *n_out, the range errors, the alignment and "nothing written when over cap" are those of walt_cpgpairs_extract[_device].
+ * The records do not depend on the launch shape (option pile_extract_blocks).
+ *
+ * With the calling.  walt_meth_pileup_batch_epi[_device] are walt_meth_pileup_batch_pairs[_device] plus ep: the calls of the
+ * batch are added as walt_epialleles_batch would add them under the same skip, behind the calling kernel (and the pair
+ * kernel, if ap is given) on the same stream.  ep == NULL is exactly the pairs form.  WALT_EINVAL when ep belongs to
+ * another index or (device form) when d_calls is NULL.  Every older entry point is this call with ep == NULL and launches
+ * what it always launched. */
+typedef struct walt_epialleles walt_epialleles;
+typedef struct {
+  uint32_t pos, last; /* forward positions of the C of pair j and of pair j + 3 */
+  uint32_t n[16];     /* MMMM, MMMU, MMUM, .. UUUU */
+} walt_epiallele_site; /* 72 bytes */
+int walt_epialleles_create(walt_index* idx, walt_epialleles** out);
+void walt_epialleles_destroy(walt_epialleles* ep);
+int walt_epialleles_clear(walt_epialleles* ep);
+uint64_t walt_epialleles_device_bytes(const walt_epialleles* ep);
+uint64_t walt_epialleles_n_pairs(const walt_epialleles* ep);
+int walt_epialleles_batch(walt_epialleles* ep, const char* calls, const uint64_t* offsets, uint32_t n, const void* records,
+                          size_t record_stride, const uint8_t* skip, size_t skip_stride);
+int walt_epialleles_batch_device(walt_epialleles* ep, const void* d_calls, const void* d_offsets, uint32_t n, const void* d_records,
+                                 size_t record_stride, const void* d_skip, size_t skip_stride, void* stream);
+int walt_epialleles_extract(walt_epialleles* ep, uint32_t pos_lo, uint32_t pos_hi, uint64_t min_total, walt_epiallele_site* out,
+                            uint64_t cap, uint64_t* n_out);
+int walt_epialleles_extract_device(walt_epialleles* ep, uint32_t pos_lo, uint32_t pos_hi, uint64_t min_total, void* d_out,
+                                   uint64_t cap, void* d_n_out, void* stream);
+int walt_meth_pileup_batch_epi(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                               const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                               int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                               walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                               walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap,
+                               walt_epialleles* ep);
+int walt_meth_pileup_batch_epi_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                      const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                      int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                      const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                      uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                      void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -14,6 +14,8 @@ loops over ``PairEndMapping`` plus ``MergePairedEndResults``
 (reference.cpp:324-417), ``makedb`` is makedb.cpp:128-159.
 """
 import ctypes
+import functools
+import inspect
 import os
 
 import numpy as np
@@ -105,6 +107,9 @@ assert nonconv_tally_dtype.itemsize == 8 and nonconv_rule_dtype.itemsize == 16
 # walt_cpgpair_site: one non-zero entry of a pair table (include/walt_amd.h, "adjacent CpG pairs"); n: MM, MU, UM, UU
 cpgpair_site_dtype = np.dtype([("pos", "<u4"), ("next", "<u4"), ("n", "<u4", (4,))])
 assert cpgpair_site_dtype.itemsize == 24
+# walt_epiallele_site: one entry of a window table (include/walt_amd.h, "four-CpG epialleles"); n: MMMM, MMMU, .. UUUU
+epiallele_site_dtype = np.dtype([("pos", "<u4"), ("last", "<u4"), ("n", "<u4", (16,))])
+assert epiallele_site_dtype.itemsize == 72
 assert meth_counts_dtype.itemsize == 16 and meth_stats_dtype.itemsize == 72
 assert best_match_dtype.itemsize == 16 and candidate_dtype.itemsize == 12
 assert pair_result_dtype.itemsize == 64 and batch_stats_dtype.itemsize == 32
@@ -306,6 +311,22 @@ def lib(pattern=None):
                                                c.c_size_t, vp, vp, u32, u32, u32, vp]
     L.walt_meth_pileup_batch_pairs_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                       vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp]
+    L.walt_epialleles_create.argtypes = [vp, c.POINTER(vp)]
+    L.walt_epialleles_destroy.argtypes = [vp]
+    L.walt_epialleles_destroy.restype = None
+    L.walt_epialleles_clear.argtypes = [vp]
+    L.walt_epialleles_device_bytes.argtypes = [vp]
+    L.walt_epialleles_device_bytes.restype = u64
+    L.walt_epialleles_n_pairs.argtypes = [vp]
+    L.walt_epialleles_n_pairs.restype = u64
+    L.walt_epialleles_batch.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t]
+    L.walt_epialleles_batch_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, vp]
+    L.walt_epialleles_extract.argtypes = [vp, u32, u32, u64, vp, u64, c.POINTER(u64)]
+    L.walt_epialleles_extract_device.argtypes = [vp, u32, u32, u64, vp, u64, vp, vp]
+    L.walt_meth_pileup_batch_epi.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                             c.c_size_t, vp, vp, u32, u32, u32, vp, vp]
+    L.walt_meth_pileup_batch_epi_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                    vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -412,25 +433,27 @@ def _rule_arg(rule):
     return rule
 
 
-def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None):
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None, epi=None):
     """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
-    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), each None when the caller
+    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), epi = (handle,), each None when the caller
     gave none.  The
     narrowest form that takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a
     call with skip only.  Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
-    widest = "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    widest = "epi" if epi else "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
     if widest is None:
         name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
     else:  # (these three take a null pile-up, a null skip and a null excl)
         name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
         if widest != "skip":
             tail += excl or (None,)
-        if widest in ("mbias", "trim", "pairs"):
+        if widest in ("mbias", "trim", "pairs", "epi"):
             tail += mbias or (None, 0)
-        if widest in ("trim", "pairs"):
+        if widest in ("trim", "pairs", "epi"):
             tail += trim or (0, 0)
-        if widest == "pairs":
-            tail += pairs
+        if widest in ("pairs", "epi"):
+            tail += pairs or (None,)
+        if widest == "epi":
+            tail += epi
     return getattr(L, name + ("_device" if device else "")), head, tail
 
 
@@ -503,6 +526,26 @@ class Comm:
         if self._h:
             self._L.walt_comm_close(self._h)
             self._h = None
+
+
+def _keyword_only_epi(plain):
+    """Index.meth_call_batch with one more, keyword-only argument epi=.  The argument cannot stand in the method's own
+    parameter list: a keyword-only parameter is listed behind every other, and the end of that list is pinned
+    (tests/test_nonconv_cpu.py), so inspect.signature goes on showing the list as it was.  plain's parameters are
+    Index._meth_batch's by name."""
+    signature = inspect.signature(plain)
+
+    @functools.wraps(plain)
+    def call(self, *args, epi=None, **kw):
+        if epi is None:
+            return plain(self, *args, **kw)
+        bound = signature.bind(self, *args, **kw)
+        bound.apply_defaults()
+        named = dict(bound.arguments)
+        del named["self"]
+        return self._meth_batch(None, epi=epi, **named)
+
+    return call
 
 
 class Index:
@@ -701,6 +744,7 @@ class Index:
         """Builds the unconverted reference on an index that holds all four strands (walt_index_enable_reference)."""
         self._ck(self._L.walt_index_enable_reference(self._h))
 
+    @_keyword_only_epi
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
                         stats=None, want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
         """Host-buffer form.  records: a best_match_dtype array, or the m1 / m2 field of a pair_result_dtype array (a
@@ -716,7 +760,7 @@ class Index:
         positions and the last trim3 before the clip point get no call (include/walt_amd.h, "ignored read ends":
         walt_meth_pileup_batch_trim; only when one is non-zero).  pairs: a CpgPairs table of this index; the calls of the
         batch are folded into it under the same skip (walt_meth_pileup_batch_pairs; only when given; want_calls may be
-        False)."""
+        False).  epi (keyword only): an Epialleles table of this index, likewise (walt_meth_pileup_batch_epi)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
                                 skip, excl, mbias, mbias_table, trim5, trim3, pairs)
 
@@ -830,12 +874,18 @@ class Index:
         reference."""
         return CpgPairs(self)
 
+    def epialleles(self):
+        """A table of four-CpG epiallele patterns on this index's device (walt_epialleles_create); the index must hold
+        the reference."""
+        return Epialleles(self)
+
     def pileup(self):
         """A per-cytosine pile-up on this index's device (walt_pileup_create); the index must hold the reference."""
         return Pileup(self)
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
-                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
+                    stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None,
+                    epi=None):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
         records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
         positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
@@ -863,31 +913,34 @@ class Index:
         form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
                                       excl is not None and (_ptr(excl_arr) if n else None,),
                                       mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3),
-                                      pairs=pairs is not None and (pairs.handle,))
+                                      pairs=pairs is not None and (pairs.handle,), epi=epi is not None and (epi.handle,))
         self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
                       conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
 
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                                conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0,
-                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
+                               d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None,
+                               *, epi=None):
         """Device-pointer form (ints are HBM addresses, stream a hipStream_t value); asynchronous.  mbias: an MBias set
         whose table mbias_table takes the calls too (walt_meth_pileup_batch_mbias_device with a null pile-up; d_calls
         must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
         pile-up); trim5 / trim3: as in meth_call_batch (walt_meth_pileup_batch_trim_device); pairs: a CpgPairs table of
-        this index that takes the calls too (walt_meth_pileup_batch_pairs_device; d_calls must be given)."""
+        this index that takes the calls too (walt_meth_pileup_batch_pairs_device; d_calls must be given); epi: an Epialleles
+        table of this index, likewise (walt_meth_pileup_batch_epi_device)."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
-        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs)
+        self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs, epi)
 
     def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5=0,
-                           trim3=0, pairs=None):
+                           trim3=0, pairs=None, epi=None):
         """Index.meth_call_batch_device (pile null) and Pileup.add_batch_device.  batch: the C arguments from d_bases to
         d_stats; skip_alone: the form a call with d_skip only goes to (the index's: walt_meth_pileup_batch_excl_device, a
         pile-up's: walt_meth_pileup_batch_skip_device)."""
         form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
                                       d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
-                                      skip_alone, _trim_arg(trim5, trim3), pairs is not None and (pairs.handle,))
+                                      skip_alone, _trim_arg(trim5, trim3), pairs is not None and (pairs.handle,),
+                                      epi is not None and (epi.handle,))
         self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
@@ -985,22 +1038,22 @@ class Pileup:
         self._h = h
 
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
-                  want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
+                  want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, *, epi=None):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs)
+                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs, epi)
 
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
-                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None):
+                         skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None, *, epi=None):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
         MBias set whose table mbias_table takes the calls too (d_calls must be given); pairs: a CpgPairs table of the
-        index that takes them as well."""
+        index that takes them as well; epi: an Epialleles table of the index, likewise."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
         self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3,
-                                       pairs)
+                                       pairs, epi)
 
     def extract(self, pos_lo=0, pos_hi=None):
         """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the
@@ -1311,6 +1364,81 @@ class CpgPairs:
     def close(self):
         if self._h:
             self._L.walt_cpgpairs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Epialleles:
+    """Four-CpG epialleles of an Index (include/walt_amd.h, "four-CpG epialleles"): for every four neighbouring CpG pairs
+    of the genome, how often one read showed each of their 16 methylation patterns (column 8 u0 + 4 u1 + 2 u2 + u3, u = 1
+    unmethylated, the lowest position first) -- exact 32-bit counters on the index's device, keyed by the number of the
+    lowest pair.  Close it before the index."""
+
+    def __init__(self, index):
+        self._index = index
+        self._L = index._L
+        self._h = None
+        h = ctypes.c_void_p()
+        index._ck(self._L.walt_epialleles_create(index._h, ctypes.byref(h)))
+        self._h = h
+
+    def add(self, calls, offsets, records, skip=None):
+        """CpgPairs.add's arguments.  Waits for the result."""
+        calls = np.ascontiguousarray(calls, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
+        calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
+        self._index._ck(self._L.walt_epialleles_batch(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
+
+    def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, stream=0):
+        """Device-pointer form (ints are HBM addresses on the index's device, stream a hipStream_t value); asynchronous."""
+        self._index._ck(self._L.walt_epialleles_batch_device(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride),
+                                                             d_skip, int(skip_stride), stream))
+
+    def extract(self, pos_lo=0, pos_hi=None, min_total=1):
+        """The entries whose lowest pair starts in the forward positions [pos_lo, pos_hi) and whose sixteen counters sum
+        to at least min_total (>= 1), ascending: epiallele_site_dtype[n] (pos, last, n[16])."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        n = ctypes.c_uint64(0)
+        rc = self._L.walt_epialleles_extract(self._h, int(pos_lo), int(pos_hi), int(min_total), None, 0, ctypes.byref(n))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        sites = np.zeros(n.value, dtype=epiallele_site_dtype)
+        if n.value:
+            self._index._ck(self._L.walt_epialleles_extract(self._h, int(pos_lo), int(pos_hi), int(min_total), _ptr(sites), n.value,
+                                                            ctypes.byref(n)))
+        return sites
+
+    def extract_device(self, pos_lo, pos_hi, min_total, d_out, cap, d_n_out, stream=0):
+        """Device-pointer form (walt_epialleles_extract_device); asynchronous."""
+        self._index._ck(self._L.walt_epialleles_extract_device(self._h, int(pos_lo), int(pos_hi), int(min_total), d_out, int(cap),
+                                                               d_n_out, stream))
+
+    @property
+    def n_pairs(self):
+        return int(self._L.walt_epialleles_n_pairs(self._h))
+
+    def clear(self):
+        self._index._ck(self._L.walt_epialleles_clear(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._L.walt_epialleles_device_bytes(self._h)
+
+    def close(self):
+        if self._h:
+            self._L.walt_epialleles_destroy(self._h)
             self._h = None
 
     def __del__(self):

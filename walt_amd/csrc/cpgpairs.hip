@@ -10,6 +10,7 @@
 
 #include "map_common.h"
 #include "cpgpairs_core.h"
+#include "cpg_device.h"
 
 namespace walt {
 
@@ -43,14 +44,6 @@ __global__ __launch_bounds__(kBlock) void k_cpg_ends(const uint32_t* __restrict_
   if (end) (void)atomicAnd(bits + cpg_end_word(end), cpg_end_mask(end));
 }
 
-__device__ __forceinline__ uint32_t cpg_block_sum(uint32_t v, uint32_t* s_red) {  // the block's sum, in every thread
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t t = 0;
-  for (uint32_t w = 0; w < kBlock / 64; ++w) t += s_red[w];
-  return t;
-}
 // scan, launch 1 of 3: the pairs of kBlock neighbouring directory blocks -> sums[block]
 __global__ __launch_bounds__(kBlock) void k_cpg_dir_sums(const uint32_t* __restrict__ bits, uint64_t n_dir,
                                                           unsigned long long* __restrict__ sums) {
@@ -96,6 +89,59 @@ __global__ __launch_bounds__(kBlock) void k_cpg_dir_apply(const uint32_t* __rest
   uint32_t before = (uint32_t)sums[blockIdx.x];
   for (uint32_t w = 0; w < kBlock / 64; ++w) before += w < wave ? s_wave[w] : 0u;
   if (i < n_dir) dir[i] = before + incl - v;
+}
+
+// what cpg_rank_build allocates for idx's genome: the bitmap with its padding, the directory, the scan words
+uint64_t cpg_rank_bytes(const walt_index* idx) {
+  const uint64_t genome_len = idx->head.genome_len;
+  const uint64_t n_dir = cpg_dir_entries(genome_len), n_sums = (n_dir + kBlock - 1) / kBlock;
+  return 4 * (cpg_bit_words(genome_len) + kCpgPadWords) + 4 * std::max<uint64_t>(n_dir, 1) +
+         8ull * std::max<uint64_t>(kCpgScanWords, n_sums + 2);
+}
+void cpg_rank_free(CpgRank& r) {
+  (void)hipFree(r.bits); (void)hipFree(r.dir); (void)hipFree(r.scan);
+  r = CpgRank();
+}
+// The pair bitmap, its directory and the scan words of one object on idx's device (the current device), built from the
+// '+' reference the index holds: what walt_cpgpairs_create and walt_epialleles_create share.  false: nothing is left
+// allocated; e == hipSuccess then means the device had no room for cpg_rank_bytes(idx), else e is the error.
+bool cpg_rank_build(const walt_index* idx, CpgRank& r, hipError_t& e) {
+  const uint64_t genome_len = idx->head.genome_len;
+  const uint64_t n_bit_words = cpg_bit_words(genome_len), n_dir = cpg_dir_entries(genome_len);
+  const uint64_t n_sums = (n_dir + kBlock - 1) / kBlock;
+  const uint64_t bits_bytes = 4 * (n_bit_words + kCpgPadWords), dir_bytes = 4 * std::max<uint64_t>(n_dir, 1);
+  const uint64_t scan_bytes = 8ull * std::max<uint64_t>(kCpgScanWords, n_sums + 2);
+  r = CpgRank();
+  r.n_words = n_bit_words + kCpgPadWords;
+  e = hipSuccess;
+  if (hipMalloc(reinterpret_cast<void**>(&r.bits), bits_bytes) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&r.dir), dir_bytes) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&r.scan), scan_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    cpg_rank_free(r);
+    return false;
+  }
+  const uint32_t ref_last = (uint32_t)((genome_len + 15) / 16 + kCpgRefPadWords - 1);
+  e = hipMemset(r.bits, 0, bits_bytes);
+  if (e == hipSuccess) e = hipMemset(r.dir, 0, dir_bytes);
+  if (e == hipSuccess && genome_len) {
+    const uint64_t n_src = (genome_len + 31) / 32;  // the words that hold a position
+    hipLaunchKernelGGL(k_cpg_bits, dim3(grid_for(n_src)), dim3(kBlock), 0, nullptr, idx->ref[0], ref_last, n_src, r.bits);
+    hipLaunchKernelGGL(k_cpg_ends, dim3(grid_for(idx->view.n_chrom)), dim3(kBlock), 0, nullptr, idx->view.start_index,
+                       idx->view.n_chrom, r.bits);
+    hipLaunchKernelGGL(k_cpg_dir_sums, dim3((unsigned)n_sums), dim3(kBlock), 0, nullptr, r.bits, n_dir, r.scan);
+    hipLaunchKernelGGL(k_cpg_scan, dim3(1), dim3(1024), 0, nullptr, r.scan, (uint32_t)n_sums, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_cpg_dir_apply, dim3((unsigned)n_sums), dim3(kBlock), 0, nullptr, r.bits, n_dir, r.scan, r.dir);
+    e = hipGetLastError();
+    unsigned long long total = 0;
+    if (e == hipSuccess) e = hipMemcpy(&total, r.scan + n_sums, 8, hipMemcpyDeviceToHost);
+    r.n_pairs = (uint32_t)total;
+  }
+  if (e != hipSuccess) {
+    cpg_rank_free(r);
+    return false;
+  }
+  return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -317,20 +363,35 @@ static int cpg_range_check(const walt_cpgpairs* ap, const char* who, uint32_t po
   return WALT_OK;
 }
 
+// The launch shape of an extraction of [pos_lo, pos_hi): the bitmap words that hold the range, cut into n_blocks chunks
+// (option pile_extract_blocks, else one block per kCpgTileWords words up to eight per CU).
+CpgShape cpg_extract_shape(const walt_index* idx, uint32_t pos_lo, uint32_t pos_hi) {
+  CpgShape sh;
+  sh.w_lo = pos_lo >> 5;
+  sh.w_hi = pos_hi > pos_lo ? ((uint64_t)pos_hi + 31u) >> 5 : sh.w_lo;
+  const uint64_t range = sh.w_hi - sh.w_lo;
+  uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks
+                                               : std::min<uint64_t>((range + kCpgTileWords - 1) / kCpgTileWords, (uint64_t)idx->n_cu * 8);
+  want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, kCpgMaxBlocks), std::max<uint64_t>(range, 1)));
+  sh.n_blocks = (uint32_t)want;
+  sh.chunk = (range + want - 1) / want;
+  return sh;
+}
+
+// k_cpg_scan over table[0 .. n) on `stream` (total_out: null, or a device word that gets the sum too)
+void cpg_scan_launch(unsigned long long* table, uint32_t n, unsigned long long* total_out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_cpg_scan, dim3(1), dim3(1024), 0, stream, table, n, total_out);
+}
+
 static CpgExtract cpg_extract_args(const walt_cpgpairs* ap, uint32_t pos_lo, uint32_t pos_hi, uint32_t& n_blocks) {
   const walt_index* idx = ap->idx;
   CpgExtract a;
   a.bits = ap->bits; a.dir = ap->dir; a.table = ap->table;
   a.n_words = ap->n_words;
   a.pos_lo = pos_lo; a.pos_hi = pos_hi;
-  a.w_lo = pos_lo >> 5;
-  a.w_hi = pos_hi > pos_lo ? ((uint64_t)pos_hi + 31u) >> 5 : a.w_lo;
-  const uint64_t range = a.w_hi - a.w_lo;
-  uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks
-                                               : std::min<uint64_t>((range + kCpgTileWords - 1) / kCpgTileWords, (uint64_t)idx->n_cu * 8);
-  want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, kCpgMaxBlocks), std::max<uint64_t>(range, 1)));
-  n_blocks = (uint32_t)want;
-  a.chunk = (range + want - 1) / want;
+  const CpgShape sh = cpg_extract_shape(idx, pos_lo, pos_hi);
+  a.w_lo = sh.w_lo; a.w_hi = sh.w_hi; a.chunk = sh.chunk;
+  n_blocks = sh.n_blocks;
   a.scan = ap->scan;
   a.out = nullptr; a.cap = 0;
   return a;
@@ -357,18 +418,14 @@ int walt_cpgpairs_create(walt_index* idx, walt_cpgpairs** out) {
     return fail(WALT_EINVAL, "walt_cpgpairs_create: the index holds no reference (open it with WALT_WITH_REFERENCE or call "
                              "walt_index_enable_reference)");
   WALT_HIP(hipSetDevice(idx->device));
-  const uint64_t genome_len = idx->head.genome_len;
-  const uint64_t n_bit_words = cpg_bit_words(genome_len), n_dir = cpg_dir_entries(genome_len);
-  const uint64_t n_sums = (n_dir + kBlock - 1) / kBlock;
-  const uint64_t bits_bytes = 4 * (n_bit_words + kCpgPadWords), dir_bytes = 4 * std::max<uint64_t>(n_dir, 1);
-  const uint64_t scan_bytes = 8ull * std::max<uint64_t>(kCpgScanWords, n_sums + 2);
   walt_cpgpairs* ap = new walt_cpgpairs;
   ap->idx = idx;
-  ap->n_words = n_bit_words + kCpgPadWords;
-  uint64_t wanted = bits_bytes + dir_bytes + scan_bytes;
+  CpgRank rank;
+  uint64_t wanted = cpg_rank_bytes(idx);
   const auto give_up = [&](int code, const std::string& msg) {  // the index stays as it was
     (void)hipGetLastError();
-    (void)hipFree(ap->bits); (void)hipFree(ap->dir); (void)hipFree(ap->scan); (void)hipFree(ap->table);
+    cpg_rank_free(rank);
+    (void)hipFree(ap->table);
     delete ap;
     return fail(code, msg);
   };
@@ -376,27 +433,14 @@ int walt_cpgpairs_create(walt_index* idx, walt_cpgpairs** out) {
     return give_up(WALT_ENOMEM, "walt_cpgpairs_create: the pair table wants " + std::to_string(wanted) +
                                     " bytes of device memory (genome_len / 8 + genome_len / 32 + 16 per CpG pair)");
   };
-  if (hipMalloc(reinterpret_cast<void**>(&ap->bits), bits_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ap->dir), dir_bytes) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&ap->scan), scan_bytes) != hipSuccess)
-    return no_memory();
-  const uint32_t ref_last = (uint32_t)((genome_len + 15) / 16 + kCpgRefPadWords - 1);
-  hipError_t e = hipMemset(ap->bits, 0, bits_bytes);
-  if (e == hipSuccess) e = hipMemset(ap->dir, 0, dir_bytes);
-  if (e == hipSuccess && genome_len) {
-    const uint64_t n_src = (genome_len + 31) / 32;  // the words that hold a position
-    hipLaunchKernelGGL(k_cpg_bits, dim3(grid_for(n_src)), dim3(kBlock), 0, nullptr, idx->ref[0], ref_last, n_src, ap->bits);
-    hipLaunchKernelGGL(k_cpg_ends, dim3(grid_for(idx->view.n_chrom)), dim3(kBlock), 0, nullptr, idx->view.start_index,
-                       idx->view.n_chrom, ap->bits);
-    hipLaunchKernelGGL(k_cpg_dir_sums, dim3((unsigned)n_sums), dim3(kBlock), 0, nullptr, ap->bits, n_dir, ap->scan);
-    hipLaunchKernelGGL(k_cpg_scan, dim3(1), dim3(1024), 0, nullptr, ap->scan, (uint32_t)n_sums, (unsigned long long*)nullptr);
-    hipLaunchKernelGGL(k_cpg_dir_apply, dim3((unsigned)n_sums), dim3(kBlock), 0, nullptr, ap->bits, n_dir, ap->scan, ap->dir);
-    e = hipGetLastError();
-    unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpy(&total, ap->scan + n_sums, 8, hipMemcpyDeviceToHost);
-    ap->n_pairs = (uint32_t)total;
+  hipError_t e = hipSuccess;
+  if (!cpg_rank_build(idx, rank, e)) {
+    if (e == hipSuccess) return no_memory();
+    return give_up(WALT_EHIP, std::string("walt_cpgpairs_create: building the pair bitmap failed: ") + hipGetErrorString(e));
   }
-  if (e != hipSuccess) return give_up(WALT_EHIP, std::string("walt_cpgpairs_create: building the pair bitmap failed: ") + hipGetErrorString(e));
+  ap->bits = rank.bits; ap->dir = rank.dir; ap->scan = rank.scan;
+  ap->n_words = rank.n_words;
+  ap->n_pairs = rank.n_pairs;
   wanted += cpg_table_bytes(ap);
   if (hipMalloc(reinterpret_cast<void**>(&ap->table), cpg_table_bytes(ap)) != hipSuccess) return no_memory();
   if (hipMemset(ap->table, 0, cpg_table_bytes(ap)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)

@@ -150,6 +150,19 @@ struct walt_cpgpairs {
   uint64_t device_bytes = 0;
 };
 
+// Four-CpG epialleles (epialleles.hip): its own pair bitmap and directory, built as walt_cpgpairs's, the table
+// count[n_pairs][16] and the extraction's block offsets.
+struct walt_epialleles {
+  walt_index* idx = nullptr;
+  uint32_t* bits = nullptr;
+  uint32_t* dir = nullptr;
+  uint32_t* table = nullptr;
+  unsigned long long* scan = nullptr;
+  uint64_t n_words = 0;
+  uint32_t n_pairs = 0;
+  uint64_t device_bytes = 0;
+};
+
 namespace walt {
 // mbias.hip: one batch of calls as the bias kernel reads it (device arrays), and the kernel on `stream`
 struct MbiasBatch {
@@ -163,6 +176,8 @@ struct MbiasBatch {
 int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream);
 // cpgpairs.hip: the pair kernel over the same batch on `stream` of the table's index's device
 int cpgpairs_launch(walt_cpgpairs* ap, const MbiasBatch& b, hipStream_t stream);
+// epialleles.hip: the window kernel over the same batch on `stream` of the table's index's device
+int epialleles_launch(walt_epialleles* ep, const MbiasBatch& b, hipStream_t stream);
 
 // nonconv.hip: one batch of calls as the judging kernel reads it (device arrays; tally null: not wanted), the kernel on
 // `stream` of idx's device, what every form refuses of a rule and a filt array (empty: nothing), and the end of a host

@@ -731,5 +731,88 @@ inline void put_allelic_line(Sink& out, const std::string& chrom, uint32_t pos, 
   out.lit(num);
 }
 
+// ---------------------------------------------------------------- <out>.epialleles (bin/walt -ME)
+// The value of -MEN: a decimal integer from 1 to 1,000,000, nothing in front of or behind its digits.
+constexpr uint32_t kMaxEpialleleMin = 1000000;
+inline bool parse_epiallele_min(const std::string& text, uint32_t& out) {
+  if (text.empty() || text.size() > 7) return false;
+  uint32_t v = 0;
+  for (const char c : text) {
+    if (c < '0' || c > '9') return false;
+    v = v * 10 + (uint32_t)(c - '0');
+  }
+  if (v < 1 || v > kMaxEpialleleMin) return false;
+  out = v;
+  return true;
+}
+// A window's statistics from its sixteen counts (column p = 8 u0 + 4 u1 + 2 u2 + u3, u = 1 unmethylated), in double:
+// meth = sum n_p (4 - popcount p) / (4 total), epipoly = 1 - sum (n_p / total)^2 (Landan 2012), entropy =
+// -1/4 sum (n_p / total) log2 (n_p / total) with 0 log 0 = 0 (Xie 2011), discordant = 1 - (n_0 + n_15) / total (Landau
+// 2014).  An empty window gives zeros.
+struct EpialleleStats {
+  uint64_t total;
+  double meth, epipoly, entropy, discordant;
+};
+inline EpialleleStats epiallele_stats(const uint64_t n[16]) {
+  EpialleleStats s = {0, 0.0, 0.0, 0.0, 0.0};
+  uint64_t meth = 0;
+  for (int p = 0; p < 16; ++p) {
+    s.total += n[p];
+    meth += n[p] * (uint64_t)(4 - __builtin_popcount((unsigned)p));
+  }
+  if (!s.total) return s;
+  const double t = (double)s.total;
+  double squares = 0.0, plogp = 0.0;
+  for (int p = 0; p < 16; ++p) {
+    if (!n[p]) continue;
+    const double f = (double)n[p] / t;
+    squares += f * f;
+    plogp += f * log2(f);
+  }
+  s.meth = (double)meth / (4.0 * t);
+  s.epipoly = 1.0 - squares;
+  s.entropy = plogp == 0.0 ? 0.0 : -0.25 * plogp;  // (no -0.000000)
+  s.discordant = 1.0 - (double)(n[0] + n[15]) / t;
+  return s;
+}
+// One entry of a window table (include/walt_amd.h, "four-CpG epialleles") as a line, tab-separated:
+//   chrom  pos  end  total  n0 .. n15  meth  epipoly  entropy  discordant
+// pos and end 0-based within the chromosome: the first and the fourth C; the four statistics as %.6f.
+inline void put_epiallele_line(Sink& out, const std::string& chrom, uint32_t pos, uint32_t end, const uint64_t n[16]) {
+  const EpialleleStats s = epiallele_stats(n);
+  char num[640];
+  int at = snprintf(num, sizeof num, "\t%u\t%u\t%llu", pos, end, (unsigned long long)s.total);
+  for (int p = 0; p < 16; ++p) at += snprintf(num + at, sizeof num - (size_t)at, "\t%llu", (unsigned long long)n[p]);
+  snprintf(num + at, sizeof num - (size_t)at, "\t%.6f\t%.6f\t%.6f\t%.6f\n", s.meth, s.epipoly, s.entropy, s.discordant);
+  out.put(chrom);
+  out.lit(num);
+}
+// One window of a run as the writer holds it, and the merge of two devices' windows: `add`, ascending by position, into
+// `rows`, ascending too -- the counters of a position both hold are added (they are additive: each device counted its
+// own share of the reads).  `other` is scratch.
+struct EpialleleRow {
+  uint32_t pos, last;
+  uint64_t n[16];
+};
+inline void merge_epiallele_rows(std::vector<EpialleleRow>& rows, const EpialleleRow* add, size_t n_add, std::vector<EpialleleRow>& other) {
+  other.clear();
+  size_t i = 0, j = 0;
+  while (i < rows.size() || j < n_add) {
+    if (j == n_add || (i < rows.size() && rows[i].pos < add[j].pos)) { other.push_back(rows[i++]); continue; }
+    EpialleleRow r = add[j++];
+    if (i < rows.size() && rows[i].pos == r.pos) {
+      for (int k = 0; k < 16; ++k) r.n[k] += rows[i].n[k];
+      ++i;
+    }
+    other.push_back(r);
+  }
+  rows.swap(other);
+}
+inline uint64_t epiallele_row_total(const EpialleleRow& r) {
+  uint64_t t = 0;
+  for (int k = 0; k < 16; ++k) t += r.n[k];
+  return t;
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

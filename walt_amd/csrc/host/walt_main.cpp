@@ -56,11 +56,14 @@ struct Options {
   string regions_file;  // -MR: methylation levels per region of a BED file (walt_pileup_regions): <out>.regions
   bool regions() const { return !regions_file.empty(); }
   bool piling() const { return methcounts || levels || regions(); }  // the run keeps pile-ups
-  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic; }  // something takes the methylation calls
+  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic || epialleles; }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
   bool allelic = false;  // -MA: adjacent-CpG state pairs per read (walt_meth_pileup_batch_pairs): <out>.allelic
+  bool epialleles = false;  // -ME: four-CpG epiallele patterns per read (walt_meth_pileup_batch_epi): <out>.epialleles
+  uint32_t epi_min = 1;     // -MEN: the fewest reads of a window that is written
+  bool epi_min_given = false;
   // -I5 -I3 -I5R2 -I3R2: the first / last bases of a read that get no methylation call (walt_meth_pileup_batch_trim), of
   // the reads of -r or -1 ([0], [1]) and of the reads of -2 ([2], [3]); the user's order, also under -P and -RP
   uint32_t ignore[4] = {0, 0, 0, 0};
@@ -119,6 +122,13 @@ static Options parse(int argc, const char** argv) {
     else if (is_opt(a, "NO", "no-overlap")) o.no_overlap = true;  // extension: the overlap of a pair counted once
     else if (is_opt(a, "MB", "mbias") || a == "--m-bias") o.mbias = true;  // extension: methylation bias by read position
     else if (is_opt(a, "MA", "allelic") || a == "--allelic-meth") o.allelic = true;  // extension: adjacent-CpG state pairs per read
+    else if (is_opt(a, "ME", "epialleles")) o.epialleles = true;  // extension: four-CpG epiallele patterns per read
+    else if (is_opt(a, "MEN", "epiallele-min") || a == "--epiallele-min-reads") {  // extension: the fewest reads of a written window
+      const string v = val();
+      if (!hostio::parse_epiallele_min(v, o.epi_min))
+        die(a + " (epialleles) wants a number of reads from 1 to 1000000, not \"" + v + "\"");
+      o.epi_min_given = true;
+    }
     else if (is_opt(a, "I5", "ignore") || is_opt(a, "I3", "ignore-3prime") || is_opt(a, "I5R2", "ignore-r2") ||
              is_opt(a, "I3R2", "ignore-3prime-r2")) {  // extension: read ends kept out of the methylation calls
       const int k = is_opt(a, "I5", "ignore") ? 0 : is_opt(a, "I3", "ignore-3prime") ? 1 : is_opt(a, "I5R2", "ignore-r2") ? 2 : 3;
@@ -177,6 +187,8 @@ static Options parse(int argc, const char** argv) {
     die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
   if ((o.filtering() || o.filter_given[3]) && !o.consumer())
     die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML, -MR or -MA there is nothing for them to do");
+  if (o.epi_min_given && !o.epialleles)
+    die("-MEN (the fewest reads of a written window) goes with -ME: without it there is nothing for it to do");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -614,6 +626,67 @@ static void write_allelic(const string& out_file, PairSet& ps, const GenomeInfo&
             (unsigned long long)couples);
 }
 
+// ---------------------------------------------------------------- -ME: four-CpG epiallele patterns per read
+// One window table per device of the run, as PairSet.  At the end of a read file the entries are extracted window by
+// window of forward positions.  On one device -MEN is the extraction's min_total; with several the host extracts every
+// entry that got a read, merges by position adding the counts, and applies -MEN to the merged totals.
+struct EpiSet {
+  vector<walt_epialleles*> p;
+  void open(const vector<walt_index*>& idx) {
+    p.assign(idx.size(), nullptr);
+    for (size_t d = 0; d < idx.size(); ++d)
+      if (walt_epialleles_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+  }
+  void close() {  // (before the indexes are closed)
+    for (walt_epialleles*& q : p) { if (q) walt_epialleles_destroy(q); q = nullptr; }
+    p.clear();
+  }
+  bool on() const { return !p.empty(); }
+  walt_epialleles* of(size_t d) const { return on() ? p[d] : nullptr; }
+};
+static void write_epialleles(const string& out_file, EpiSet& es, const GenomeInfo& g, uint32_t min_reads, bool verbose) {
+  OutFile mf;
+  if (!mf.open_append(out_file + ".epialleles")) die("cannot open input file " + out_file + ".epialleles");
+  const uint64_t genome_len = g.start.back();
+  const uint64_t window = std::min<uint64_t>(kCountsWindow / 2, genome_len);
+  const uint64_t cap = window / 2 + 1;  // pairs do not overlap
+  vector<walt_epiallele_site> buf((size_t)cap);  // allocated once
+  vector<hostio::EpialleleRow> rows, add, other;
+  const bool merge = es.p.size() > 1;
+  uint64_t n_total = 0, windows = 0;
+  uint32_t chr = 0;
+  Sink out;
+  for (uint64_t lo = 0; lo < genome_len; lo += window) {
+    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
+    rows.clear();
+    for (size_t d = 0; d < es.p.size(); ++d) {
+      uint64_t n = 0;
+      check(walt_epialleles_extract(es.p[d], (uint32_t)lo, (uint32_t)hi, merge ? 1 : min_reads, buf.data(), cap, &n));
+      add.resize((size_t)n);
+      for (uint64_t i = 0; i < n; ++i) {
+        add[i].pos = buf[i].pos;
+        add[i].last = buf[i].last;
+        for (int k = 0; k < 16; ++k) add[i].n[k] = buf[i].n[k];
+      }
+      hostio::merge_epiallele_rows(rows, add.data(), add.size(), other);
+    }
+    out.clear();
+    for (const hostio::EpialleleRow& r : rows) {
+      const uint64_t total = hostio::epiallele_row_total(r);
+      if (total < min_reads) continue;
+      while (r.pos >= g.start[chr + 1]) ++chr;  // (ascending positions; last lies in the same chromosome)
+      hostio::put_epiallele_line(out, g.name[chr], r.pos - g.start[chr], r.last - g.start[chr], r.n);
+      windows += total;
+      ++n_total;
+    }
+    if (out.n) mf.write(out.p, out.n);
+  }
+  mf.close();
+  if (verbose)
+    fprintf(stderr, "[walt_amd epialleles: %llu entries, %llu windows of four neighbouring CpGs]\n", (unsigned long long)n_total,
+            (unsigned long long)windows);
+}
+
 // ---------------------------------------------------------------- -D: PCR duplicates
 // One duplicate set per read file, on the first device of the run.  A batch is mapped by all devices first; then the
 // whole batch's records are fed to the set in input order (so the verdict depends neither on -N nor on -g); only then are
@@ -855,6 +928,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.mbias) mbs.open(dev.ids, 1);
   PairSet pairs;
   if (o.allelic) pairs.open(dev.idx);
+  EpiSet epi;
+  if (o.epialleles) epi.open(dev.idx);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   FilterSet flt;
@@ -919,7 +994,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
       return rc;
     };
     // the calls of a share, on the device that mapped it: one call takes whatever the options give it -- the pile-up (-MC),
-    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB), the pair table (-MA) -- each null without its
+    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB), the pair table (-MA), the window table (-ME) -- each null without its
     // option (all null: walt_meth_call_batch) -- and the ignored read ends (-I5 / -I3; both 0 without them: the kernels a
     // run always launched)
     // -F -FC -FP: first the share's verdicts (the whole read up to its clip point, whatever -I5 / -I3 say), ORed into the
@@ -936,11 +1011,11 @@ static void process_se(const Options& o, const string& reads_file, const string&
         flt.merge(lo, hi, dups.on() ? dups.dup.data() : nullptr);
         skip = flt.skip.data() + lo;
       }
-      return walt_meth_pileup_batch_pairs(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
+      return walt_meth_pileup_batch_epi(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
                                          sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
                                          clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
                                          o.meth ? &meth_of[d] : nullptr, skip, 1, nullptr,
-                                         mbs.of(d), 0, o.ignore[0], o.ignore[1], pairs.of(d));
+                                         mbs.of(d), 0, o.ignore[0], o.ignore[1], pairs.of(d), epi.of(d));
     };
     if (!dups.on()) {
       dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
@@ -1025,6 +1100,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
     mbs.close();
   }
   if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
+  if (epi.on()) { write_epialleles(out_file, epi, g, o.epi_min, o.verbose); epi.close(); }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   if (flt.on()) flt.write_stats(out_file, o.verbose);
   const double t_c0 = now_s();
@@ -1183,6 +1259,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   if (o.mbias) mbs.open(dev.ids, 2);
   PairSet pairs;  // -MA: both mates into the same table, each by itself
   if (o.allelic) pairs.open(dev.idx);
+  EpiSet epi;  // -ME: likewise
+  if (o.epialleles) epi.open(dev.idx);
   DupSet dups;
   if (o.dedup) dups.open(dev.ids[0]);
   FilterSet flt;
@@ -1280,7 +1358,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     // The calls of a share, on the device that mapped it.  -NO: first the share's intervals from the records in user order.
     // Then both slots through one call that takes whatever the options give it -- the pile-up (-MC: both mates into the
     // device's), the verdicts as skip bytes (-D), the interval words for the user's mate 2 (-NO; none for mate 1: the call
-    // it always got), the bias set (-MB: table k takes slot k), the pair table (-MA) -- each null without its option -- and the slot's ignored
+    // it always got), the bias set (-MB: table k takes slot k), the pair table (-MA), the window table (-ME) -- each null without its option -- and the slot's ignored
     // read ends (0 without -I5 -I3 -I5R2 -I3R2: the kernels a run always launched).  Slot 0 was mapped C->T,
     // slot 1 G->A (-RP: as conv says).
     // -F -FC -FP: before all that the verdicts of the share's two slots (each mate's whole read up to its clip point), the
@@ -1315,13 +1393,13 @@ static void process_pe(const Options& o, const string& file1, const string& file
                                           &overlap_of[2 * d], o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
       }
       for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_pairs(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
+        rc = walt_meth_pileup_batch_epi(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
                                          k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
                                          2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
                                          o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
                                          skip ? skip + 2 * (size_t)lo + k : nullptr, 2,
                                          o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k,
-                                         trim_slot[k][0], trim_slot[k][1], pairs.of(d));
+                                         trim_slot[k][0], trim_slot[k][1], pairs.of(d), epi.of(d));
       return rc;
     };
     if (!dups.on()) {
@@ -1465,6 +1543,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
     mbs.close();
   }
   if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
+  if (epi.on()) { write_epialleles(out_file, epi, g, o.epi_min, o.verbose); epi.close(); }
   if (dups.on()) { dups.write_stats(out_file); dups.close(); }
   if (flt.on()) flt.write_stats(out_file, o.verbose);
   dev.close();
@@ -1478,7 +1557,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
@@ -1501,6 +1580,7 @@ int main(int argc, const char** argv) {
     if (o.regions()) for (auto& f : outs) { std::ofstream regions(f + ".regions"); }
     if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
     if (o.allelic) for (auto& f : outs) { std::ofstream allelic(f + ".allelic"); }
+    if (o.epialleles) for (auto& f : outs) { std::ofstream epialleles(f + ".epialleles"); }
     if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
     if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");

@@ -362,6 +362,7 @@ struct MethCall {
   uint32_t table = 0;
   uint32_t trim5 = 0, trim3 = 0;   // the ignored read ends (include/walt_amd.h, "ignored read ends"); both 0: none
   walt_cpgpairs* ap = nullptr;     // the pair table that takes the calls too (include/walt_amd.h, "adjacent CpG pairs")
+  walt_epialleles* ep = nullptr;   // the window table that takes the calls too (include/walt_amd.h, "four-CpG epialleles")
   // the rule that judges the calls too (include/walt_amd.h, "non-converted reads"; null: none), and where the verdicts go
   bool rule_form = false;          // walt_meth_nonconv_batch[_device]: a rule must be given
   const walt_nonconv_rule* rule = nullptr;
@@ -399,6 +400,11 @@ static int meth_call_check(const MethCall& c, bool has_calls) {
     if (!has_calls)
       return fail(WALT_EINVAL, who + ": the pair table is counted from the calls: d_calls must not be NULL when a pair table is given");
   }
+  if (c.ep) {  // (include/walt_amd.h, "four-CpG epialleles"): the same index, calls to fold
+    if (c.ep->idx != c.idx) return fail(WALT_EINVAL, who + ": the epiallele table belongs to another index");
+    if (!has_calls)
+      return fail(WALT_EINVAL, who + ": the epiallele table is counted from the calls: d_calls must not be NULL when an epiallele table is given");
+  }
   return WALT_OK;
 }
 
@@ -415,8 +421,8 @@ static int meth_nonconv_check(const MethCall& c, bool has_calls) {
 }
 
 // c: a checked call whose arrays are on the device.  The calling kernel and, with a bias set (which comes with calls),
-// the bias kernel from the calls just written: behind it on the same stream.  Likewise the pair kernel with a pair table
-// and the judging kernel with a rule.
+// the bias kernel from the calls just written: behind it on the same stream.  Likewise the pair kernel with a pair table,
+// the window kernel with an epiallele table and the judging kernel with a rule.
 static int meth_launch(const MethCall& c) {
   walt_index* const idx = c.idx;
   if (c.n == 0 || (!c.calls && !c.counts && !c.stats && !c.pile)) return WALT_OK;
@@ -466,6 +472,9 @@ static int meth_launch(const MethCall& c) {
   if (c.ap)
     if (const int rc = cpgpairs_launch(c.ap, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream))
       return rc;
+  if (c.ep)
+    if (const int rc = epialleles_launch(c.ep, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream))
+      return rc;
   if (!c.rule) return WALT_OK;
   return nonconv_launch(idx, {c.calls, c.offsets, c.n, c.records, c.record_stride, *c.rule, c.filt, c.filt_stride, c.tally}, stream);
 }
@@ -497,7 +506,7 @@ static int meth_batch_host(const MethCall& c) {
   const std::string bad = call_reads_refusal(c.who, offsets, n, static_cast<const uint8_t*>(c.conv), c.conv_stride);
   if (!bad.empty()) return fail(WALT_EINVAL, bad);
   walt_meth_stats* stats = static_cast<walt_meth_stats*>(c.stats);
-  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb && !c.rule && !c.ap) return WALT_OK;
+  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb && !c.rule && !c.ap && !c.ep) return WALT_OK;
   WALT_HIP(hipSetDevice(c.idx->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(c.records, c.record_stride, n);
@@ -514,7 +523,7 @@ static int meth_batch_host(const MethCall& c) {
   if (c.call_len && (rc = d_len.put(c.call_len, (size_t)n * 4, what))) return rc;
   if (c.skip && (rc = d_skip.put(sk.data(), n, what))) return rc;
   if (c.excl && (rc = d_excl.put(c.excl, (size_t)n * 4, what))) return rc;
-  if ((c.calls || c.mb || c.rule || c.ap) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias and pair tables are counted, the verdict made, from the device copy)
+  if ((c.calls || c.mb || c.rule || c.ap || c.ep) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias, pair and window tables are counted, the verdict made, from the device copy)
   if (c.rule && (rc = d_filt.get(n, what))) return rc;
   if (c.rule && c.tally && (rc = d_tally.get((size_t)n * sizeof(walt_nonconv_tally), what))) return rc;
   if (c.counts && (rc = d_counts.get((size_t)n * sizeof(walt_meth_counts), what))) return rc;
@@ -716,6 +725,35 @@ int walt_meth_pileup_batch_pairs(walt_index* idx, walt_pileup* p, const char* ba
                           .calls = calls, .counts = counts, .stats = stats,
                           .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
                           .trim5 = trim5, .trim3 = trim3, .ap = ap});
+}
+
+// the pairs forms plus an epiallele table (include/walt_amd.h, "four-CpG epialleles"); ep null: the pairs form
+int walt_meth_pileup_batch_epi_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                      const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                      int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                      const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                      uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                      void* stream) {
+  return meth_batch_device({.who = "walt_meth_pileup_batch_epi_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .mb = mb, .table = table,
+                            .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .stream = stream});
+}
+
+int walt_meth_pileup_batch_epi(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                               const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                               int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                               walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                               walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap,
+                               walt_epialleles* ep) {
+  return meth_batch_host({.who = "walt_meth_pileup_batch_epi", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
+                          .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep});
 }
 
 // the calling call plus the verdict on its calls (include/walt_amd.h, "non-converted reads"): no pile-up, no statistics

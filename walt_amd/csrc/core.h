@@ -1674,6 +1674,67 @@ WALT_HD uint32_t count_mismatch_regs2(const uint32_t* g /*[NW + 1]*/, uint32_t s
   tmm = t;
   return mm;
 }
+
+// The same count with the shift taken out of the candidate loop.  A dense record starts kWinLead bases in front of its
+// position, so a read of seed shift seed_i meets it sh = 2 (kWinLead - seed_i) bits in: count_mismatch_regs funnels
+// every window word down by sh, per candidate.  sh is fixed for the read; shifting the READ up by sh once compares the
+// same base pairs on the record's own words.
+//   align_word      word w of the multiword left shift by sh bits (sh even, 0 .. 30): the bits that leave word w - 1
+//                   (`below`; 0 for w = 0) enter word w from the bottom
+//   align_read      rd_a[NW + 1], mk_a[NW + 1]: rd[NW], mk[NW] shifted so; the low sh bits of word 0 are zero, word NW
+//                   holds what left word NW - 1
+//   count_mismatch_aligned  over words 0 .. NW - 1 of g, and word NW when `top` is set; top is `mk_a[NW] != 0` (a read
+//                   of len bases has compared bases up to len + kWinLead - seed_i: beyond 16 NW or not)
+// PRECONDITION: mk has bits at even positions only (bit 2k stands for base k).  Then a base's two bits stay in one word
+// under an even shift, and for every g, rd:  count_mismatch_aligned<NW>(g, rd_a, mk_a, mk_a[NW] != 0) ==
+// count_mismatch_regs<NW>(g, sh, rd, mk).  Every mask source keeps it: the mask table's words are sums of
+// 1 << 2 (q & 15) (host_index.cpp), tail_mask_word is cut from 0x55555555, compare_mask_word is their union.
+WALT_HD uint32_t align_word(uint32_t cur, uint32_t below, uint32_t sh) {
+  return (cur << sh) | ((below >> 1) >> (31u - sh));  // (no shift by 32 at sh = 0, and no select)
+}
+template <int NW>
+WALT_HD void align_read(const uint32_t* rd, const uint32_t* mk, uint32_t sh, uint32_t* rd_a /*[NW + 1]*/, uint32_t* mk_a /*[NW + 1]*/) {
+  rd_a[0] = align_word(rd[0], 0u, sh);
+  mk_a[0] = align_word(mk[0], 0u, sh);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int w = 1; w < NW; ++w) {
+    rd_a[w] = align_word(rd[w], rd[w - 1], sh);
+    mk_a[w] = align_word(mk[w], mk[w - 1], sh);
+  }
+  rd_a[NW] = align_word(0u, rd[NW - 1], sh);
+  mk_a[NW] = align_word(0u, mk[NW - 1], sh);
+}
+template <int NW>
+WALT_HD uint32_t count_mismatch_aligned(const uint32_t* g /*[NW + 1]*/, const uint32_t* rd_a, const uint32_t* mk_a, bool top) {
+  uint32_t mm = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int w = 0; w < NW; ++w) {
+    const uint32_t x = g[w] ^ rd_a[w];
+    mm += popc32((x | (x >> 1)) & mk_a[w]);
+  }
+  if (top) {
+    const uint32_t x = g[NW] ^ rd_a[NW];
+    mm += popc32((x | (x >> 1)) & mk_a[NW]);
+  }
+  return mm;
+}
+// An item header is 8 words, the read's words rd[NW], then its masks mk[NW] (map_common.h item_quads).  Word i of the
+// header with both arrays aligned IN PLACE -- rd_a[w] where rd[w] was, mk_a[w] where mk[w] was -- and the two top
+// words behind them: rd_a[NW] at word 8 + 2 NW, mk_a[NW] at 8 + 2 NW + 1.  aligned_header_word: word i < 8 + 2 NW from
+// the header's words i (cur) and i - 1 (below); the first eight words stay, the first word of either array takes
+// nothing from below.  aligned_header_top: the top word from the array's last word (header word 8 + NW - 1 or
+// 8 + 2 NW - 1).
+template <int NW>
+WALT_HD uint32_t aligned_header_word(uint32_t i, uint32_t cur, uint32_t below, uint32_t sh) {
+  const bool first = i == 8u || i == 8u + NW;
+  return align_word(cur, first ? 0u : below, i >= 8u ? sh : 0u);
+}
+WALT_HD uint32_t aligned_header_top(uint32_t last, uint32_t sh) { return align_word(0u, last, sh); }
+
 // bit 2k of word w set for every read offset 16 w + k that holds care character p of seed shift seed_i, p in [p0, p1)
 WALT_HD uint32_t care_mask_word(uint32_t w, uint32_t seed_i, uint32_t p0, uint32_t p1) {
   uint32_t m = 0;

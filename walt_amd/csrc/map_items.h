@@ -388,6 +388,10 @@ __device__ __forceinline__ void item_stream(const IndexView& iv, uint32_t strand
   // for an item that is no tail item
   constexpr bool kTailWide = kPat != 3 && DENSE && NW <= 10 && long_seed_nw<NW>();
   uint32_t tmw[kTailWide ? NW : 1];
+  // the plain dense path: the item's words and masks moved up to where the records hold them (core.h align_read);
+  // the top word is compared only by the items whose last bases reach it (7 words: the record ends with the read)
+  constexpr bool kAligned = DENSE && NW <= Sink::kAlignWords && !kTailWide;  // (kAlignWords <= 8: the sink's kernel says up to where it pays)
+  uint32_t rd_a[kAligned ? NW + 1 : 1], mk_a[kAligned ? NW + 1 : 1];
   auto decode = [&](const uint4& h) {
     id = bcast(h.x, 0); l = bcast(h.y, 0); size = bcast(h.z, 0); rec0 = bcast(h.w, 0);
     len = bcast(h.x, 1); seed_i = bcast(h.y, 1); tail = bcast(h.z, 1);
@@ -413,6 +417,8 @@ __device__ __forceinline__ void item_stream(const IndexView& iv, uint32_t strand
       rd[w] = bcast(va, a >> 2);
       mk[w] = bcast(vc, c >> 2);
     }
+    // (scalar work, once per item: the steps compare the record's words unshifted)
+    if constexpr (kAligned) align_read<NW>(rd, mk, 2 * (kWinLead - seed_i), rd_a, mk_a);
   };
   // the item after it: index (the batch's next, or the first of the batch grabbed meanwhile) and header load
   uint4 hdn = zero;
@@ -493,6 +499,8 @@ __device__ __forceinline__ void item_stream(const IndexView& iv, uint32_t strand
           uint32_t tmm;
           m = count_mismatch_regs2<NW>(wv, 2 * (kWinLead - seed_i), rd, mk, tmw, tmm);
           in = in && tmm == 0 && tail != 2u;  // (tail == 2: the region was proved larger than -b, tail_items_narrow_wide)
+        } else if constexpr (kAligned) {
+          m = count_mismatch_aligned<NW>(wv, rd_a, mk_a, NW != 7 && mk_a[NW] != 0u);  // (uniform)
         } else {
           m = count_mismatch_regs<NW>(wv, 2 * (kWinLead - seed_i), rd, mk);
         }

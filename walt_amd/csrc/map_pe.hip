@@ -751,6 +751,7 @@ struct SurvivorSink {
   uint32_t n_verified;
   uint32_t b, tail, in_region;  // -b (paired.cpp:161-163) for tail items, whose region the lanes count here
   uint32_t grab_next, grab_end;  // this wavefront's stock of pool chunks (wave-uniform): kPoolGrab per visit to the pool's counter
+  static constexpr int kAlignWords = 8;  // item_stream aligns the item's words to the records for up to this many words
   static __device__ __forceinline__ uint32_t strand(uint32_t id) { return ((id >> 24) & 7u) >= 3u ? 1u : 0u; }
   __device__ __forceinline__ void begin(uint32_t id_, uint32_t seed_, uint32_t pos_, uint32_t tail_) {
     id = id_;

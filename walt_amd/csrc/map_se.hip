@@ -1524,6 +1524,9 @@ struct SummarySink {
   LaneBest acc;
   uint32_t in_region;  // this lane's candidates that belong to the region (tail items: whose care characters >= 44 match)
   uint32_t n_verified;
+  // item_stream aligns the item's words to the records for up to this many words (core.h align_read): the 8-word
+  // instance of k_se_verify sits at its six wavefronts' 80 registers and spills four with the ninth aligned word
+  static constexpr int kAlignWords = 7;
   static __device__ __forceinline__ uint32_t strand(uint32_t id) { return id >> 31; }
   __device__ __forceinline__ void begin(uint32_t id_, uint32_t seed_, uint32_t, uint32_t tail_) {
     id = id_; seed_i = seed_; tail = tail_;
@@ -1779,7 +1782,9 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
   __syncthreads();
   const uint32_t n_chrom = iv.n_chrom, top_step = top_step_of(n_chrom);
   const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  // (the wavefront's number said to be uniform: the deal's state -- batch, place in it, the units ahead -- is scalar then)
+  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   uint32_t n_verified = 0;
   if (wave < n_units) {
   uint32_t* const cursor = &sh.ctl[2];
@@ -1791,7 +1796,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
   const uint32_t dealt = n_waves * first_batch;
   auto grab = [&]() {
     uint32_t v = 0;
-    if (lane == 0) v = dealt + atomicAdd(cursor, batch);
+    if (lane == 0) v = atomicAdd(cursor, batch);  // (`dealt` is added where the batch begins: a scalar there)
     return v;
   };
   uint32_t b0 = wave, t = 0, stride = n_waves, cur_batch = first_batch, nb_v = 0;
@@ -1807,7 +1812,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
       ++t;
       ni = b0 + t * stride;
     } else {
-      b0 = (deal & 1u) ? bcast(nb_v, 0) : 0xFFFFFFFFu;
+      b0 = (deal & 1u) ? dealt + bcast(nb_v, 0) : 0xFFFFFFFFu;
       deal = 0u;
       t = 0;
       ni = b0;
@@ -1834,8 +1839,12 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
     e.y = e.y < (uint32_t)R ? e.y : (uint32_t)R;
     return e;
   };
-  const uint32_t rr = lane >> 3, qq = lane & 7u;
   auto headers = [&](const uint2& e) __attribute__((always_inline)) -> uint4 {  // lane 8 r + q: quad q of the unit's r-th item
+    // (the lane's own numbers are made where they are used, once per unit: as loop invariants they would hold registers
+    // through the steps)
+    uint32_t ln = lane;
+    asm volatile("" : "+v"(ln));
+    const uint32_t rr = ln >> 3, qq = ln & 7u;
     uint32_t item = e.x;
     if (e.y > 1u) {  // (uniform)
       const uint32_t p = e.x + (rr < e.y ? rr : 0u);
@@ -1872,10 +1881,44 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
     y.c = load_global(rp + 1);
     if constexpr (NW > 7) y.e = load_global(reinterpret_cast<const uint4*>(sv.win2) + rec);
   };
-  // the current unit, the one after it (entry and headers), and the entry of the one after that
-  uint2 ue = unit_entry(wave);
-  uint4 hv = headers(ue);
-  uint32_t i1 = advance();
+  // The reads of a unit meet every record at a shift that is theirs alone, 2 (kWinLead - seed_i) bits: their words and
+  // masks are moved up by it ONCE, where the unit starts, all R reads in one pass over the header lanes (core.h
+  // aligned_header_word: lane 8 r + q, component c is header word 4 q + c of the r-th read), so that a step compares the
+  // record's words as they were loaded (count_mismatch_aligned) and shifts nothing.
+  auto align_unit = [&](uint4& h) {
+    constexpr uint32_t kWordQuads = (8 + 2 * NW + 3) >> 2;  // the quads that hold the item's words (of the last, 7 words: its first two)
+    uint32_t ln = lane;  // (as in headers)
+    asm volatile("" : "+v"(ln));
+    const uint32_t q = ln & 7u;
+    uint32_t seed_i = (uint32_t)__shfl((int)h.y, (int)((ln & ~7u) | 1u));
+    seed_i = seed_i <= kWinLead ? seed_i : 0u;  // (lanes of no read)
+    const uint32_t sh_read = 2 * (kWinLead - seed_i);
+    const uint32_t shv = q < kWordQuads ? sh_read : 0u;  // (the lanes behind the item's words keep what they hold)
+    const uint32_t below = (uint32_t)__shfl((int)h.w, (int)ln - 1);  // (the top lane: the last mask word; quad 0 takes nothing)
+    uint32_t rd_last = 0;
+    if constexpr (NW > 7) rd_last = (uint32_t)__shfl((int)h.w, (int)((ln & ~7u) | (uint32_t)((8 + NW - 1) >> 2)));
+    // (from the top down: every word takes the bits that left the word below it as that word was)
+    h.w = aligned_header_word<NW>(4 * q + 3, h.w, h.z, shv);
+    h.z = aligned_header_word<NW>(4 * q + 2, h.z, h.y, shv);
+    h.y = aligned_header_word<NW>(4 * q + 1, h.y, h.x, shv);
+    h.x = aligned_header_word<NW>(4 * q + 0, h.x, below, shv);
+    if constexpr (NW > 7) {  // (the 7-word records end where the longest read they take ends: no top word)
+      constexpr uint32_t kTopQuad = (8 + 2 * NW) >> 2;  // the lane of the two top words: behind the item's quads
+      static_assert(((8 + NW - 1) & 3) == 3 && ((8 + 2 * NW) & 3) == 0 && kTopQuad == kWordQuads && kTopQuad < 8,
+                    "the last read and mask words are .w components, the top words the .x and .y of the lane behind them");
+      h.x = q == kTopQuad ? aligned_header_top(rd_last, sh_read) : h.x;
+      h.y = q == kTopQuad ? aligned_header_top(below, sh_read) : h.y;
+    }
+    // (finished here: sunk towards the next step, the shuffled words would stay live across the unit border's own work)
+    asm volatile("" : "+v"(h.x), "+v"(h.y), "+v"(h.z), "+v"(h.w));
+  };
+  // the current unit, the one after it (entry and headers), and the entry of the one after that.  A wavefront starts
+  // on a unit of NO reads with its first unit as the next one: the first step evaluates nothing and takes the unit border
+  // as every later unit does, so the headers are aligned in one place (a second copy of align_unit in front of the loop
+  // cost the loop eight registers and spilled three)
+  uint2 ue = make_uint2(0u, 0u);
+  uint4 hv = zero;
+  uint32_t i1 = wave;
   uint2 ue1 = unit_entry(i1);
   uint4 hv1 = headers(ue1);  // (no unit: item 0's first quad, unused)
   uint32_t i2 = advance();
@@ -1913,18 +1956,18 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
     for (int r = 0; r < R; ++r) {
       if ((uint32_t)r < ue.y) {  // (uniform)
         const uint32_t len = bcast(hv.x, 8 * r + 1), seed_i = bcast(hv.y, 8 * r + 1);
-        uint32_t rd[NW], mk[NW];
+        uint32_t rd[NW + 1], mk[NW + 1];  // aligned (align_unit); the top words behind the masks
 #pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          const int a = 8 + w, c = 8 + NW + w;
+        for (int w = 0; w <= NW; ++w) {
+          const int a = w < NW ? 8 + w : 8 + 2 * NW, c = w < NW ? 8 + NW + w : 8 + 2 * NW + 1;
           const uint32_t va = (a & 3) == 0 ? hv.x : (a & 3) == 1 ? hv.y : (a & 3) == 2 ? hv.z : hv.w;
           const uint32_t vc = (c & 3) == 0 ? hv.x : (c & 3) == 1 ? hv.y : (c & 3) == 2 ? hv.z : hv.w;
-          rd[w] = bcast(va, 8 * r + (a >> 2));
-          mk[w] = bcast(vc, 8 * r + (c >> 2));
+          rd[w] = (w < NW || NW > 7) ? bcast(va, 8 * r + (a >> 2)) : 0u;
+          mk[w] = (w < NW || NW > 7) ? bcast(vc, 8 * r + (c >> 2)) : 0u;
         }
         const uint32_t g = pos - seed_i;
         const bool ok = k < size && (pos - c_lo >= seed_i) && (g + len < c_hi);
-        const uint32_t m = count_mismatch_regs<NW>(wv, 2 * (kWinLead - seed_i), rd, mk);
+        const uint32_t m = count_mismatch_aligned<NW>(wv, rd, mk, NW > 7 && mk[NW] != 0u);  // (uniform)
         n_verified += ok ? 1u : 0u;
         lane_best_add(acc[r], k, ok ? g : 0u, ok ? m : 0xFFFFFFFFu);
       }
@@ -1941,6 +1984,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
       }
       if (hn) {
         ue = ue1; hv = hv1;
+        align_unit(hv);  // (before the next headers are asked for: its registers are free again by then)
         i1 = i2; ue1 = ue2;
         hv1 = headers(ue1);
         i2 = advance();
@@ -1953,8 +1997,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
       base += 64;
     }
   };
-  begin();
-  issue(strand, rec0, size, 0u, bx);
+  begin();  // (size 1: the step of no reads is the unit's last; bx holds zeros, what it would load nobody reads)
   for (;;) {
     step(bx, by);
     if (done) break;

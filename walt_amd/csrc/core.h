@@ -1734,6 +1734,28 @@ WALT_HD uint32_t aligned_header_word(uint32_t i, uint32_t cur, uint32_t below, u
   return align_word(cur, first ? 0u : below, i >= 8u ? sh : 0u);
 }
 WALT_HD uint32_t aligned_header_top(uint32_t last, uint32_t sh) { return align_word(0u, last, sh); }
+// The operands of one read of a unit as the grouped dense verifier keeps them in LDS (map_se.hip k_se_verify_shared): a
+// record of operand_words<NW>() words.  What a step needs lies in front, in whole quads and in the order a step uses it
+// -- the length, the seed shift, then rd_a[w] and mk_a[w] side by side, w = 0 .. NW - 1 and, for NW > 7, the two top
+// words: operand_step_words<NW>() = 16 words for NW = 7, 20 for NW = 8 -- so that a quad is done with once its two or
+// four words are compared; what the unit's end needs lies behind it: the item's id, then its `tail`.  operand_slot: the
+// place of word i of the aligned header (aligned_header_word) in the record, kNoOperand for a word that is not kept.
+constexpr uint32_t kNoOperand = 0xFFFFFFFFu;
+template <int NW>
+constexpr uint32_t operand_step_words() { return 2u + 2u * NW + (NW > 7 ? 2u : 0u); }
+template <int NW>
+constexpr uint32_t operand_words() { return (operand_step_words<NW>() + 2u + 3u) & ~3u; }
+template <int NW>
+WALT_HD constexpr uint32_t operand_slot(uint32_t i) {
+  return i == 0u ? operand_step_words<NW>()                                             // id
+         : i == 4u ? 0u                                                                  // length
+         : i == 5u ? 1u                                                                  // seed shift
+         : i == 6u ? operand_step_words<NW>() + 1u                                       // tail
+         : (i >= 8u && i < 8u + NW) ? 2u + 2u * (i - 8u)                                 // rd_a[i - 8]
+         : (i >= 8u + NW && i < 8u + 2u * NW) ? 3u + 2u * (i - 8u - NW)                  // mk_a[i - 8 - NW]
+         : (NW > 7 && (i == 8u + 2u * NW || i == 9u + 2u * NW)) ? 2u + i - 8u            // the top words
+                                                                 : kNoOperand;
+}
 
 // bit 2k of word w set for every read offset 16 w + k that holds care character p of seed shift seed_i, p in [p0, p1)
 WALT_HD uint32_t care_mask_word(uint32_t w, uint32_t seed_i, uint32_t p0, uint32_t p1) {

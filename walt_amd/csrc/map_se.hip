@@ -1750,7 +1750,8 @@ __global__ __launch_bounds__(kBlock) void k_se_share_cut(HeavyStage hs, SeShare 
 // The units of a (chunk, round), one per wavefront: the region's records streamed once (item_stream's two record
 // buffers, every step the same loads), every step evaluated for the unit's reads.  What depends on the record alone --
 // the edge bit, the chromosome bounds, the words -- is done once per step; a read brings its seed shift, length, words
-// and masks, wave-uniform, read out of the lanes that loaded its header (lane 8 r + q: quad q of the unit's r-th item).
+// and masks, the same for all lanes: aligned once per unit in the lanes that loaded its header (lane 8 r + q: quad q of
+// the unit's r-th item), kept in a per-wavefront LDS area and read back by every step (core.h operand_slot).
 // Units in the numbering of the launch: the large ones (dealt round robin, as item_stream deals), the others, then
 // one per item behind the grouped ones.
 template <int NW, int R>
@@ -1783,7 +1784,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
   const uint32_t n_chrom = iv.n_chrom, top_step = top_step_of(n_chrom);
   const uint32_t lane = threadIdx.x & 63;
   // (the wavefront's number said to be uniform: the deal's state -- batch, place in it, the units ahead -- is scalar then)
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+  const uint32_t n_waves = (uint32_t)__builtin_amdgcn_readfirstlane((int)((gridDim.x * blockDim.x) >> 6));
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
   uint32_t n_verified = 0;
   if (wave < n_units) {
@@ -1792,8 +1793,12 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
   const bool many = n_units >= 32 * n_waves;
   uint32_t batch = many ? n_units / (4 * n_waves) : 2u;
   batch = batch > kVerifyBatchMax ? kVerifyBatchMax : batch;
-  const uint32_t first_batch = many ? batch : (uint32_t)((3ull * n_units + 4ull * n_waves - 1) / (4ull * n_waves));
-  const uint32_t dealt = n_waves * first_batch;
+  uint32_t first_batch = many ? batch : (uint32_t)((3ull * n_units + 4ull * n_waves - 1) / (4ull * n_waves));
+  // (the quotients come out of the vector unit: said to be uniform, they and the deal's state after them are scalars --
+  // a dozen vector registers less, which is what lets a read's operands be vector registers without a spill)
+  batch = (uint32_t)__builtin_amdgcn_readfirstlane((int)batch);
+  first_batch = (uint32_t)__builtin_amdgcn_readfirstlane((int)first_batch);
+  const uint32_t dealt = (uint32_t)__builtin_amdgcn_readfirstlane((int)(n_waves * first_batch));
   auto grab = [&]() {
     uint32_t v = 0;
     if (lane == 0) v = atomicAdd(cursor, batch);  // (`dealt` is added where the batch begins: a scalar there)
@@ -1912,12 +1917,49 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
     // (finished here: sunk towards the next step, the shuffled words would stay live across the unit border's own work)
     asm volatile("" : "+v"(h.x), "+v"(h.y), "+v"(h.z), "+v"(h.w));
   };
+  // A unit's aligned operands, per wavefront, in LDS (core.h operand_slot: one record of kOpWords words per read, what a
+  // step needs in its first kOpStep / 4 quads): written once per unit by the lanes that hold the aligned headers, read
+  // back in every step at an address all lanes share, which broadcasts.  The reads are LDS instructions beside the record
+  // loads, not lane reads on the vector unit, and the headers are not live across the steps.  The area is the
+  // wavefront's own and a wavefront's LDS instructions execute in order: a fence of wavefront scope orders the accesses
+  // for the compiler, and the wavefronts of a block, which run different numbers of units, never wait for each other.
+  constexpr uint32_t kOpWords = operand_words<NW>(), kOpStep = operand_step_words<NW>();
+  static_assert(kOpStep % 4 == 0 && kOpWords % 4 == 0 && operand_slot<NW>(8) == 2 && operand_slot<NW>(8 + NW) == 3 &&
+                    operand_slot<NW>(8 + 2 * NW - 1) == 2 * NW + 1 && operand_slot<NW>(6) == kOpStep + 1 &&
+                    operand_slot<NW>(8 + 2 * NW + 1) == (NW > 7 ? kOpStep - 1 : kNoOperand),
+                "a step's operands are whole quads, the top words kept only where there are top words");
+  __shared__ __attribute__((aligned(16))) uint32_t s_ops[kBlock / 64][R * kOpWords];
+  uint32_t* const ops = s_ops[threadIdx.x >> 6];
+  auto store_unit = [&](const uint4& h) {  // (all R records, also those of no read: a step may ask for the record behind its read's)
+    uint32_t ln = lane;  // (as in headers)
+    asm volatile("" : "+v"(ln));
+    const uint32_t rr = ln >> 3, q = ln & 7u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // (behind the last unit's reads)
+    if (rr < (uint32_t)R) {
+      const uint32_t v[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+      for (uint32_t c = 0; c < 4; ++c) {
+        const uint32_t slot = operand_slot<NW>(4 * q + c);
+        if (slot != kNoOperand) ops[rr * kOpWords + slot] = v[c];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  // A read asks for its own operands, all quads at once, and compares as they arrive (counted waits).  Asking one read
+  // ahead -- the loads held in front of the previous read's compare -- was built and measured: 95 registers instead of 84
+  // and the same kernel time, the other wavefronts of the SIMD cover the LDS latency.
+  typedef uint32_t OpQuad __attribute__((ext_vector_type(4)));
+  constexpr int kOpQuads = (int)(kOpStep / 4);
+  auto load_quad = [&](int r, int j) -> OpQuad {
+    return *reinterpret_cast<const OpQuad*>(ops + (uint32_t)r * kOpWords + 4u * (uint32_t)j);
+  };
   // the current unit, the one after it (entry and headers), and the entry of the one after that.  A wavefront starts
   // on a unit of NO reads with its first unit as the next one: the first step evaluates nothing and takes the unit border
   // as every later unit does, so the headers are aligned in one place (a second copy of align_unit in front of the loop
   // cost the loop eight registers and spilled three)
   uint2 ue = make_uint2(0u, 0u);
-  uint4 hv = zero;
   uint32_t i1 = wave;
   uint2 ue1 = unit_entry(i1);
   uint4 hv1 = headers(ue1);  // (no unit: item 0's first quad, unused)
@@ -1925,7 +1967,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
   uint2 ue2 = unit_entry(i2);
   LaneBest acc[R];
   uint32_t strand = 0, size = 1, rec0 = 0, base = 0;
-  auto begin = [&]() {
+  auto begin = [&](const uint4& hv) {  // hv: the unit's headers
     strand = bcast(hv.x, 0) >> 31; size = bcast(hv.z, 0); rec0 = bcast(hv.w, 0);
     size = size ? size : 1u;
 #pragma unroll
@@ -1955,19 +1997,24 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if ((uint32_t)r < ue.y) {  // (uniform)
-        const uint32_t len = bcast(hv.x, 8 * r + 1), seed_i = bcast(hv.y, 8 * r + 1);
-        uint32_t rd[NW + 1], mk[NW + 1];  // aligned (align_unit); the top words behind the masks
+        OpQuad oq[kOpQuads];
 #pragma unroll
-        for (int w = 0; w <= NW; ++w) {
-          const int a = w < NW ? 8 + w : 8 + 2 * NW, c = w < NW ? 8 + NW + w : 8 + 2 * NW + 1;
-          const uint32_t va = (a & 3) == 0 ? hv.x : (a & 3) == 1 ? hv.y : (a & 3) == 2 ? hv.z : hv.w;
-          const uint32_t vc = (c & 3) == 0 ? hv.x : (c & 3) == 1 ? hv.y : (c & 3) == 2 ? hv.z : hv.w;
-          rd[w] = (w < NW || NW > 7) ? bcast(va, 8 * r + (a >> 2)) : 0u;
-          mk[w] = (w < NW || NW > 7) ? bcast(vc, 8 * r + (c >> 2)) : 0u;
-        }
+        for (int j = 0; j < kOpQuads; ++j) oq[j] = load_quad(r, j);
+        const uint32_t len = oq[0].x, seed_i = oq[0].y;
         const uint32_t g = pos - seed_i;
         const bool ok = k < size && (pos - c_lo >= seed_i) && (g + len < c_hi);
-        const uint32_t m = count_mismatch_aligned<NW>(wv, rd, mk, NW > 7 && mk[NW] != 0u);  // (uniform)
+        uint32_t m = 0;  // count_mismatch_aligned on the words as they lie in the quads
+#pragma unroll
+        for (int j = 0; j < kOpQuads; ++j) {
+#pragma unroll
+          for (int c = j ? 0 : 2; c < 4; c += 2) {
+            const int w = (4 * j + c - 2) >> 1;  // (w = NW: the top words behind the masks)
+            const uint32_t x = wv[w] ^ oq[j][c], mk_w = oq[j][c + 1];
+            const uint32_t mm_w = popc32((x | (x >> 1)) & mk_w);
+            // (the top word counts where the read reaches it -- uniform: every lane read the same mask)
+            if (w < NW || __builtin_amdgcn_readfirstlane((int)mk_w) != 0) m += mm_w;
+          }
+        }
         n_verified += ok ? 1u : 0u;
         lane_best_add(acc[r], k, ok ? g : 0u, ok ? m : 0xFFFFFFFFu);
       }
@@ -1976,20 +2023,22 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if ((uint32_t)r < ue.y) {  // (uniform) SummarySink::end for the unit's r-th item
-          const uint32_t id = bcast(hv.x, 8 * r), seed_i = bcast(hv.y, 8 * r + 1), tail = bcast(hv.z, 8 * r + 1);
+          const uint32_t id = ops[r * kOpWords + kOpStep], seed_i = ops[r * kOpWords + 1], tail = ops[r * kOpWords + kOpStep + 1];
           uint4 res = lane_best_reduce(acc[r]);
           if (tail && size > b) res = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);  // (every slot of these instances' regions belongs to it)
           if (lane == 0) hs.sums[(uint64_t)((id >> 31) ? 1u + seed_i : 0u) * hs.hcap + (id & 0x7FFFFFFFu)] = res;
         }
       }
       if (hn) {
-        ue = ue1; hv = hv1;
+        ue = ue1;
+        uint4 hv = hv1;
+        begin(hv);
         align_unit(hv);  // (before the next headers are asked for: its registers are free again by then)
+        store_unit(hv);
         i1 = i2; ue1 = ue2;
         hv1 = headers(ue1);
         i2 = advance();
         ue2 = unit_entry(i2);
-        begin();
       } else {
         done = true;
       }
@@ -1997,7 +2046,7 @@ __global__ __launch_bounds__(kBlock, NW > 7 ? 4 : 5) void k_se_verify_shared(
       base += 64;
     }
   };
-  begin();  // (size 1: the step of no reads is the unit's last; bx holds zeros, what it would load nobody reads)
+  begin(zero);  // (size 1: the step of no reads is the unit's last; bx holds zeros, what it would load nobody reads)
   for (;;) {
     step(bx, by);
     if (done) break;

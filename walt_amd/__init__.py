@@ -1299,18 +1299,21 @@ class MBias:
             pass
 
 
-class CpgPairs:
-    """Adjacent-CpG state pairs of an Index (include/walt_amd.h, "adjacent CpG pairs"): for every two neighbouring CpG
-    pairs of the genome, how often one read called them MM, MU, UM, UU -- exact 32-bit counters on the index's device,
-    keyed by the number of the lower pair.  Close it before the index."""
+class _CpgTable:
+    """What CpgPairs and Epialleles share: a table keyed by CpG pair number on an Index's device (the C functions
+    walt_<_prefix>_*).  Close it before the index."""
+    _prefix = None
 
     def __init__(self, index):
         self._index = index
         self._L = index._L
         self._h = None
         h = ctypes.c_void_p()
-        index._ck(self._L.walt_cpgpairs_create(index._h, ctypes.byref(h)))
+        index._ck(self._fn("create")(index._h, ctypes.byref(h)))
         self._h = h
+
+    def _fn(self, name):
+        return getattr(self._L, "walt_%s_%s" % (self._prefix, name))
 
     def add(self, calls, offsets, records, skip=None):
         """calls: the uint8 array Index.meth_call_batch returned (indexed from offsets[0]); offsets: n + 1; records: a
@@ -1322,127 +1325,82 @@ class CpgPairs:
         records, rec_ptr, rec_stride = _records_arg(records, n)
         skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
         calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
-        self._index._ck(self._L.walt_cpgpairs_batch(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
+        self._index._ck(self._fn("batch")(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
 
     def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, stream=0):
         """Device-pointer form (ints are HBM addresses on the index's device, stream a hipStream_t value); asynchronous."""
-        self._index._ck(self._L.walt_cpgpairs_batch_device(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride), d_skip,
-                                                           int(skip_stride), stream))
+        self._index._ck(self._fn("batch_device")(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride), d_skip,
+                                                 int(skip_stride), stream))
+
+    def _extract(self, dtype, *args):
+        """extract(*args, out, cap, n_out) twice: for the count, then into an array of `dtype`."""
+        n = ctypes.c_uint64(0)
+        rc = self._fn("extract")(self._h, *args, None, 0, ctypes.byref(n))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        sites = np.zeros(n.value, dtype=dtype)
+        if n.value:
+            self._index._ck(self._fn("extract")(self._h, *args, _ptr(sites), n.value, ctypes.byref(n)))
+        return sites
+
+    @property
+    def n_pairs(self):
+        return int(self._fn("n_pairs")(self._h))
+
+    def clear(self):
+        self._index._ck(self._fn("clear")(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def device_bytes(self):
+        return self._fn("device_bytes")(self._h)
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CpgPairs(_CpgTable):
+    """Adjacent-CpG state pairs of an Index (include/walt_amd.h, "adjacent CpG pairs"): for every two neighbouring CpG
+    pairs of the genome, how often one read called them MM, MU, UM, UU -- exact 32-bit counters on the index's device,
+    keyed by the number of the lower pair.  Close it before the index."""
+    _prefix = "cpgpairs"
 
     def extract(self, pos_lo=0, pos_hi=None):
         """The non-zero entries whose lower pair starts in the forward positions [pos_lo, pos_hi), ascending:
         cpgpair_site_dtype[n] (pos, next, n[4] = MM, MU, UM, UU)."""
         pos_hi = self._index.genome_len if pos_hi is None else pos_hi
-        n = ctypes.c_uint64(0)
-        rc = self._L.walt_cpgpairs_extract(self._h, int(pos_lo), int(pos_hi), None, 0, ctypes.byref(n))
-        if rc != WALT_OK and n.value == 0:
-            self._index._ck(rc)
-        sites = np.zeros(n.value, dtype=cpgpair_site_dtype)
-        if n.value:
-            self._index._ck(self._L.walt_cpgpairs_extract(self._h, int(pos_lo), int(pos_hi), _ptr(sites), n.value, ctypes.byref(n)))
-        return sites
+        return self._extract(cpgpair_site_dtype, int(pos_lo), int(pos_hi))
 
     def extract_device(self, pos_lo, pos_hi, d_out, cap, d_n_out, stream=0):
         """Device-pointer form (walt_cpgpairs_extract_device); asynchronous."""
         self._index._ck(self._L.walt_cpgpairs_extract_device(self._h, int(pos_lo), int(pos_hi), d_out, int(cap), d_n_out, stream))
 
-    @property
-    def n_pairs(self):
-        return int(self._L.walt_cpgpairs_n_pairs(self._h))
 
-    def clear(self):
-        self._index._ck(self._L.walt_cpgpairs_clear(self._h))
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def device_bytes(self):
-        return self._L.walt_cpgpairs_device_bytes(self._h)
-
-    def close(self):
-        if self._h:
-            self._L.walt_cpgpairs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Epialleles:
+class Epialleles(_CpgTable):
     """Four-CpG epialleles of an Index (include/walt_amd.h, "four-CpG epialleles"): for every four neighbouring CpG pairs
     of the genome, how often one read showed each of their 16 methylation patterns (column 8 u0 + 4 u1 + 2 u2 + u3, u = 1
     unmethylated, the lowest position first) -- exact 32-bit counters on the index's device, keyed by the number of the
-    lowest pair.  Close it before the index."""
-
-    def __init__(self, index):
-        self._index = index
-        self._L = index._L
-        self._h = None
-        h = ctypes.c_void_p()
-        index._ck(self._L.walt_epialleles_create(index._h, ctypes.byref(h)))
-        self._h = h
-
-    def add(self, calls, offsets, records, skip=None):
-        """CpgPairs.add's arguments.  Waits for the result."""
-        calls = np.ascontiguousarray(calls, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = offsets.size - 1
-        records, rec_ptr, rec_stride = _records_arg(records, n)
-        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
-        calls_ptr = calls.ctypes.data - int(offsets[0]) if n else None
-        self._index._ck(self._L.walt_epialleles_batch(self._h, calls_ptr, _ptr(offsets), n, rec_ptr, rec_stride, skip_ptr, skip_stride))
-
-    def add_device(self, d_calls, d_offsets, n, d_records, record_stride=16, d_skip=None, skip_stride=1, stream=0):
-        """Device-pointer form (ints are HBM addresses on the index's device, stream a hipStream_t value); asynchronous."""
-        self._index._ck(self._L.walt_epialleles_batch_device(self._h, d_calls, d_offsets, int(n), d_records, int(record_stride),
-                                                             d_skip, int(skip_stride), stream))
+    lowest pair.  add and add_device take CpgPairs's arguments.  Close it before the index."""
+    _prefix = "epialleles"
 
     def extract(self, pos_lo=0, pos_hi=None, min_total=1):
         """The entries whose lowest pair starts in the forward positions [pos_lo, pos_hi) and whose sixteen counters sum
         to at least min_total (>= 1), ascending: epiallele_site_dtype[n] (pos, last, n[16])."""
         pos_hi = self._index.genome_len if pos_hi is None else pos_hi
-        n = ctypes.c_uint64(0)
-        rc = self._L.walt_epialleles_extract(self._h, int(pos_lo), int(pos_hi), int(min_total), None, 0, ctypes.byref(n))
-        if rc != WALT_OK and n.value == 0:
-            self._index._ck(rc)
-        sites = np.zeros(n.value, dtype=epiallele_site_dtype)
-        if n.value:
-            self._index._ck(self._L.walt_epialleles_extract(self._h, int(pos_lo), int(pos_hi), int(min_total), _ptr(sites), n.value,
-                                                            ctypes.byref(n)))
-        return sites
+        return self._extract(epiallele_site_dtype, int(pos_lo), int(pos_hi), int(min_total))
 
     def extract_device(self, pos_lo, pos_hi, min_total, d_out, cap, d_n_out, stream=0):
         """Device-pointer form (walt_epialleles_extract_device); asynchronous."""
         self._index._ck(self._L.walt_epialleles_extract_device(self._h, int(pos_lo), int(pos_hi), int(min_total), d_out, int(cap),
                                                                d_n_out, stream))
-
-    @property
-    def n_pairs(self):
-        return int(self._L.walt_epialleles_n_pairs(self._h))
-
-    def clear(self):
-        self._index._ck(self._L.walt_epialleles_clear(self._h))
-
-    @property
-    def handle(self):
-        return self._h
-
-    @property
-    def device_bytes(self):
-        return self._L.walt_epialleles_device_bytes(self._h)
-
-    def close(self):
-        if self._h:
-            self._L.walt_epialleles_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -165,11 +165,27 @@ WALT_HD void cpg_slice(const uint32_t w[4], int i0, Number&& number, Add&& add, 
   }
 }
 
+// The pair table's fold, as k_cpg_fold, the extraction and cpg_fold_read take a fold: the columns of an entry, the fold of
+// a slice, how two stretches meet, and what the call(s) in front of a slice -- `carry` from earlier trips, then `left`
+// from the lanes in front of it -- add with the slice's first call.  (epialleles_core.h has the other one, EpiFold.)
+struct CpgPairFold {
+  static constexpr uint32_t kColumns = 4;
+  template <class Number, class Add>
+  static WALT_HD void slice(const uint32_t w[4], int i0, Number&& number, Add&& add, unsigned long long& first, unsigned long long& last) {
+    cpg_slice(w, i0, number, add, first, last);
+  }
+  static WALT_HD unsigned long long combine(unsigned long long a, unsigned long long b) { return cpg_combine(a, b); }
+  template <class Add>
+  static WALT_HD void straddle(unsigned long long carry, unsigned long long left, unsigned long long first, Add&& add) {
+    cpg_couple(cpg_combine(carry, left), first, add);
+  }
+};
+
 // One read as a group of the kernel takes it, on one thread: per trip the eight lanes' slices, each lane's incoming call
-// by the scan the three cross-lane steps make (lane s after step d holds the rightmost call of lanes s - 2 d + 1 .. s),
-// the trip's last call carried to the next.  before / after: as in mbias_load_slice.
-template <class Number, class Add>
-WALT_HD void cpg_read(const uint8_t* __restrict__ rb, int len, uint64_t before, uint64_t after, Number&& number, Add&& add) {
+// (chain) by the scan the three cross-lane steps make (lane s after step d holds the fold of slices s - 2 d + 1 .. s),
+// the trip's fold carried to the next.  before / after: as in mbias_load_slice.
+template <class Fold, class Number, class Add>
+WALT_HD void cpg_fold_read(const uint8_t* __restrict__ rb, int len, uint64_t before, uint64_t after, Number&& number, Add&& add) {
   const int head = (int)((uintptr_t)rb & 15u);
   const int trips = nonconv_trips(len, head);
   unsigned long long carry = 0ull;
@@ -181,15 +197,19 @@ WALT_HD void cpg_read(const uint8_t* __restrict__ rb, int len, uint64_t before, 
       if (i0 < len) {
         uint32_t w[4];
         mbias_load_slice(rb, len, i0, before, after, w);
-        cpg_slice(w, i0, number, add, first[sub], incl[sub]);
+        Fold::slice(w, i0, number, add, first[sub], incl[sub]);
       }
     }
     for (int d = 1; d < (int)kCpgGroup; d <<= 1)
-      for (int sub = (int)kCpgGroup - 1; sub >= d; --sub) incl[sub] = cpg_combine(incl[sub - d], incl[sub]);
-    for (int sub = 0; sub < (int)kCpgGroup; ++sub)
-      cpg_couple(cpg_combine(carry, sub ? incl[sub - 1] : 0ull), first[sub], add);
-    carry = cpg_combine(carry, incl[kCpgGroup - 1]);
+      for (int sub = (int)kCpgGroup - 1; sub >= d; --sub) incl[sub] = Fold::combine(incl[sub - d], incl[sub]);
+    for (int sub = 0; sub < (int)kCpgGroup; ++sub) Fold::straddle(carry, sub ? incl[sub - 1] : 0ull, first[sub], add);
+    carry = Fold::combine(carry, incl[kCpgGroup - 1]);
   }
+}
+// the pair table's model under the name its CPU harness (tests/cpgpairs_harness.cpp) calls
+template <class Number, class Add>
+WALT_HD void cpg_read(const uint8_t* __restrict__ rb, int len, uint64_t before, uint64_t after, Number&& number, Add&& add) {
+  cpg_fold_read<CpgPairFold>(rb, len, before, after, number, add);
 }
 
 }  // namespace walt

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -136,10 +137,12 @@ struct walt_mbias {
   unsigned long long* tabs = nullptr;
 };
 
-// Adjacent CpG pairs (cpgpairs.hip): one bit per forward position that starts a pair (n_words words, the zero padding
-// included), the pairs in front of every block of 128 positions, the table count[n_pairs][4] and the extraction's block
-// offsets.
-struct walt_cpgpairs {
+// A table keyed by CpG pair number (cpgpairs.hip): one bit per forward position that starts a pair (n_words words, the
+// zero padding included), the pairs in front of every block of 128 positions, the table count[n_pairs][columns] and the
+// extraction's block offsets.  The two public tables are this with 4 columns (adjacent CpG pairs) and with 16 (four-CpG
+// epialleles); each has its own bitmap and directory.
+namespace walt {
+struct CpgTable {
   walt_index* idx = nullptr;
   uint32_t* bits = nullptr;
   uint32_t* dir = nullptr;
@@ -149,23 +152,14 @@ struct walt_cpgpairs {
   uint32_t n_pairs = 0;
   uint64_t device_bytes = 0;
 };
-
-// Four-CpG epialleles (epialleles.hip): its own pair bitmap and directory, built as walt_cpgpairs's, the table
-// count[n_pairs][16] and the extraction's block offsets.
-struct walt_epialleles {
-  walt_index* idx = nullptr;
-  uint32_t* bits = nullptr;
-  uint32_t* dir = nullptr;
-  uint32_t* table = nullptr;
-  unsigned long long* scan = nullptr;
-  uint64_t n_words = 0;
-  uint32_t n_pairs = 0;
-  uint64_t device_bytes = 0;
-};
+}  // namespace walt
+struct walt_cpgpairs : walt::CpgTable {};
+struct walt_epialleles : walt::CpgTable {};
 
 namespace walt {
-// mbias.hip: one batch of calls as the bias kernel reads it (device arrays), and the kernel on `stream`
-struct MbiasBatch {
+// One batch of calls as the kernels that consume calls read it (k_mbias, k_cpg_fold, k_nonconv without the skip bytes):
+// device arrays in a launch, the caller's host arrays in calls_host_batch.
+struct CallsBatch {
   const void *calls, *offsets;
   uint32_t n;
   const void* records;
@@ -173,11 +167,25 @@ struct MbiasBatch {
   const void* skip;  // null: none
   size_t skip_stride;
 };
-int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream);
-// cpgpairs.hip: the pair kernel over the same batch on `stream` of the table's index's device
-int cpgpairs_launch(walt_cpgpairs* ap, const MbiasBatch& b, hipStream_t stream);
-// epialleles.hip: the window kernel over the same batch on `stream` of the table's index's device
-int epialleles_launch(walt_epialleles* ep, const MbiasBatch& b, hipStream_t stream);
+// the same as a kernel takes it: the first member of its argument struct
+struct CallsView {
+  const uint8_t* calls;
+  const uint64_t* offsets;
+  uint32_t n;
+  const uint8_t* records;
+  uint64_t rec_stride;
+  const uint8_t* skip;         // null: none
+  uint64_t skip_stride;
+};
+inline CallsView calls_view(const CallsBatch& b) {
+  return {static_cast<const uint8_t*>(b.calls), static_cast<const uint64_t*>(b.offsets), b.n, static_cast<const uint8_t*>(b.records),
+          b.rec_stride, static_cast<const uint8_t*>(b.skip), b.skip_stride};
+}
+// mbias.hip: the bias kernel over a batch on `stream`
+int mbias_launch(walt_mbias* mb, uint32_t table, const CallsBatch& b, hipStream_t stream);
+// cpgpairs.hip: the fold kernel of either table over the same batch on `stream` of the table's index's device
+int cpgpairs_launch(walt_cpgpairs* ap, const CallsBatch& b, hipStream_t stream);
+int epialleles_launch(walt_epialleles* ep, const CallsBatch& b, hipStream_t stream);
 
 // nonconv.hip: one batch of calls as the judging kernel reads it (device arrays; tally null: not wanted), the kernel on
 // `stream` of idx's device, what every form refuses of a rule and a filt array (empty: nothing), and the end of a host
@@ -214,6 +222,73 @@ struct DeviceTemp {
     return WALT_OK;
   }
 };
+
+// What the device forms of the calls consumers refuse of a batch's arrays (`who`: the call).  out: null, or the two
+// arrays walt_nonconv_batch_device writes besides, {filt, tally}.
+inline int calls_device_check(const std::string& who, const CallsBatch& b, const void* const* out = nullptr) {
+  if (b.n && (!b.calls || !b.offsets || !b.records || (out && !out[0])))
+    return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets" + (out ? ", records or filt)" : " or records)"));
+  if (((uintptr_t)b.records & 3u) || ((uintptr_t)b.offsets & 7u) || (out && ((uintptr_t)out[1] & 7u)))
+    return fail(WALT_EINVAL, who + ": records must be 4-byte aligned, offsets " + (out ? "and tally " : "") + "8-byte aligned");
+  return WALT_OK;
+}
+
+// The host form of a calls consumer after its own refusals: h holds the caller's host arrays (no alignment is asked of
+// them; the device copies are aligned).  The calls from the first read's on, the offsets relative to it, the records
+// and skip bytes packed as the kernels read them (the caller's strides stay on the host) go to temporaries on `device`;
+// launch(device batch) queues the work on the null stream, which is waited for.  any_length: offsets need only be
+// non-decreasing (walt_nonconv_batch, which also wants `filt`); else scan_offsets's rule, no read above 1024 calls.
+template <class Launch>
+inline int calls_host_batch(const std::string& who, const char* what, const CallsBatch& h, bool any_length, const void* filt,
+                            int device, Launch&& launch) {
+  if (h.n == 0) return WALT_OK;
+  const uint64_t* offsets = static_cast<const uint64_t*>(h.offsets);
+  const uint32_t n = h.n;
+  if (!offsets || !h.records || (any_length && !filt) || (!h.calls && offsets[n] > offsets[0]))
+    return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets" + (any_length ? ", records or filt)" : " or records)"));
+  if (any_length) {
+    for (uint32_t i = 0; i < n; ++i)
+      if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, who + ": offsets not non-decreasing");
+  } else {
+    uint32_t max_len = 0;
+    if (const char* bad = scan_offsets(offsets, n, &max_len)) return fail(WALT_EINVAL, who + ": " + bad);
+  }
+  WALT_HIP(hipSetDevice(device));
+  const uint64_t nbytes = offsets[n] - offsets[0];
+  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(h.records, h.rec_stride, n);
+  const std::vector<uint8_t> sk = pack_strided<uint8_t>(h.skip, h.skip_stride, h.skip ? n : 0);
+  std::vector<uint64_t> rel;
+  const uint64_t* off = rebase_offsets(offsets, n, rel);
+  DeviceTemp d_calls, d_off, d_rec, d_skip;
+  int rc;
+  if ((rc = d_calls.put(nbytes ? static_cast<const char*>(h.calls) + offsets[0] : nullptr, nbytes, what)) ||
+      (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) || (rc = d_rec.put(rec.data(), (size_t)n * 16, what)) ||
+      (h.skip && (rc = d_skip.put(sk.data(), n, what))))
+    return rc;
+  if ((rc = launch(CallsBatch{d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1}))) return rc;
+  WALT_HIP(hipStreamSynchronize(nullptr));
+  return WALT_OK;
+}
+
+// what every call over a range of forward positions refuses of its object (a pile-up, a CpgTable: `noun`) and the range
+template <class T>
+inline int range_refusal(const T* obj, const char* who, const char* noun, uint32_t pos_lo, uint32_t pos_hi) {
+  if (!obj) return fail(WALT_EINVAL, std::string(who) + ": bad argument (null " + noun + ")");
+  const uint32_t genome_len = obj->idx->head.genome_len;
+  if (pos_lo <= pos_hi && pos_hi <= genome_len) return WALT_OK;
+  return fail(WALT_EINVAL, std::string(who) + ": range [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) +
+                               ") is not inside the genome's " + std::to_string(genome_len) + " positions");
+}
+
+// The blocks of an extraction over `range` units (positions, bitmap words): option pile_extract_blocks, else one per
+// `tile` units up to eight per CU; at least one, at most max_blocks and one per unit.  *chunk: units per block.
+inline uint32_t extract_blocks(const walt_index* idx, uint64_t range, uint32_t tile, uint32_t max_blocks, uint64_t* chunk) {
+  uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks
+                                               : std::min<uint64_t>((range + tile - 1) / tile, (uint64_t)idx->n_cu * 8);
+  want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, max_blocks), std::max<uint64_t>(range, 1)));
+  *chunk = (range + want - 1) / want;
+  return (uint32_t)want;
+}
 
 // grow-only device buffer `slot` of idx (freed by walt_index_close)
 inline hipError_t host_api_buffer(walt_index* idx, int slot, size_t bytes, void** out) {

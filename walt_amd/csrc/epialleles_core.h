@@ -114,31 +114,24 @@ WALT_HD void epi_straddle(unsigned long long in, unsigned long long head, Add&& 
   if (in && head) (void)epi_replay(in, head, add);
 }
 
-// One read as a group of the kernel takes it, on one thread: per trip the eight lanes' slices, each lane's incoming chain
-// by the scan the three cross-lane steps make (lane s after step d holds chain(slices s - 2 d + 1 .. s)), the trip's
-// chain carried to the next.  before / after: as in mbias_load_slice.
+// The epiallele table's fold (cpgpairs_core.h CpgPairFold has the shape; cpg_fold_read<EpiFold> is the one-thread model
+// of the kernel).  A slice without a call with a pair ends no window: its straddle costs no combine.
+struct EpiFold {
+  static constexpr uint32_t kColumns = kEpiColumns;
+  template <class Number, class Add>
+  static WALT_HD void slice(const uint32_t w[4], int i0, Number&& number, Add&& add, unsigned long long& head, unsigned long long& tail) {
+    epi_slice(w, i0, number, add, head, tail);
+  }
+  static WALT_HD unsigned long long combine(unsigned long long a, unsigned long long b) { return epi_combine(a, b); }
+  template <class Add>
+  static WALT_HD void straddle(unsigned long long carry, unsigned long long left, unsigned long long head, Add&& add) {
+    if (head) epi_straddle(epi_combine(carry, left), head, add);
+  }
+};
+// the epiallele table's model under the name its CPU harness (tests/epialleles_harness.cpp) calls
 template <class Number, class Add>
 WALT_HD void epi_read(const uint8_t* __restrict__ rb, int len, uint64_t before, uint64_t after, Number&& number, Add&& add) {
-  const int head = (int)((uintptr_t)rb & 15u);
-  const int trips = nonconv_trips(len, head);
-  unsigned long long carry = 0ull;
-  for (int t = 0; t < trips; ++t) {
-    unsigned long long first[kCpgGroup], incl[kCpgGroup];
-    for (int sub = 0; sub < (int)kCpgGroup; ++sub) {
-      const int i0 = -head + 16 * ((int)kCpgGroup * t + sub);
-      first[sub] = incl[sub] = 0ull;
-      if (i0 < len) {
-        uint32_t w[4];
-        mbias_load_slice(rb, len, i0, before, after, w);
-        epi_slice(w, i0, number, add, first[sub], incl[sub]);
-      }
-    }
-    for (int d = 1; d < (int)kCpgGroup; d <<= 1)
-      for (int sub = (int)kCpgGroup - 1; sub >= d; --sub) incl[sub] = epi_combine(incl[sub - d], incl[sub]);
-    for (int sub = 0; sub < (int)kCpgGroup; ++sub)
-      epi_straddle(epi_combine(carry, sub ? incl[sub - 1] : 0ull), first[sub], add);
-    carry = epi_combine(carry, incl[kCpgGroup - 1]);
-  }
+  cpg_fold_read<EpiFold>(rb, len, before, after, number, add);
 }
 
 }  // namespace walt

@@ -20,13 +20,7 @@ constexpr uint32_t kMbiasMaxTables = 8;
 static_assert(kMbiasPositions == WALT_MBIAS_POSITIONS && kMbiasWords == WALT_MBIAS_WORDS, "the header's table is mbias_core.h's");
 
 struct MbiasArgs {
-  const uint8_t* calls;
-  const uint64_t* offsets;
-  uint32_t n;
-  const uint8_t* records;
-  uint64_t rec_stride;
-  const uint8_t* skip;         // null: none
-  uint64_t skip_stride;
+  CallsView v;
   unsigned long long* tabs;    // the kMbiasReplicas replicas of the table that is fed
 };
 
@@ -48,13 +42,13 @@ __global__ __launch_bounds__(kBlock) void k_mbias(const MbiasArgs a) {
   __syncthreads();
   const uint32_t sub = threadIdx.x & (kMbiasGroup - 1);
   const uint64_t groups = (uint64_t)gridDim.x * (kBlock / kMbiasGroup);
-  const uint64_t batch_lo = a.offsets[0], batch_hi = a.offsets[a.n];  // the calls the batch owns: a slice stays inside them
-  for (uint64_t r = (uint64_t)blockIdx.x * (kBlock / kMbiasGroup) + threadIdx.x / kMbiasGroup; r < a.n; r += groups) {
-    const uint64_t off = a.offsets[r], end = a.offsets[r + 1];
-    const uint32_t times = reinterpret_cast<const uint32_t*>(a.records + r * a.rec_stride)[1];
-    const uint32_t skip = a.skip ? a.skip[r * a.skip_stride] : 0u;
+  const uint64_t batch_lo = a.v.offsets[0], batch_hi = a.v.offsets[a.v.n];  // the calls the batch owns: a slice stays inside them
+  for (uint64_t r = (uint64_t)blockIdx.x * (kBlock / kMbiasGroup) + threadIdx.x / kMbiasGroup; r < a.v.n; r += groups) {
+    const uint64_t off = a.v.offsets[r], end = a.v.offsets[r + 1];
+    const uint32_t times = reinterpret_cast<const uint32_t*>(a.v.records + r * a.v.rec_stride)[1];
+    const uint32_t skip = a.v.skip ? a.v.skip[r * a.v.skip_stride] : 0u;
     if (!mbias_counted(times, skip, off, end) || off < batch_lo || end > batch_hi) continue;  // (before any index or address)
-    const uint8_t* rb = a.calls + off;
+    const uint8_t* rb = a.v.calls + off;
     const int len = (int)(end - off);
     const int head = (int)((uintptr_t)rb & 15u);
     for (int i0 = -head + 16 * (int)sub; i0 < len; i0 += 16 * (int)kMbiasGroup) {
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(kBlock) void k_mbias(const MbiasArgs a) {
 static uint64_t mbias_bytes(uint32_t n_tables) { return (uint64_t)n_tables * kMbiasReplicas * kMbiasWords * 8; }
 
 // what both forms refuse before they look at the batch
-static int mbias_set_check(const walt_mbias* mb, const std::string& who, uint32_t table, const MbiasBatch& b) {
+static int mbias_set_check(const walt_mbias* mb, const std::string& who, uint32_t table, const CallsBatch& b) {
   if (!mb) return fail(WALT_EINVAL, who + ": bad argument (null bias set)");
   if (table >= mb->n_tables)
     return fail(WALT_EINVAL, who + ": table " + std::to_string(table) + " of a bias set with " + std::to_string(mb->n_tables));
@@ -86,18 +80,10 @@ static int mbias_set_check(const walt_mbias* mb, const std::string& who, uint32_
   return bad.empty() ? WALT_OK : fail(WALT_EINVAL, who + ": " + bad);
 }
 
-int mbias_launch(walt_mbias* mb, uint32_t table, const MbiasBatch& b, hipStream_t stream) {
+int mbias_launch(walt_mbias* mb, uint32_t table, const CallsBatch& b, hipStream_t stream) {
   if (b.n == 0) return WALT_OK;
   WALT_HIP(hipSetDevice(mb->device));
-  MbiasArgs a;
-  a.calls = static_cast<const uint8_t*>(b.calls);
-  a.offsets = static_cast<const uint64_t*>(b.offsets);
-  a.n = b.n;
-  a.records = static_cast<const uint8_t*>(b.records);
-  a.rec_stride = b.rec_stride;
-  a.skip = static_cast<const uint8_t*>(b.skip);
-  a.skip_stride = b.skip_stride;
-  a.tabs = mb->tabs + (uint64_t)table * kMbiasReplicas * kMbiasWords;
+  const MbiasArgs a = {calls_view(b), mb->tabs + (uint64_t)table * kMbiasReplicas * kMbiasWords};
   const uint64_t want = ((uint64_t)b.n + kBlock / kMbiasGroup - 1) / (kBlock / kMbiasGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)mb->n_cu * kMbiasBlocksPerCu);
   hipLaunchKernelGGL(k_mbias, dim3(grid), dim3(kBlock), 0, stream, a);
@@ -184,40 +170,20 @@ int walt_mbias_read(walt_mbias* mb, uint32_t table, uint64_t* out) {
 int walt_mbias_batch_device(walt_mbias* mb, uint32_t table, const void* d_calls, const void* d_offsets, uint32_t n,
                             const void* d_records, size_t record_stride, const void* d_skip, size_t skip_stride, void* stream) {
   const std::string who = "walt_mbias_batch_device";
-  const MbiasBatch b = {d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride};
+  const CallsBatch b = {d_calls, d_offsets, n, d_records, record_stride, d_skip, skip_stride};
   if (const int rc = mbias_set_check(mb, who, table, b)) return rc;
-  if (n && (!d_calls || !d_offsets || !d_records)) return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets or records)");
-  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_offsets & 7u))
-    return fail(WALT_EINVAL, who + ": records must be 4-byte aligned, offsets 8-byte aligned");
+  if (const int rc = calls_device_check(who, b)) return rc;
   return mbias_launch(mb, table, b, reinterpret_cast<hipStream_t>(stream));
 }
 
 int walt_mbias_batch(walt_mbias* mb, uint32_t table, const char* calls, const uint64_t* offsets, uint32_t n, const void* records,
                      size_t record_stride, const uint8_t* skip, size_t skip_stride) {
   const std::string who = "walt_mbias_batch";
-  // (host arrays: no alignment is asked of them; the device copies below are aligned)
-  int rc = mbias_set_check(mb, who, table, {calls, offsets, n, records, record_stride, skip, skip_stride});
-  if (rc) return rc;
-  if (n == 0) return WALT_OK;
-  if (!offsets || !records || (!calls && offsets[n] > offsets[0])) return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets or records)");
-  uint32_t max_len = 0;
+  const CallsBatch host = {calls, offsets, n, records, record_stride, skip, skip_stride};
+  if (const int rc = mbias_set_check(mb, who, table, host)) return rc;
   static_assert(kMbiasPositions == 1024, "scan_offsets refuses what the table has no position for");
-  if (const char* bad = scan_offsets(offsets, n, &max_len)) return fail(WALT_EINVAL, who + ": " + bad);
-  WALT_HIP(hipSetDevice(mb->device));
-  const uint64_t nbytes = offsets[n] - offsets[0];
-  // records and skip bytes as the kernel reads them: packed (the caller's strides stay on the host)
-  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(records, record_stride, n);
-  const std::vector<uint8_t> sk = pack_strided<uint8_t>(skip, skip_stride, skip ? n : 0);
-  std::vector<uint64_t> rel;
-  const uint64_t* off = rebase_offsets(offsets, n, rel);
-  const char* what = "methylation bias";
-  DeviceTemp d_calls, d_off, d_rec, d_skip;
-  if ((rc = d_calls.put(nbytes ? calls + offsets[0] : nullptr, nbytes, what)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
-      (rc = d_rec.put(rec.data(), (size_t)n * 16, what)) || (skip && (rc = d_skip.put(sk.data(), n, what))))
-    return rc;
-  if ((rc = mbias_launch(mb, table, {d_calls.p, d_off.p, n, d_rec.p, 16, d_skip.p, 1}, nullptr))) return rc;
-  WALT_HIP(hipStreamSynchronize(nullptr));
-  return WALT_OK;
+  return calls_host_batch(who, "methylation bias", host, false, nullptr, mb->device,
+                          [&](const CallsBatch& b) { return mbias_launch(mb, table, b, nullptr); });
 }
 
 }  // extern "C"

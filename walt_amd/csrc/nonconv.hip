@@ -16,11 +16,7 @@ namespace walt {
 constexpr uint32_t kNonconvBlocksPerCu = 8;  // no LDS, few registers: the grid is bounded by the device, the loop strides
 
 struct NonconvArgs {
-  const uint8_t* calls;
-  const uint64_t* offsets;
-  uint32_t n;
-  const uint8_t* records;
-  uint64_t rec_stride;
+  CallsView v;                // (no skip bytes: a verdict is written for every read)
   walt_nonconv_rule rule;
   uint8_t* filt;
   uint64_t filt_stride;
@@ -47,14 +43,14 @@ __device__ __forceinline__ NonconvSum nonconv_step(const NonconvSum& s, int d) {
 __global__ __launch_bounds__(kBlock) void k_nonconv(const NonconvArgs a) {
   const uint32_t sub = threadIdx.x & (kNonconvGroup - 1);
   const uint64_t groups = (uint64_t)gridDim.x * (kBlock / kNonconvGroup);
-  const uint64_t batch_lo = a.offsets[0], batch_hi = a.offsets[a.n];  // the calls the batch owns: a slice stays inside them
-  for (uint64_t r = (uint64_t)blockIdx.x * (kBlock / kNonconvGroup) + threadIdx.x / kNonconvGroup; r < a.n; r += groups) {
-    const uint64_t off = a.offsets[r], end = a.offsets[r + 1];
-    const uint32_t times = reinterpret_cast<const uint32_t*>(a.records + r * a.rec_stride)[1];
+  const uint64_t batch_lo = a.v.offsets[0], batch_hi = a.v.offsets[a.v.n];  // the calls the batch owns: a slice stays inside them
+  for (uint64_t r = (uint64_t)blockIdx.x * (kBlock / kNonconvGroup) + threadIdx.x / kNonconvGroup; r < a.v.n; r += groups) {
+    const uint64_t off = a.v.offsets[r], end = a.v.offsets[r + 1];
+    const uint32_t times = reinterpret_cast<const uint32_t*>(a.v.records + r * a.v.rec_stride)[1];
     NonconvSum run = nonconv_identity();
     uint32_t fails = 0u;
     if (nonconv_judged(times, off, end) && off >= batch_lo && end <= batch_hi) {  // (before any address; the same for the group)
-      const uint8_t* rb = a.calls + off;
+      const uint8_t* rb = a.v.calls + off;
       const int len = (int)(end - off);
       const int head = (int)((uintptr_t)rb & 15u);
       const int trips = nonconv_trips(len, head);
@@ -93,16 +89,8 @@ __global__ __launch_bounds__(kBlock) void k_nonconv_pairs(const uint8_t* __restr
 int nonconv_launch(const walt_index* idx, const NonconvBatch& b, hipStream_t stream) {
   if (b.n == 0) return WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
-  NonconvArgs a;
-  a.calls = static_cast<const uint8_t*>(b.calls);
-  a.offsets = static_cast<const uint64_t*>(b.offsets);
-  a.n = b.n;
-  a.records = static_cast<const uint8_t*>(b.records);
-  a.rec_stride = b.rec_stride;
-  a.rule = b.rule;
-  a.filt = static_cast<uint8_t*>(b.filt);
-  a.filt_stride = b.filt_stride;
-  a.tally = static_cast<unsigned long long*>(b.tally);
+  const NonconvArgs a = {calls_view({b.calls, b.offsets, b.n, b.records, b.rec_stride, nullptr, 0}), b.rule, static_cast<uint8_t*>(b.filt),
+                         b.filt_stride, static_cast<unsigned long long*>(b.tally)};
   const uint64_t want = ((uint64_t)b.n + kBlock / kNonconvGroup - 1) / (kBlock / kNonconvGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * kNonconvBlocksPerCu);
   hipLaunchKernelGGL(k_nonconv, dim3(grid), dim3(kBlock), 0, stream, a);
@@ -147,10 +135,8 @@ int walt_nonconv_batch_device(walt_index* idx, const void* d_calls, const void* 
                               void* d_tally, void* stream) {
   const std::string who = "walt_nonconv_batch_device";
   if (const int rc = nonconv_check(idx, who, record_stride, rule, d_filt, filt_stride)) return rc;
-  if (n && (!d_calls || !d_offsets || !d_records || !d_filt))
-    return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets, records or filt)");
-  if (((uintptr_t)d_records & 3u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_tally & 7u))
-    return fail(WALT_EINVAL, who + ": records must be 4-byte aligned, offsets and tally 8-byte aligned");
+  const void* const out[2] = {d_filt, d_tally};
+  if (const int rc = calls_device_check(who, {d_calls, d_offsets, n, d_records, record_stride, nullptr, 0}, out)) return rc;
   return nonconv_launch(idx, {d_calls, d_offsets, n, d_records, record_stride, *rule, d_filt, filt_stride, d_tally},
                         reinterpret_cast<hipStream_t>(stream));
 }
@@ -159,29 +145,17 @@ int walt_nonconv_batch(walt_index* idx, const char* calls, const uint64_t* offse
                        size_t record_stride, const walt_nonconv_rule* rule, uint8_t* filt, size_t filt_stride,
                        walt_nonconv_tally* tally) {
   const std::string who = "walt_nonconv_batch";
-  // (host arrays: no alignment is asked of them; the device copies below are aligned)
   int rc = nonconv_check(idx, who, record_stride, rule, filt, filt_stride);
-  if (rc) return rc;
-  if (n == 0) return WALT_OK;
-  if (!offsets || !records || !filt || (!calls && offsets[n] > offsets[0]))
-    return fail(WALT_EINVAL, who + ": bad argument (null calls, offsets, records or filt)");
-  for (uint32_t i = 0; i < n; ++i)  // (a read of more than 1024 calls is legal here: it is not judged)
-    if (offsets[i + 1] < offsets[i]) return fail(WALT_EINVAL, who + ": offsets not non-decreasing");
-  WALT_HIP(hipSetDevice(idx->device));
-  const uint64_t nbytes = offsets[n] - offsets[0];
-  const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(records, record_stride, n);
-  std::vector<uint64_t> rel;
-  const uint64_t* off = rebase_offsets(offsets, n, rel);
+  if (rc || n == 0) return rc;
+  // (any_length: a read of more than 1024 calls is legal here: it is not judged)
   const char* what = "non-converted reads";
-  DeviceTemp d_calls, d_off, d_rec, d_filt, d_tally;
-  if ((rc = d_calls.put(nbytes ? calls + offsets[0] : nullptr, nbytes, what)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
-      (rc = d_rec.put(rec.data(), (size_t)n * 16, what)) || (rc = d_filt.get(n, what)) ||
-      (tally && (rc = d_tally.get((size_t)n * sizeof(walt_nonconv_tally), what))))
-    return rc;
-  if ((rc = nonconv_launch(idx, {d_calls.p, d_off.p, n, d_rec.p, 16, *rule, d_filt.p, 1, d_tally.p}, nullptr))) return rc;
-  WALT_HIP(hipStreamSynchronize(nullptr));
-  if ((rc = nonconv_results(d_filt.p, d_tally.p, n, filt, filt_stride, tally))) return rc;
-  return WALT_OK;
+  DeviceTemp d_filt, d_tally;
+  rc = calls_host_batch(who, what, {calls, offsets, n, records, record_stride, nullptr, 0}, true, filt, idx->device, [&](const CallsBatch& b) {
+    int e;
+    if ((e = d_filt.get(n, what)) || (tally && (e = d_tally.get((size_t)n * sizeof(walt_nonconv_tally), what)))) return e;
+    return nonconv_launch(idx, {b.calls, b.offsets, n, b.records, b.rec_stride, *rule, d_filt.p, 1, d_tally.p}, nullptr);
+  });
+  return rc ? rc : nonconv_results(d_filt.p, d_tally.p, n, filt, filt_stride, tally);
 }
 
 int walt_nonconv_pairs_batch_device(walt_index* idx, const void* d_pairs, uint32_t n, void* d_filt, void* stream) {

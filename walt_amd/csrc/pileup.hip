@@ -465,23 +465,14 @@ static PileArgs pile_args(const walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi
   a.start_index = idx->view.start_index;
   a.n_chrom = idx->view.n_chrom;
   a.pos_lo = pos_lo; a.pos_hi = pos_hi;
-  const uint64_t range = (uint64_t)pos_hi - pos_lo;
-  uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks
-                                               : std::min<uint64_t>((range + kPileTile - 1) / kPileTile, (uint64_t)idx->n_cu * 8);
-  want = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, kPileMaxBlocks), std::max<uint64_t>(range, 1)));
-  n_blocks = (uint32_t)want;
-  a.chunk = (range + want - 1) / want;
+  n_blocks = extract_blocks(idx, (uint64_t)pos_hi - pos_lo, kPileTile, kPileMaxBlocks, &a.chunk);
   a.table = p->table;
   a.sites = nullptr; a.cap = 0; a.n_sites_out = nullptr; a.offref_out = nullptr;
   return a;
 }
 
 static int pile_range_check(const walt_pileup* p, const char* who, uint32_t pos_lo, uint32_t pos_hi) {
-  if (!p) return fail(WALT_EINVAL, std::string(who) + ": bad argument (null pile-up)");
-  if (pos_lo > pos_hi || pos_hi > p->idx->head.genome_len)
-    return fail(WALT_EINVAL, std::string(who) + ": range [" + std::to_string(pos_lo) + ", " + std::to_string(pos_hi) +
-                                 ") is not inside the genome's " + std::to_string(p->idx->head.genome_len) + " positions");
-  return WALT_OK;
+  return range_refusal(p, who, "pile-up", pos_lo, pos_hi);
 }
 
 // count and scan on `stream`
@@ -590,17 +581,16 @@ int walt_pileup_extract(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, walt_m
     return fail(WALT_EINVAL, "walt_pileup_extract: the range holds " + std::to_string(tot[0]) + " sites, the array has room for " +
                                  std::to_string(cap));
   if (!tot[0]) return WALT_OK;
-  void* d_sites = nullptr;
-  if (hipMalloc(&d_sites, tot[0] * sizeof(walt_meth_site)) != hipSuccess) {
+  DeviceTemp d_sites;
+  if (hipMalloc(&d_sites.p, tot[0] * sizeof(walt_meth_site)) != hipSuccess) {
     (void)hipGetLastError();
     return fail(WALT_ENOMEM, "walt_pileup_extract: hipMalloc of " + std::to_string(tot[0] * sizeof(walt_meth_site)) + " bytes failed");
   }
-  a.sites = static_cast<walt_meth_site*>(d_sites);
+  a.sites = static_cast<walt_meth_site*>(d_sites.p);
   a.cap = tot[0];
   hipLaunchKernelGGL(k_pile_write, dim3(n_blocks), dim3(kBlock), 0, nullptr, a, n_blocks);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(sites, d_sites, tot[0] * sizeof(walt_meth_site), hipMemcpyDeviceToHost);
-  (void)hipFree(d_sites);
+  if (e == hipSuccess) e = hipMemcpy(sites, d_sites.p, tot[0] * sizeof(walt_meth_site), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(WALT_EHIP, std::string("walt_pileup_extract: ") + hipGetErrorString(e));
   return WALT_OK;
 }

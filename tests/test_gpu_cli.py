@@ -286,3 +286,42 @@ def test_cli_makedb_on_gpu_writes_files_the_reference_binary_maps_from(scratch):
         return recs, int(work["too_short"])
     want = run_se_case(b, "se_sam_au", mapper)["out.sam"]
     assert got == want and len(got) > 1000
+
+
+CONSUMERS = [("-M", ".methstats"), ("-MC", ".methcounts"), ("-ML", ".levels"), ("-MB", ".mbias"), ("-MA", ".allelic"),
+             ("-ME", ".epialleles")]
+STATS = [".dupstats", ".filterstats"]
+_together = {}  # mode -> the files of the run with every consumer, on one index replica and on two
+
+
+def _consumer_run(cli_index, scratch, mode, tag, args):
+    """Every modifier of the calls (-D -F -I5 -I3 -C, paired-end also -NO -I5R2; plain, -P and -RP) in batches of which
+    the third is short, with the consumers of `args`."""
+    clip = [v for v in META["cases"].values() if v["kind"] == "se_clip"][0]
+    common = ["-i", cli_index, "-sam", "-D", "-F", "3", "-I5", "2", "-I3", "1", "-C", refio.args_to_opts(clip["args"])["C"]]
+    if mode == "se":
+        common += ["-r", os.path.join(refio.GOLDEN, "se_ct.fastq"), "-N", "500"]  # 1200 reads: 500, 500, 200
+    else:
+        mates = ["pe_2.fastq", "pe_1.fastq"] if mode == "pe_P" else ["pe_1.fastq", "pe_2.fastq"]  # (-P: mate 1 is the A-rich one)
+        common += ["-1", os.path.join(refio.GOLDEN, mates[0]), "-2", os.path.join(refio.GOLDEN, mates[1]), "-N", "300",
+                   "-NO", "-I5R2", "1"] + {"pe": [], "pe_P": ["-P"], "pe_RP": ["-RP"]}[mode]  # 800 pairs: 300, 300, 200
+    return _run_cli(os.path.join(scratch, "together_%s_%s" % (mode, tag)), common + ["-o", "out.sam"] + args)
+
+
+@pytest.mark.parametrize("flag,sfx", CONSUMERS)
+@pytest.mark.parametrize("mode", ["se", "pe", "pe_P", "pe_RP"])
+def test_cli_consumers_together_write_what_each_writes_alone(cli_index, scratch, mode, flag, sfx):
+    """Every consumer of the methylation calls at once, under every modifier of the calls: each consumer's file must be
+    the file of a run that asks for that consumer alone under the same modifiers, <out>.dupstats and <out>.filterstats
+    the files of each such run, and all of them the same on two index replicas (-g 0,0) as on one."""
+    if mode not in _together:
+        everything = [f for f, _ in CONSUMERS]
+        _together[mode] = (_consumer_run(cli_index, scratch, mode, "g0", everything + ["-g", "0"]),
+                           _consumer_run(cli_index, scratch, mode, "g00", everything + ["-g", "0,0"]))
+    one, two = _together[mode]
+    assert one["out.sam"] == two["out.sam"] and one["out.sam"].count("\tXM:Z:") > 500
+    alone = _consumer_run(cli_index, scratch, mode, flag.strip("-"), [flag, "-g", "0"])
+    for s in [sfx] + STATS:
+        assert len(one["out.sam" + s]) > 0, s
+        assert one["out.sam" + s] == two["out.sam" + s], "%s: %s differs between -g 0 and -g 0,0" % (mode, s)
+        assert alone["out.sam" + s] == one["out.sam" + s], "%s: %s of %s alone differs from the run with every consumer" % (mode, s, flag)

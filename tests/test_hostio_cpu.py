@@ -197,3 +197,89 @@ def test_clipping_of_short_reads_pinned_against_the_reference_binary(scratch):
         f.write(CLIP_TINY)
     got = cxx_dump(fq2, 10 ** 6, CLIP_ADAPTOR, 2, 0, scratch)[0].decode()
     assert [ln.split("\t")[1] for ln in got.splitlines() if not ln.startswith("#")] == ["ACGTAGATCGGA", "AGATCGG"]
+
+
+# ---- hostio::merge_rows: the merge by position of the tables the driver writes (-MC sites, -MA entries, -ME windows)
+MERGE_KINDS = {"sites": (0, 2, 32), "pairs": (1, 4, 64), "windows": (2, 16, 64)}  # kind, counters per row, their bits
+
+
+def merge_cases(width, bits):
+    """name -> one to three devices' rows [(pos, counters)], each device ascending by position"""
+    rng = random.Random(width)
+    big = (1 << bits) - 5  # sums of two wrap a 32-bit counter; a 64-bit one is far above 2^32 (and wraps as well)
+
+    def row(pos, hi=1000):
+        return (pos, [rng.randrange(hi) for _ in range(width)])
+
+    def rows(positions, hi=1000):
+        return [row(p, hi) for p in sorted(positions)]
+
+    some = rows(rng.sample(range(5000), 30))
+    return {
+        "empty add": [some, []],
+        "empty rows": [[], some],
+        "nothing at all": [[], [], []],
+        "one device": [some],
+        "all positions equal": [rows(range(100, 140)), rows(range(100, 140)), rows(range(100, 140))],
+        "all positions disjoint": [rows(range(0, 90, 3)), rows(range(1, 90, 3)), rows(range(2, 90, 3))],
+        "interleaved, ties at the first and last position": [rows([7, 9, 20, 21, 40, 77]), rows([7, 8, 21, 30, 77]), rows([7, 10, 40, 76, 77])],
+        "the largest positions": [rows([0, 2 ** 32 - 2, 2 ** 32 - 1]), rows([2 ** 32 - 1])],
+        "counters that wrap or pass 2^32": [[(5, [big] * width), (6, [2 ** 32 - 1] * width)], [(5, [9] * width), (6, [1] * width), (8, [big] * width)]],
+    }
+
+
+def dictionary_merge(devices, bits):
+    acc = {}
+    for dev in devices:
+        for pos, counters in dev:
+            acc[pos] = [(a + b) % (1 << bits) for a, b in zip(acc.get(pos, [0] * len(counters)), counters)]
+    return sorted(acc.items())
+
+
+def cxx_merge(kind, width, devices):
+    L = refio.hostio_harness()
+    L.hio_merge_rows.restype = ctypes.c_uint64
+    assert L.hio_merge_counters(kind) == width
+    flat = [r for dev in devices for r in dev]
+    n_rows = (ctypes.c_uint64 * max(1, len(devices)))(*[len(dev) for dev in devices])
+    pos = (ctypes.c_uint32 * max(1, len(flat)))(*[p for p, _ in flat])
+    counters = (ctypes.c_uint64 * max(1, len(flat) * width))(*[c for _, cs in flat for c in cs])
+    out_pos = (ctypes.c_uint32 * max(1, len(flat)))()
+    out_counters = (ctypes.c_uint64 * max(1, len(flat) * width))()
+    n = L.hio_merge_rows(kind, len(devices), n_rows, pos, counters, out_pos, out_counters)
+    assert n <= len(flat)
+    return [(out_pos[i], list(out_counters[i * width:(i + 1) * width])) for i in range(n)]
+
+
+@pytest.mark.parametrize("table", sorted(MERGE_KINDS))
+def test_merge_rows_adds_the_devices_windows_by_position(table):
+    kind, width, bits = MERGE_KINDS[table]
+    for name, devices in merge_cases(width, bits).items():
+        want = dictionary_merge(devices, bits)
+        assert cxx_merge(kind, width, devices) == want, name
+        if name.startswith("counters"):
+            assert want[0][1] == [4] * width and want[1][1] == [0 if bits == 32 else 2 ** 32] * width
+
+
+def test_merge_rows_under_the_sanitizers(scratch):
+    """tests/hostio_sanitize_main.cpp: the same cases through a program of its own with -fsanitize=address,undefined"""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.fail("g++ is needed to build the sanitizer program")
+    lines, n_cases = [], 0
+    for table, (kind, width, bits) in sorted(MERGE_KINDS.items()):
+        for name, devices in merge_cases(width, bits).items():
+            n_cases += 1
+            lines.append("%d %d" % (kind, len(devices)))
+            for dev in devices + [dictionary_merge(devices, bits)]:
+                lines.append(" ".join([str(len(dev))] + [str(v) for pos, cs in dev for v in [pos] + cs]))
+    cases = os.path.join(scratch, "merge_cases.txt")
+    with open(cases, "w") as f:
+        f.write("%d\n%s\n" % (n_cases, "\n".join(lines)))
+    exe = os.path.join(scratch, "hostio_sanitize")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fopenmp", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(refio.HERE, "hostio_sanitize_main.cpp"), os.path.join(refio.HERE, "hostio_harness.cpp"), "-o", exe],
+                   check=True, timeout=600)
+    run = subprocess.run([exe, cases], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and run.stdout.startswith("ok "), run.stdout + run.stderr

@@ -787,26 +787,38 @@ inline void put_epiallele_line(Sink& out, const std::string& chrom, uint32_t pos
   out.put(chrom);
   out.lit(num);
 }
-// One window of a run as the writer holds it, and the merge of two devices' windows: `add`, ascending by position, into
-// `rows`, ascending too -- the counters of a position both hold are added (they are additive: each device counted its
-// own share of the reads).  `other` is scratch.
-struct EpialleleRow {
-  uint32_t pos, last;
-  uint64_t n[16];
-};
-inline void merge_epiallele_rows(std::vector<EpialleleRow>& rows, const EpialleleRow* add, size_t n_add, std::vector<EpialleleRow>& other) {
+// The merge of two devices' windows of a table written by position (-MC, -MA, -ME): `add`, ascending by `pos`, into
+// `rows`, ascending too; a position both hold becomes one row, plus(row, other_row) adding the counters (they are
+// additive: each device counted its own share of the reads).  `other` is scratch.
+template <class Row, class Plus>
+inline void merge_rows(std::vector<Row>& rows, const Row* add, size_t n_add, std::vector<Row>& other, Plus plus) {
   other.clear();
   size_t i = 0, j = 0;
   while (i < rows.size() || j < n_add) {
     if (j == n_add || (i < rows.size() && rows[i].pos < add[j].pos)) { other.push_back(rows[i++]); continue; }
-    EpialleleRow r = add[j++];
-    if (i < rows.size() && rows[i].pos == r.pos) {
-      for (int k = 0; k < 16; ++k) r.n[k] += rows[i].n[k];
-      ++i;
-    }
+    Row r = add[j++];
+    if (i < rows.size() && rows[i].pos == r.pos) plus(r, rows[i++]);
     other.push_back(r);
   }
   rows.swap(other);
+}
+// The rows of the three tables and how two rows of one position add.  A site of -MC is the device's record, its counters
+// added in 32 bits as on the device; an entry of -MA and a window of -ME are held with counters of 64 bits.
+inline void add_site_row(walt_meth_site& r, const walt_meth_site& o) { r.meth += o.meth; r.unmeth += o.unmeth; }
+struct AllelicRow {
+  uint32_t pos, next;
+  uint64_t n[4];
+};
+struct EpialleleRow {
+  uint32_t pos, last;
+  uint64_t n[16];
+};
+template <class Row>  // (an AllelicRow or an EpialleleRow)
+inline void add_counter_row(Row& r, const Row& o) {
+  for (size_t k = 0; k < sizeof r.n / sizeof r.n[0]; ++k) r.n[k] += o.n[k];
+}
+inline void merge_epiallele_rows(std::vector<EpialleleRow>& rows, const EpialleleRow* add, size_t n_add, std::vector<EpialleleRow>& other) {
+  merge_rows(rows, add, n_add, other, add_counter_row<EpialleleRow>);
 }
 inline uint64_t epiallele_row_total(const EpialleleRow& r) {
   uint64_t t = 0;

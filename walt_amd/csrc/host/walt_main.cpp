@@ -10,6 +10,10 @@
 // each thread owning a contiguous range of the batch, so the files come out in
 // read order and byte-identical to the reference binary's
 // (tests/test_gpu_cli.py compares against the golden files).
+// process_se and process_pe hold what differs between the modes (loading, the mapping call, formatting, .mapstats);
+// what the extensions share exists once: kOutput / Append (the side files), HandleSet (one handle per device),
+// write_window_table (.methcounts / .allelic / .epialleles), Consumers (all that takes the methylation calls: open,
+// start_batch, view + call_slot, finish), run_batch (a batch's schedule, -D included), reserve_records.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,6 +29,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unistd.h>
 #include <vector>
 
@@ -288,6 +293,31 @@ struct SideFiles {  // the _ambiguous / _unmapped files of StatSingleReads (mapp
   void close() { amb.close(); unm.close(); }
 };
 
+// The files a run writes beside its main output, <out><suffix>: main truncates those whose option is on (walt.cpp:230-233
+// for the first), and the end of every read file appends its block to each.
+enum { kMapstats, kMethstats, kMethcounts, kLevels, kRegions, kMbias, kAllelic, kEpialleles, kDupstats, kFilterstats, kOutputs };
+static const struct { bool (*on)(const Options&); const char* suffix; } kOutput[kOutputs] = {
+    {[](const Options&) { return true; }, ".mapstats"},
+    {[](const Options& o) { return o.meth; }, ".methstats"},
+    {[](const Options& o) { return o.methcounts; }, ".methcounts"},
+    {[](const Options& o) { return o.levels; }, ".levels"},
+    {[](const Options& o) { return o.regions(); }, ".regions"},
+    {[](const Options& o) { return o.mbias; }, ".mbias"},
+    {[](const Options& o) { return o.allelic; }, ".allelic"},
+    {[](const Options& o) { return o.epialleles; }, ".epialleles"},
+    {[](const Options& o) { return o.dedup; }, ".dupstats"},
+    {[](const Options& o) { return o.filtering(); }, ".filterstats"},
+};
+struct Append {  // one of them, open for appending
+  OutFile f;
+  Append(const string& out_file, int which) {
+    const string path = out_file + kOutput[which].suffix;
+    if (!f.open_append(path)) die("cannot open input file " + path);
+  }
+  ~Append() { f.close(); }
+  void write(const Sink& s) { if (s.n) f.write(s.p, s.n); }
+};
+
 // ---------------------------------------------------------------- single-end writers, mapping.cpp:329-419
 static void out_mr_line(const walt_best_match& bm, View name, View seq, View score, bool flip, const GenomeInfo& g,
                         bool ag, Sink& f) {
@@ -375,103 +405,140 @@ static void clip_points(const Batch& b, const string& adaptor, int T, vector<uin
   for (uint32_t j = 0; j < b.n; ++j)
     out[j] = hostio::adaptor_clip_point(View{b.base + (b.seq_v[j] >> 16), (uint32_t)(b.seq_v[j] & 0xFFFF)}, ad);
 }
-static void write_methstats(const string& out_file, const Sink& ms) {
-  OutFile mf;
-  if (!mf.open_append(out_file + ".methstats")) die("cannot open input file " + out_file + ".methstats");
-  mf.write(ms.p, ms.n);
-  mf.close();
-}
 
-// ---------------------------------------------------------------- -MC: per-cytosine pile-up
-// One pile-up per device of the run; a share's calls go into the pile-up of the device that mapped it.  At the end of
-// a read file the table is written window by window of forward positions (a bounded buffer per device: a window holds
-// at most as many sites as positions), the windows of several devices merged by position with their counts added.
-struct PileSet {
-  vector<walt_pileup*> p;
-  void open(const vector<walt_index*>& idx) {
-    p.assign(idx.size(), nullptr);
-    for (size_t d = 0; d < idx.size(); ++d)
-      if (walt_pileup_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+// ---------------------------------------------------------------- one handle per device of the run
+// A pile-up (-MC -ML -MR), a bias set (-MB), a pair table (-MA) or a window table (-ME): a share's calls are counted on
+// the device that made them, and the end of a read file adds the devices' counters up on the host.  The handles are
+// destroyed before their indexes are closed (Consumers::finish; when an error unwinds, the destructor).
+template <class H, void (*Destroy)(H*)>
+struct HandleSet {
+  vector<H*> p;
+  HandleSet() {}
+  HandleSet(const HandleSet&) = delete;
+  HandleSet& operator=(const HandleSet&) = delete;
+  ~HandleSet() { close(); }
+  template <class Create>  // create(d, &handle) -> status
+  void open(size_t n_devices, Create create) {
+    p.assign(n_devices, nullptr);
+    for (size_t d = 0; d < n_devices; ++d)
+      if (create(d, &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
   }
   void close() {
-    for (walt_pileup*& q : p) { if (q) walt_pileup_destroy(q); q = nullptr; }
+    for (H* q : p) if (q) Destroy(q);
+    p.clear();
   }
   bool on() const { return !p.empty(); }
+  H* of(size_t d) const { return on() ? p[d] : nullptr; }
 };
-static const uint32_t kCountsWindow = 1u << 22;  // positions per extraction (64 MB of records per device at most)
-static void write_methcounts(const string& out_file, PileSet& ps, const GenomeInfo& g, bool verbose) {
-  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
-  OutFile mf;
-  if (!mf.open_append(out_file + ".methcounts")) die("cannot open input file " + out_file + ".methcounts");
+typedef HandleSet<walt_pileup, walt_pileup_destroy> PileUps;
+typedef HandleSet<walt_mbias, walt_mbias_destroy> MbiasSet;  // one table per mate: table k takes slot k
+typedef HandleSet<walt_cpgpairs, walt_cpgpairs_destroy> PairTables;
+typedef HandleSet<walt_epialleles, walt_epialleles_destroy> WindowTables;
+
+// ---------------------------------------------------------------- -MC -MA -ME: tables written by forward position
+// At the end of a read file a table is written window by window of forward positions (a bounded buffer: capacity() says
+// how many entries a window can hold), the windows of several devices merged by position with their counters added.
+// A Table supplies its file and window (kOut, kWindow), the record of its extraction and the row the host merges (Site,
+// Row; row() where the row's counters are wider), extract(), how two rows of a position add(), whether a merged row is
+// written (keep(), which also tallies), its line() and its -v line (report()).
+static const uint32_t kCountsWindow = 1u << 22;  // positions per extraction (64 MB of records at most)
+template <class F>  // fn(lo, hi) for every window of the genome
+static void for_each_window(uint64_t genome_len, uint64_t window, F fn) {
+  for (uint64_t lo = 0; lo < genome_len; lo += window) fn((uint32_t)lo, (uint32_t)std::min<uint64_t>(lo + window, genome_len));
+}
+template <class Table, class Handles>
+static void write_window_table(Table& t, const Handles& set, const string& out_file, const GenomeInfo& g, bool verbose) {
+  Append mf(out_file, Table::kOut);
   const uint64_t genome_len = g.start.back();
-  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
-  vector<vector<walt_meth_site>> buf(ps.p.size(), vector<walt_meth_site>((size_t)window));  // allocated once
-  vector<walt_meth_site> merged, other;
-  uint64_t off[2] = {0, 0}, n_total = 0;
+  const uint64_t window = std::min<uint64_t>(Table::kWindow, genome_len);
+  const uint64_t cap = Table::capacity(window);
+  typedef typename Table::Site Site;
+  typedef typename Table::Row Row;
+  vector<Site> buf((size_t)cap);  // allocated once
+  vector<Row> rows, add, other;
+  uint64_t n_total = 0;
   uint32_t chr = 0;
   Sink out;
-  for (uint64_t lo = 0; lo < genome_len; lo += window) {
-    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
-    const walt_meth_site* rows = buf[0].data();
-    uint64_t n_rows = 0;
-    for (size_t d = 0; d < ps.p.size(); ++d) {
-      uint64_t n = 0, o2[2] = {0, 0};
-      check(walt_pileup_extract(ps.p[d], (uint32_t)lo, (uint32_t)hi, buf[d].data(), window, &n, o2));
-      off[0] += o2[0]; off[1] += o2[1];
-      if (d == 0) { n_rows = n; continue; }
-      other.clear();  // merge by position, adding the counts
-      const walt_meth_site* b = buf[d].data();
-      uint64_t i = 0, j = 0;
-      while (i < n_rows || j < n) {
-        if (j == n || (i < n_rows && rows[i].pos < b[j].pos)) other.push_back(rows[i++]);
-        else if (i == n_rows || b[j].pos < rows[i].pos) other.push_back(b[j++]);
-        else { walt_meth_site s = rows[i++]; s.meth += b[j].meth; s.unmeth += b[j].unmeth; ++j; other.push_back(s); }
+  for_each_window(genome_len, window, [&](uint32_t lo, uint32_t hi) {
+    const Row* cur = nullptr;  // the window's rows: one device's as extracted, several devices' merged
+    size_t n_cur = 0;
+    for (size_t d = 0; d < set.p.size(); ++d) {
+      uint64_t n = 0;
+      check(t.extract(set.p[d], lo, hi, buf.data(), cap, &n));
+      const Row* src;
+      if constexpr (std::is_same<Site, Row>::value) {
+        src = buf.data();  // a site is a row: nothing to copy
+      } else {
+        add.resize((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) add[i] = Table::row(buf[i]);
+        src = add.data();
       }
-      merged.swap(other);
-      rows = merged.data();
-      n_rows = merged.size();
+      if (set.p.size() == 1) { cur = src; n_cur = (size_t)n; break; }
+      if (d == 0) rows.clear();
+      hostio::merge_rows(rows, src, (size_t)n, other, Table::add);
+      cur = rows.data(); n_cur = rows.size();
     }
     out.clear();
-    for (uint64_t k = 0; k < n_rows; ++k) {
-      const walt_meth_site& s = rows[k];
-      while (s.pos >= g.start[chr + 1]) ++chr;  // (ascending positions)
-      out.put(g.name[chr]); out.ch('\t'); out.u32(s.pos - g.start[chr]); out.ch('\t'); out.ch((char)s.strand); out.ch('\t');
-      out.lit(ctx[s.context & 3]); out.ch('\t'); out.u32(s.meth); out.ch('\t'); out.u32(s.unmeth); out.ch('\n');
+    for (size_t k = 0; k < n_cur; ++k) {
+      const Row& r = cur[k];
+      if (!t.keep(r)) continue;
+      while (r.pos >= g.start[chr + 1]) ++chr;  // (ascending positions; an entry lies inside one chromosome)
+      t.line(out, g.name[chr], g.start[chr], r);
+      ++n_total;
     }
-    n_total += n_rows;
-    if (out.n) mf.write(out.p, out.n);
-  }
-  mf.close();
-  if (verbose)
-    fprintf(stderr, "[walt_amd methcounts: %llu sites; off-reference calls (on an A or T of the reference): %llu methylated, %llu unmethylated]\n",
-            (unsigned long long)n_total, (unsigned long long)off[0], (unsigned long long)off[1]);
+    mf.write(out);
+  });
+  if (verbose) t.report(n_total);
 }
+
+// -MC: the per-cytosine pile-up; a window holds at most as many sites as positions
+struct SiteTable {
+  typedef walt_meth_site Site;
+  typedef walt_meth_site Row;
+  static constexpr int kOut = kMethcounts;
+  static constexpr uint32_t kWindow = kCountsWindow;
+  uint64_t off[2];
+  static uint64_t capacity(uint64_t window) { return window; }
+  int extract(walt_pileup* p, uint32_t lo, uint32_t hi, Site* buf, uint64_t cap, uint64_t* n) {
+    uint64_t o2[2] = {0, 0};
+    const int rc = walt_pileup_extract(p, lo, hi, buf, cap, n, o2);
+    off[0] += o2[0]; off[1] += o2[1];
+    return rc;
+  }
+  static void add(Row& r, const Row& o) { hostio::add_site_row(r, o); }
+  bool keep(const Row&) { return true; }
+  void line(Sink& out, const string& chrom, uint32_t chrom_start, const Row& s) {
+    static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+    out.put(chrom); out.ch('\t'); out.u32(s.pos - chrom_start); out.ch('\t'); out.ch((char)s.strand); out.ch('\t');
+    out.lit(ctx[s.context & 3]); out.ch('\t'); out.u32(s.meth); out.ch('\t'); out.u32(s.unmeth); out.ch('\n');
+  }
+  void report(uint64_t n_rows) {
+    fprintf(stderr, "[walt_amd methcounts: %llu sites; off-reference calls (on an A or T of the reference): %llu methylated, %llu unmethylated]\n",
+            (unsigned long long)n_rows, (unsigned long long)off[0], (unsigned long long)off[1]);
+  }
+};
 
 // ---------------------------------------------------------------- -ML: genome-wide methylation levels
 // Maxima and covered sites are not additive across devices: the other devices' counters are folded into the first
 // device's pile-up, window by window (once per read file, shared with -MR), and one summary runs there over the whole
 // genome.
-static void fold_pileups(PileSet& ps, uint64_t genome_len) {
+static void fold_pileups(PileUps& ps, uint64_t genome_len) {
   if (ps.p.size() < 2) return;
   const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
   vector<uint32_t> m((size_t)window), u((size_t)window);
   for (size_t d = 1; d < ps.p.size(); ++d)
-    for (uint64_t lo = 0; lo < genome_len; lo += window) {
-      const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
-      check(walt_pileup_read(ps.p[d], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
-      check(walt_pileup_add(ps.p[0], (uint32_t)lo, (uint32_t)hi, m.data(), u.data()));
-    }
+    for_each_window(genome_len, window, [&](uint32_t lo, uint32_t hi) {
+      check(walt_pileup_read(ps.p[d], lo, hi, m.data(), u.data()));
+      check(walt_pileup_add(ps.p[0], lo, hi, m.data(), u.data()));
+    });
 }
 // (the counters are folded by now)
-static void write_levels(const string& out_file, PileSet& ps, const GenomeInfo& g, bool verbose) {
+static void write_levels(const string& out_file, PileUps& ps, const GenomeInfo& g, bool verbose) {
   walt_levels lv;
   check(walt_pileup_levels(ps.p[0], 0, (uint32_t)g.start.back(), &lv));
   Sink out;
   hostio::put_levels_block(out, lv);
-  OutFile mf;
-  if (!mf.open_append(out_file + ".levels")) die("cannot open input file " + out_file + ".levels");
-  mf.write(out.p, out.n);
-  mf.close();
+  Append(out_file, kLevels).write(out);
   if (verbose) fwrite(out.p, 1, out.n, stderr);
 }
 
@@ -501,21 +568,21 @@ struct RegionSet {
   }
 };
 static RegionSet g_regions;
-static void write_regions(const string& out_file, PileSet& ps) {
+static void write_regions(const string& out_file, PileUps& ps) {
   vector<walt_region_levels> lv(g_regions.regions.size());
   check(walt_pileup_regions(ps.p[0], g_regions.regions.data(), g_regions.regions.size(), lv.data()));
   Sink out;
   hostio::put_regions_block(out, g_regions.bed, lv.data());
-  OutFile mf;
-  if (!mf.open_append(out_file + ".regions")) die("cannot open input file " + out_file + ".regions");
-  mf.write(out.p, out.n);
-  mf.close();
+  Append(out_file, kRegions).write(out);
 }
 
 // the end of a read file: <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the
 // counters cleared
-static void end_of_file_pileups(const Options& o, const string& out_file, PileSet& ps, const GenomeInfo& g) {
-  if (o.methcounts) write_methcounts(out_file, ps, g, o.verbose);
+static void end_of_file_pileups(const Options& o, const string& out_file, PileUps& ps, const GenomeInfo& g) {
+  if (o.methcounts) {
+    SiteTable t = {{0, 0}};
+    write_window_table(t, ps, out_file, g, o.verbose);
+  }
   if (o.levels || o.regions()) fold_pileups(ps, g.start.back());
   if (o.levels) write_levels(out_file, ps, g, o.verbose);
   if (o.regions()) write_regions(out_file, ps);
@@ -525,167 +592,78 @@ static void end_of_file_pileups(const Options& o, const string& out_file, PileSe
 // ---------------------------------------------------------------- -MB: methylation bias by read position
 // One set per device of the run, one table per mate; a share's calls are counted on the device that made them.  At the
 // end of a read file the host adds the devices' tables, writes the blocks and clears the sets.
-struct MbiasSet {
-  vector<walt_mbias*> p;
-  uint32_t n_tables = 0;
-  void open(const vector<int>& ids, uint32_t tables) {
-    p.assign(ids.size(), nullptr);
-    n_tables = tables;
-    for (size_t d = 0; d < ids.size(); ++d)
-      if (walt_mbias_create(ids[d], tables, &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+static void mbias_block(const MbiasSet& mbs, Sink& out, uint32_t table) {  // the table summed over the devices
+  vector<uint64_t> sum(WALT_MBIAS_WORDS, 0), one(WALT_MBIAS_WORDS);
+  for (walt_mbias* q : mbs.p) {
+    check(walt_mbias_read(q, table, one.data()));
+    for (size_t w = 0; w < sum.size(); ++w) sum[w] += one[w];
   }
-  void close() {
-    for (walt_mbias*& q : p) { if (q) walt_mbias_destroy(q); q = nullptr; }
-    p.clear();
-  }
-  bool on() const { return !p.empty(); }
-  walt_mbias* of(size_t d) const { return on() ? p[d] : nullptr; }
-  void block(Sink& out, uint32_t table) const {  // the table summed over the devices
-    vector<uint64_t> sum(WALT_MBIAS_WORDS, 0), one(WALT_MBIAS_WORDS);
-    for (walt_mbias* q : p) {
-      check(walt_mbias_read(q, table, one.data()));
-      for (size_t w = 0; w < sum.size(); ++w) sum[w] += one[w];
-    }
-    hostio::put_mbias_block(out, sum.data());
-  }
-  void write(const string& out_file, const Sink& ms) {
-    OutFile mf;
-    if (!mf.open_append(out_file + ".mbias")) die("cannot open input file " + out_file + ".mbias");
-    mf.write(ms.p, ms.n);
-    mf.close();
-    for (walt_mbias* q : p) check(walt_mbias_clear(q));
-  }
-};
+  hostio::put_mbias_block(out, sum.data());
+}
+static void mbias_write(MbiasSet& mbs, const string& out_file, const Sink& ms) {
+  Append(out_file, kMbias).write(ms);
+  for (walt_mbias* q : mbs.p) check(walt_mbias_clear(q));
+}
 
 // ---------------------------------------------------------------- -MA: adjacent-CpG state pairs per read
-// One pair table per device of the run; a share's calls are folded on the device that made them.  At the end of a read
-// file the non-zero entries are extracted window by window of forward positions (a bounded buffer per device: pairs do
-// not overlap, so a window holds at most half as many entries as positions), the windows of several devices merged by
-// position with their counts added -- the counters are additive -- and written with the test of each table.
-struct PairSet {
-  vector<walt_cpgpairs*> p;
-  void open(const vector<walt_index*>& idx) {
-    p.assign(idx.size(), nullptr);
-    for (size_t d = 0; d < idx.size(); ++d)
-      if (walt_cpgpairs_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+// Pairs do not overlap, so a window holds at most half as many entries as positions; each line carries the test of its
+// table.  The device counts in 32 bits, the host adds the devices' counters in 64.
+struct PairTable {
+  typedef walt_cpgpair_site Site;
+  typedef hostio::AllelicRow Row;
+  static constexpr int kOut = kAllelic;
+  static constexpr uint32_t kWindow = kCountsWindow;
+  uint64_t couples;
+  static uint64_t capacity(uint64_t window) { return window / 2 + 1; }
+  int extract(walt_cpgpairs* p, uint32_t lo, uint32_t hi, Site* buf, uint64_t cap, uint64_t* n) {
+    return walt_cpgpairs_extract(p, lo, hi, buf, cap, n);
   }
-  void close() {  // (before the indexes are closed)
-    for (walt_cpgpairs*& q : p) { if (q) walt_cpgpairs_destroy(q); q = nullptr; }
-    p.clear();
+  static Row row(const Site& b) { return Row{b.pos, b.next, {b.n[0], b.n[1], b.n[2], b.n[3]}}; }
+  static void add(Row& r, const Row& o) { hostio::add_counter_row(r, o); }
+  bool keep(const Row& r) { couples += r.n[0] + r.n[1] + r.n[2] + r.n[3]; return true; }
+  void line(Sink& out, const string& chrom, uint32_t chrom_start, const Row& r) {  // (next lies in the same chromosome)
+    hostio::put_allelic_line(out, chrom, r.pos - chrom_start, r.next - chrom_start, r.n);
   }
-  bool on() const { return !p.empty(); }
-  walt_cpgpairs* of(size_t d) const { return on() ? p[d] : nullptr; }
-};
-struct AllelicRow {
-  uint32_t pos, next;
-  uint64_t n[4];
-};
-static void write_allelic(const string& out_file, PairSet& ps, const GenomeInfo& g, bool verbose) {
-  OutFile mf;
-  if (!mf.open_append(out_file + ".allelic")) die("cannot open input file " + out_file + ".allelic");
-  const uint64_t genome_len = g.start.back();
-  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
-  const uint64_t cap = window / 2 + 1;
-  vector<walt_cpgpair_site> buf((size_t)cap);  // allocated once
-  vector<AllelicRow> rows, other;
-  uint64_t n_total = 0, couples = 0;
-  uint32_t chr = 0;
-  Sink out;
-  for (uint64_t lo = 0; lo < genome_len; lo += window) {
-    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
-    rows.clear();
-    for (size_t d = 0; d < ps.p.size(); ++d) {
-      uint64_t n = 0;
-      check(walt_cpgpairs_extract(ps.p[d], (uint32_t)lo, (uint32_t)hi, buf.data(), cap, &n));
-      other.clear();  // merge by position, adding the counts
-      uint64_t i = 0, j = 0;
-      while (i < rows.size() || j < n) {
-        if (j == n || (i < rows.size() && rows[i].pos < buf[j].pos)) { other.push_back(rows[i++]); continue; }
-        const walt_cpgpair_site& b = buf[j++];
-        AllelicRow r = {b.pos, b.next, {b.n[0], b.n[1], b.n[2], b.n[3]}};
-        if (i < rows.size() && rows[i].pos == b.pos) {
-          for (int k = 0; k < 4; ++k) r.n[k] += rows[i].n[k];
-          ++i;
-        }
-        other.push_back(r);
-      }
-      rows.swap(other);
-    }
-    out.clear();
-    for (const AllelicRow& r : rows) {
-      while (r.pos >= g.start[chr + 1]) ++chr;  // (ascending positions; next lies in the same chromosome)
-      hostio::put_allelic_line(out, g.name[chr], r.pos - g.start[chr], r.next - g.start[chr], r.n);
-      couples += r.n[0] + r.n[1] + r.n[2] + r.n[3];
-    }
-    n_total += rows.size();
-    if (out.n) mf.write(out.p, out.n);
-  }
-  mf.close();
-  if (verbose)
-    fprintf(stderr, "[walt_amd allelic: %llu entries, %llu couples of neighbouring CpGs]\n", (unsigned long long)n_total,
+  void report(uint64_t n_rows) {
+    fprintf(stderr, "[walt_amd allelic: %llu entries, %llu couples of neighbouring CpGs]\n", (unsigned long long)n_rows,
             (unsigned long long)couples);
-}
+  }
+};
 
 // ---------------------------------------------------------------- -ME: four-CpG epiallele patterns per read
-// One window table per device of the run, as PairSet.  At the end of a read file the entries are extracted window by
-// window of forward positions.  On one device -MEN is the extraction's min_total; with several the host extracts every
-// entry that got a read, merges by position adding the counts, and applies -MEN to the merged totals.
-struct EpiSet {
-  vector<walt_epialleles*> p;
-  void open(const vector<walt_index*>& idx) {
-    p.assign(idx.size(), nullptr);
-    for (size_t d = 0; d < idx.size(); ++d)
-      if (walt_epialleles_create(idx[d], &p[d]) != WALT_OK) { const string e = walt_last_error(); close(); die(e); }
+// As the pair table, in windows of half as many positions (an entry is three times as large).  On one device -MEN is
+// the extraction's min_total; with several the host extracts every entry that got a read, merges, and applies -MEN to
+// the merged totals.
+struct WindowTable {
+  typedef walt_epiallele_site Site;
+  typedef hostio::EpialleleRow Row;
+  static constexpr int kOut = kEpialleles;
+  static constexpr uint32_t kWindow = kCountsWindow / 2;
+  uint32_t min_reads, min_extracted;  // -MEN; the same on one device, 1 on several
+  uint64_t windows;
+  static uint64_t capacity(uint64_t window) { return window / 2 + 1; }  // pairs do not overlap
+  int extract(walt_epialleles* p, uint32_t lo, uint32_t hi, Site* buf, uint64_t cap, uint64_t* n) {
+    return walt_epialleles_extract(p, lo, hi, min_extracted, buf, cap, n);
   }
-  void close() {  // (before the indexes are closed)
-    for (walt_epialleles*& q : p) { if (q) walt_epialleles_destroy(q); q = nullptr; }
-    p.clear();
+  static Row row(const Site& b) {
+    Row r = {b.pos, b.last, {}};
+    for (int k = 0; k < 16; ++k) r.n[k] = b.n[k];
+    return r;
   }
-  bool on() const { return !p.empty(); }
-  walt_epialleles* of(size_t d) const { return on() ? p[d] : nullptr; }
-};
-static void write_epialleles(const string& out_file, EpiSet& es, const GenomeInfo& g, uint32_t min_reads, bool verbose) {
-  OutFile mf;
-  if (!mf.open_append(out_file + ".epialleles")) die("cannot open input file " + out_file + ".epialleles");
-  const uint64_t genome_len = g.start.back();
-  const uint64_t window = std::min<uint64_t>(kCountsWindow / 2, genome_len);
-  const uint64_t cap = window / 2 + 1;  // pairs do not overlap
-  vector<walt_epiallele_site> buf((size_t)cap);  // allocated once
-  vector<hostio::EpialleleRow> rows, add, other;
-  const bool merge = es.p.size() > 1;
-  uint64_t n_total = 0, windows = 0;
-  uint32_t chr = 0;
-  Sink out;
-  for (uint64_t lo = 0; lo < genome_len; lo += window) {
-    const uint64_t hi = std::min<uint64_t>(lo + window, genome_len);
-    rows.clear();
-    for (size_t d = 0; d < es.p.size(); ++d) {
-      uint64_t n = 0;
-      check(walt_epialleles_extract(es.p[d], (uint32_t)lo, (uint32_t)hi, merge ? 1 : min_reads, buf.data(), cap, &n));
-      add.resize((size_t)n);
-      for (uint64_t i = 0; i < n; ++i) {
-        add[i].pos = buf[i].pos;
-        add[i].last = buf[i].last;
-        for (int k = 0; k < 16; ++k) add[i].n[k] = buf[i].n[k];
-      }
-      hostio::merge_epiallele_rows(rows, add.data(), add.size(), other);
-    }
-    out.clear();
-    for (const hostio::EpialleleRow& r : rows) {
-      const uint64_t total = hostio::epiallele_row_total(r);
-      if (total < min_reads) continue;
-      while (r.pos >= g.start[chr + 1]) ++chr;  // (ascending positions; last lies in the same chromosome)
-      hostio::put_epiallele_line(out, g.name[chr], r.pos - g.start[chr], r.last - g.start[chr], r.n);
-      windows += total;
-      ++n_total;
-    }
-    if (out.n) mf.write(out.p, out.n);
+  static void add(Row& r, const Row& o) { hostio::add_counter_row(r, o); }
+  bool keep(const Row& r) {
+    const uint64_t total = hostio::epiallele_row_total(r);
+    if (total >= min_reads) windows += total;
+    return total >= min_reads;
   }
-  mf.close();
-  if (verbose)
-    fprintf(stderr, "[walt_amd epialleles: %llu entries, %llu windows of four neighbouring CpGs]\n", (unsigned long long)n_total,
+  void line(Sink& out, const string& chrom, uint32_t chrom_start, const Row& r) {  // (last lies in the same chromosome)
+    hostio::put_epiallele_line(out, chrom, r.pos - chrom_start, r.last - chrom_start, r.n);
+  }
+  void report(uint64_t n_rows) {
+    fprintf(stderr, "[walt_amd epialleles: %llu entries, %llu windows of four neighbouring CpGs]\n", (unsigned long long)n_rows,
             (unsigned long long)windows);
-}
+  }
+};
 
 // ---------------------------------------------------------------- -D: PCR duplicates
 // One duplicate set per read file, on the first device of the run.  A batch is mapped by all devices first; then the
@@ -717,10 +695,9 @@ struct DupSet {
     if (records) snprintf(num, sizeof num, "records: %llu\nduplicates: %llu\nduplication rate: %.6f\n", (unsigned long long)records,
                           (unsigned long long)duplicates, (double)duplicates / (double)records);
     else snprintf(num, sizeof num, "records: 0\nduplicates: 0\nduplication rate: NA\n");
-    OutFile f;
-    if (!f.open_append(out_file + ".dupstats")) die("cannot open input file " + out_file + ".dupstats");
-    f.write(num, strlen(num));
-    f.close();
+    Sink ms;
+    ms.lit(num);
+    Append(out_file, kDupstats).write(ms);
   }
 };
 
@@ -763,10 +740,7 @@ struct FilterSet {
     Sink ms;
     const uint32_t r[4] = {rule.min_meth, rule.min_run, rule.min_percent, rule.min_total};
     hostio::put_filter_block(ms, records, filtered, r);
-    OutFile f;
-    if (!f.open_append(out_file + ".filterstats")) die("cannot open input file " + out_file + ".filterstats");
-    f.write(ms.p, ms.n);
-    f.close();
+    Append(out_file, kFilterstats).write(ms);
     if (verbose) fwrite(ms.p, 1, ms.n, stderr);
   }
 };
@@ -902,6 +876,194 @@ static void leave_now(bool verbose) {
   _exit(bad ? EXIT_FAILURE : EXIT_SUCCESS);
 }
 
+// ---------------------------------------------------------------- what takes the methylation calls of a read file
+// A slot is one read of a record: the read of a single-end run, mate k of a paired-end one.  The batch's per-record bytes
+// (conversions, duplicate and filter verdicts, skip bytes) hold n_slots bytes per record, slot k's at offset k.
+// One slot's view of a share: what the calling calls take, each pointer at the share's first record
+struct SlotView {
+  const char* bases;
+  const uint64_t* offsets;
+  const void* rec;  // the slot's walt_best_match of the first record; rec_stride bytes to the next
+  size_t rec_stride;
+  const uint8_t* conv;  // -R -RP: the conversion of each record, or null: `conversion` for all
+  int conversion;
+  const uint32_t* clip;  // -C
+  char* calls;           // -M -sam: the batch's calls, at the offsets of its bases
+  walt_meth_stats* stats;
+  uint8_t* filt;        // -F: the verdicts
+  const uint8_t* skip;  // -D -F: what keeps a record out of the counts
+  size_t stride;        // of conv, filt and skip: n_slots
+  const uint32_t* excl;  // -NO: the interval words (the user's mate 2 only)
+  uint32_t table;        // -MB
+  uint32_t ignore5, ignore3;
+};
+
+struct Consumers {
+  const DeviceSet* dev = nullptr;
+  bool calling = false;  // something takes the calls
+  int n_slots = 1;
+  PileUps pile;        // both mates into the device's pile-up
+  MbiasSet mbs;
+  PairTables pairs;    // both mates into the same table, each by itself
+  WindowTables epi;    // likewise
+  DupSet dups;
+  FilterSet flt;
+  // the current batch
+  vector<uint8_t> conv;      // -R -RP: the conversion of every record's slots ('T' / 'A')
+  vector<char> calls[2];     // -M -sam: the methylation calls of each slot's batch, at the offsets of its bases
+  vector<uint32_t> clip[2];  // -C: the clip point of every read
+  // -NO: per pair, the read positions of the user's mate 2 that its mate 1 already calls (include/walt_amd.h, "overlap of
+  // a pair").  The totals: pairs with an overlap, mate-2 bases left uncalled
+  vector<uint32_t> excl;
+  vector<walt_meth_stats> meth_of;  // [device * n_slots + slot]
+  vector<uint64_t> overlap_of;      // [device * 2 + total]
+  // the read file so far
+  walt_meth_stats meth_total[2];  // per slot
+  uint64_t overlap_total[2] = {0, 0};
+
+  void open(const Options& o, const DeviceSet& devices, int slots) {
+    dev = &devices;
+    calling = o.consumer();
+    n_slots = slots;
+    const size_t n = dev->size();
+    if (o.piling()) pile.open(n, [&](size_t d, walt_pileup** h) { return walt_pileup_create(dev->idx[d], h); });
+    if (o.mbias) mbs.open(n, [&](size_t d, walt_mbias** h) { return walt_mbias_create(dev->ids[d], (uint32_t)slots, h); });
+    if (o.allelic) pairs.open(n, [&](size_t d, walt_cpgpairs** h) { return walt_cpgpairs_create(dev->idx[d], h); });
+    if (o.epialleles) epi.open(n, [&](size_t d, walt_epialleles** h) { return walt_epialleles_create(dev->idx[d], h); });
+    if (o.dedup) dups.open(dev->ids[0]);
+    flt.open(o);
+    memset(meth_total, 0, sizeof meth_total);
+  }
+  // bt[k], adaptors[k]: slot k's reads and the adaptor they were clipped at
+  void start_batch(const Options& o, const Batch* bt, const string* adaptors, bool both_conversions, int T) {
+    const size_t n_devices = dev->size();
+    const uint32_t n = bt[0].n;
+    const size_t bytes = (size_t)n_slots * n;
+    if (both_conversions && conv.size() < bytes) conv.resize(bytes);
+    meth_of.resize(n_slots * n_devices);
+    memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
+    for (int k = 0; k < n_slots && calling; ++k) {
+      if (o.meth && o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
+      if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
+    }
+    if (o.no_overlap) {
+      overlap_of.assign(2 * n_devices, 0);
+      if (excl.size() < n) excl.resize(n);
+    }
+    if (flt.on()) flt.start(bytes);
+  }
+  const uint8_t* dup_bytes() const { return dups.on() ? dups.dup.data() : nullptr; }
+  // slot k of the share of device d that starts at record lo; ignore: the slot's -I5 / -I3 bounds
+  SlotView view(const Options& o, size_t d, uint32_t lo, int k, const Batch& b, const void* rec, size_t rec_stride,
+                bool both_conversions, int conversion, const uint32_t* ignore) {
+    const size_t at = (size_t)n_slots * lo + k;
+    const uint8_t* skip = flt.on() ? flt.skip.data() : dup_bytes();  // (-F: the verdicts ORed with -D's, FilterSet::merge)
+    SlotView v;
+    v.bases = b.bases; v.offsets = b.offsets + lo;
+    v.rec = rec; v.rec_stride = rec_stride;
+    v.conv = both_conversions ? conv.data() + at : nullptr; v.conversion = conversion;
+    v.clip = clip[k].empty() ? nullptr : clip[k].data() + lo;
+    v.calls = o.meth && o.sam ? calls[k].data() : nullptr;
+    v.stats = o.meth ? &meth_of[n_slots * d + k] : nullptr;
+    v.filt = flt.on() ? flt.filt.data() + at : nullptr;
+    v.skip = skip ? skip + at : nullptr;
+    v.stride = n_slots;
+    v.excl = nullptr;
+    v.table = (uint32_t)k;
+    v.ignore5 = ignore[0]; v.ignore3 = ignore[1];
+    return v;
+  }
+  // The calls of one slot of a share, on the device that mapped it.  With a rule (-F -FC -FP) the verdict pass: the calls
+  // of the whole read up to its clip point, whatever -I5 / -I3 say, stay on the device and are judged there.  Without one
+  // the pass that counts: one call takes whatever the options give it -- pile-up, skip bytes, interval words, bias set,
+  // pair table, window table -- each null without its option (all null: walt_meth_call_batch) and the ignored read ends
+  // 0 without theirs, so that a run launches only the kernels its options ask for.
+  int call_slot(size_t d, uint32_t n, const SlotView& v, const walt_nonconv_rule* rule) const {
+    walt_index* idx = dev->idx[d];
+    if (rule)
+      return walt_meth_nonconv_batch(idx, v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride, v.conversion, v.clip,
+                                     nullptr, rule, v.filt, v.stride, nullptr);
+    return walt_meth_pileup_batch_epi(idx, pile.of(d), v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride,
+                                      v.conversion, v.clip, v.calls, nullptr, v.stats, v.skip, v.stride, v.excl, mbs.of(d),
+                                      v.table, v.ignore5, v.ignore3, pairs.of(d), epi.of(d));
+  }
+  // The end of a read file: <out>.methstats, the pile-up's files, <out>.mbias, .allelic, .epialleles, .dupstats and
+  // .filterstats, each table cleared or closed behind its file.  slot_of_user_mate: null for single-end reads; for pairs
+  // the slot that holds the user's mate 1 and mate 2 (exchanged under -P), whose blocks get a heading each.
+  void finish(const Options& o, const string& out_file, const GenomeInfo& g, const int* slot_of_user_mate) {
+    auto blocks = [&](Sink& ms, auto put) {
+      for (int u = 0; u < n_slots; ++u) {
+        if (slot_of_user_mate) ms.lit(u ? "mate2\n" : "mate1\n");
+        put(slot_of_user_mate ? slot_of_user_mate[u] : 0);
+      }
+    };
+    Sink settings;  // the lines behind the blocks of <out>.methstats, also written under -v
+    if (o.no_overlap) {  // over all unique proper pairs, duplicates (-D) included
+      char overlap[96];
+      snprintf(overlap, sizeof overlap, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
+      settings.lit(overlap);
+    }
+    if (o.ignoring()) hostio::put_ignore_line(settings, o.ignore, 2 * n_slots);
+    if (o.meth) {
+      Sink ms;
+      blocks(ms, [&](int slot) { put_meth_block(ms, meth_total[slot]); });
+      if (settings.n) ms.put(settings.p, settings.n);
+      Append(out_file, kMethstats).write(ms);
+    }
+    if (o.verbose && settings.n) fwrite(settings.p, 1, settings.n, stderr);
+    if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
+    if (mbs.on()) {
+      Sink ms;
+      blocks(ms, [&](int slot) { mbias_block(mbs, ms, (uint32_t)slot); });
+      mbias_write(mbs, out_file, ms);
+      mbs.close();
+    }
+    if (pairs.on()) {
+      PairTable t = {0};
+      write_window_table(t, pairs, out_file, g, o.verbose);
+      pairs.close();
+    }
+    if (epi.on()) {
+      WindowTable t = {o.epi_min, epi.p.size() > 1 ? 1 : o.epi_min, 0};
+      write_window_table(t, epi, out_file, g, o.verbose);
+      epi.close();
+    }
+    if (dups.on()) { dups.write_stats(out_file); dups.close(); }
+    if (flt.on()) flt.write_stats(out_file, o.verbose);
+  }
+};
+
+// One batch.  Without -D every device maps its share and makes the share's calls behind it.  With -D every share is
+// mapped first, then feed() puts the whole batch's records through the duplicate set in input order (so the verdict
+// depends neither on -N nor on -g), and only then are the calls made, share by share, with the verdicts as skip bytes.
+// map_share(d, lo, hi) and meth_share(d, lo, hi) return a status; the batch's totals are added to the read file's.
+template <class Map, class Feed, class Meth>
+static void run_batch(Consumers& c, uint32_t n, Map map_share, Feed feed, Meth meth_share) {
+  const DeviceSet& dev = *c.dev;
+  if (!c.dups.on()) {
+    dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
+      const int rc = map_share(d, lo, hi);
+      return rc == WALT_OK && c.calling ? meth_share(d, lo, hi) : rc;
+    });
+  } else {
+    dev.for_each_share(n, map_share);
+    feed();
+    if (c.calling) dev.for_each_share(n, meth_share);
+  }
+  for (size_t i = 0; i < c.meth_of.size(); ++i) add_meth(c.meth_total[i % c.n_slots], c.meth_of[i]);
+  for (size_t i = 0; i < c.overlap_of.size(); ++i) c.overlap_total[i & 1] += c.overlap_of[i];
+}
+
+// the batch's records in page-locked memory, grown by an eighth more than asked so that equal batches allocate once
+template <class R>
+static void reserve_records(R*& res, size_t& cap, uint32_t n) {
+  if (cap >= n) return;
+  walt_host_free(res);
+  res = nullptr;
+  cap = n + n / 8;
+  check(walt_host_alloc(cap * sizeof(R), (void**)&res));
+}
+
 // ProcessSingledEndReads, mapping.cpp:421-526
 static void process_se(const Options& o, const string& reads_file, const string& out_file, bool last_file) {
   const int T = host_threads(o);
@@ -921,19 +1083,8 @@ static void process_se(const Options& o, const string& reads_file, const string&
   });
   DeviceSet dev;
   dev.open(o, (o.rpbat ? WALT_STRANDS_ALL : o.ag ? WALT_STRANDS_GA : WALT_STRANDS_CT) | (o.consumer() ? WALT_WITH_REFERENCE : 0u));
-  const bool calling = o.consumer();
-  PileSet pile;
-  if (o.piling()) pile.open(dev.idx);
-  MbiasSet mbs;
-  if (o.mbias) mbs.open(dev.ids, 1);
-  PairSet pairs;
-  if (o.allelic) pairs.open(dev.idx);
-  EpiSet epi;
-  if (o.epialleles) epi.open(dev.idx);
-  DupSet dups;
-  if (o.dedup) dups.open(dev.ids[0]);
-  FilterSet flt;
-  flt.open(o);
+  Consumers cs;
+  cs.open(o, dev, 1);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
@@ -946,11 +1097,6 @@ static void process_se(const Options& o, const string& reads_file, const string&
   if (o.sam) { string h = sam_head(g); fout.write(h.data(), h.size()); }
   walt_best_match* res = nullptr;
   size_t res_cap = 0;
-  vector<uint8_t> conv;  // -R: the conversion of every record ('T' / 'A')
-  vector<char> calls;    // -M -sam: the methylation calls of the batch, at the offsets of its bases
-  vector<uint32_t> clip; // -M -C: the clip point of every read
-  walt_meth_stats meth_total;
-  memset(&meth_total, 0, sizeof meth_total);
   vector<Sink> sinks((size_t)T * kSinks);
   vector<SeCounts> acc(T);
   // Only the ingest runs ahead.  Storing a batch's lines from a helper thread while the next batch is formatted was
@@ -973,63 +1119,29 @@ static void process_se(const Options& o, const string& reads_file, const string&
       rd.threads = T_bg;
       pre.start([&, cur]() { rd.load(o.batch_size, o.adaptor, bt[cur ^ 1]); });
     }
-    if (res_cap < n) {
-      walt_host_free(res);
-      res = nullptr;
-      res_cap = n + n / 8;
-      check(walt_host_alloc(res_cap * sizeof(walt_best_match), (void**)&res));
-    }
+    reserve_records(res, res_cap, n);
     t0 = now_s();
     vector<uint64_t> short_of(dev.size(), 0);
-    if (o.rpbat && conv.size() < n) conv.resize(n);
-    vector<walt_meth_stats> meth_of(dev.size());
-    memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
-    if (o.meth && o.sam && calls.size() < b.offsets[n]) calls.resize(b.offsets[n]);
-    if (calling && !o.adaptor.empty()) clip_points(b, o.adaptor, T, clip);
+    cs.start_batch(o, &b, &o.adaptor, o.rpbat, T);
     auto map_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs;
-      const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, conv.data() + lo, &bs)
+      const int rc = o.rpbat ? walt_map_se_rpbat_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.max_mismatches, o.b, res + lo, cs.conv.data() + lo, &bs)
                              : walt_map_se_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, o.ag, o.max_mismatches, o.b, res + lo, &bs);
       short_of[d] = bs.too_short;
       return rc;
     };
-    // the calls of a share, on the device that mapped it: one call takes whatever the options give it -- the pile-up (-MC),
-    // the verdicts as skip bytes (-D: duplicates neither piled up nor summed), the bias set (-MB), the pair table (-MA), the window table (-ME) -- each null without its
-    // option (all null: walt_meth_call_batch) -- and the ignored read ends (-I5 / -I3; both 0 without them: the kernels a
-    // run always launched)
-    // -F -FC -FP: first the share's verdicts (the whole read up to its clip point, whatever -I5 / -I3 say), ORed into the
-    // skip bytes beside -D's
-    if (flt.on()) flt.start(n);
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
-      if (!calling) return (int)WALT_OK;
-      const uint8_t* skip = dups.on() ? dups.dup.data() + lo : nullptr;
-      if (flt.on()) {
-        const int rc = walt_meth_nonconv_batch(dev.idx[d], b.bases, b.offsets + lo, hi - lo, res + lo, sizeof(walt_best_match),
-                                               o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
-                                               clip.empty() ? nullptr : clip.data() + lo, nullptr, &flt.rule, flt.filt.data() + lo, 1, nullptr);
+      const SlotView v = cs.view(o, d, lo, 0, b, res + lo, sizeof(walt_best_match), o.rpbat, o.ag ? 'A' : 'T', o.ignore);
+      if (cs.flt.on()) {  // first the share's verdicts, ORed into the skip bytes beside -D's
+        const int rc = cs.call_slot(d, hi - lo, v, &cs.flt.rule);
         if (rc != WALT_OK) return rc;
-        flt.merge(lo, hi, dups.on() ? dups.dup.data() : nullptr);
-        skip = flt.skip.data() + lo;
+        cs.flt.merge(lo, hi, cs.dup_bytes());
       }
-      return walt_meth_pileup_batch_epi(dev.idx[d], o.piling() ? pile.p[d] : nullptr, b.bases, b.offsets + lo, hi - lo, res + lo,
-                                         sizeof(walt_best_match), o.rpbat ? conv.data() + lo : nullptr, 1, o.ag ? 'A' : 'T',
-                                         clip.empty() ? nullptr : clip.data() + lo, o.meth && o.sam ? calls.data() : nullptr, nullptr,
-                                         o.meth ? &meth_of[d] : nullptr, skip, 1, nullptr,
-                                         mbs.of(d), 0, o.ignore[0], o.ignore[1], pairs.of(d), epi.of(d));
+      return cs.call_slot(d, hi - lo, v, nullptr);
     };
-    if (!dups.on()) {
-      dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
-        const int rc = map_share(d, lo, hi);
-        return rc == WALT_OK ? meth_share(d, lo, hi) : rc;
-      });
-    } else {  // -D: every share mapped, then the whole batch through the set in input order, then the calls
-      dev.for_each_share(n, map_share);
-      dups.feed_se(res, o.rpbat ? conv.data() : nullptr, o.ag ? 'A' : 'T', n);
-      if (calling) dev.for_each_share(n, meth_share);
-    }
-    if (flt.on()) flt.count_se(res, dups.on() ? dups.dup.data() : nullptr, n);
+    run_batch(cs, n, map_share, [&]() { cs.dups.feed_se(res, o.rpbat ? cs.conv.data() : nullptr, o.ag ? 'A' : 'T', n); }, meth_share);
+    if (cs.flt.on()) cs.flt.count_se(res, cs.dup_bytes(), n);
     for (uint64_t v : short_of) st.too_short += (uint32_t)v;
-    for (const walt_meth_stats& m : meth_of) add_meth(meth_total, m);
     t_map += now_s() - t0;
     if (!more) unlock_idle.start([&, cur]() { bt[cur ^ 1].release(); });
     t0 = now_s();
@@ -1044,14 +1156,14 @@ static void process_se(const Options& o, const string& reads_file, const string&
       for (uint32_t j = lo; j < hi; ++j) {
         c.update(res[j].times);
         // -R: a record of the G->A conversion is written as a -A run writes it (MR), or tagged (SAM)
-        const bool ag = o.rpbat ? conv[j] == 'A' : o.ag;
-        const bool dup = dups.on() && dups.dup[j];  // (a duplicate has times == 1: its only line is the main file's)
-        const bool gone = flt.on() && flt.filt[j];  // (and so has a filtered read)
+        const bool ag = o.rpbat ? cs.conv[j] == 'A' : o.ag;
+        const bool dup = cs.dups.on() && cs.dups.dup[j];  // (a duplicate has times == 1: its only line is the main file's)
+        const bool gone = cs.flt.on() && cs.flt.filt[j];  // (and so has a filtered read)
         if (!o.sam) { if (!dup && !gone) out_single_results(res[j], b.name(j), b.seq(j), b.score(j), g, ag, side.out_amb, side.out_unm,
                                                    s[kMain], s[kAmb1], s[kUnm1]); }
         else out_single_sam(res[j], b.name(j), b.seq(j), b.score(j), g, side.out_amb, side.out_unm, s[kMain],
                             o.rpbat ? (ag ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
-                            o.meth ? View{calls.data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0},
+                            o.meth ? View{cs.calls[0].data() + b.offsets[j], b.seq(j).len} : View{nullptr, 0},
                             (dup ? 0x400 : 0) + (gone ? 0x200 : 0));
       }
       acc[t] = c;
@@ -1080,29 +1192,9 @@ static void process_se(const Options& o, const string& reads_file, const string&
     Sink ms;
     st.put_block(ms, 0);
     ms.ch('\n');
-    OutFile mf;
-    if (!mf.open_append(out_file + ".mapstats")) die("cannot open input file " + out_file + ".mapstats");
-    mf.write(ms.p, ms.n);
-    mf.close();
+    Append(out_file, kMapstats).write(ms);
   }
-  if (o.meth) {
-    Sink ms;
-    put_meth_block(ms, meth_total);
-    if (o.ignoring()) hostio::put_ignore_line(ms, o.ignore, 2);
-    write_methstats(out_file, ms);
-  }
-  if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\n", o.ignore[0], o.ignore[1]);
-  if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
-  if (mbs.on()) {
-    Sink ms;
-    mbs.block(ms, 0);
-    mbs.write(out_file, ms);
-    mbs.close();
-  }
-  if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
-  if (epi.on()) { write_epialleles(out_file, epi, g, o.epi_min, o.verbose); epi.close(); }
-  if (dups.on()) { dups.write_stats(out_file); dups.close(); }
-  if (flt.on()) flt.write_stats(out_file, o.verbose);
+  cs.finish(o, out_file, g, nullptr);
   const double t_c0 = now_s();
   dev.close();
   if (o.verbose)
@@ -1252,19 +1344,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
   double t0 = now_s();
   DeviceSet dev;
   dev.open(o, WALT_STRANDS_ALL | (o.consumer() ? WALT_WITH_REFERENCE : 0u));  // (all four strands are resident: one pass over them)
-  const bool calling = o.consumer();
-  PileSet pile;  // -MC: both mates into the same pile-up
-  if (o.piling()) pile.open(dev.idx);
-  MbiasSet mbs;  // -MB: table k takes slot k
-  if (o.mbias) mbs.open(dev.ids, 2);
-  PairSet pairs;  // -MA: both mates into the same table, each by itself
-  if (o.allelic) pairs.open(dev.idx);
-  EpiSet epi;  // -ME: likewise
-  if (o.epialleles) epi.open(dev.idx);
-  DupSet dups;
-  if (o.dedup) dups.open(dev.ids[0]);
-  FilterSet flt;
-  flt.open(o);
+  Consumers cs;
+  cs.open(o, dev, 2);
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
@@ -1287,18 +1368,11 @@ static void process_pe(const Options& o, const string& file1, const string& file
   Batch bts[2][2];  // [buffer][mate]: one pair of batches is mapped and written while the next is read
   walt_pair_result* pr = nullptr;
   size_t pr_cap = 0;
-  vector<uint8_t> conv;  // -RP: the conversion of each mate's record ('T' / 'A'), two per pair
-  vector<char> calls[2];     // -M -sam: the methylation calls of each slot's batch, at the offsets of its bases
-  vector<uint32_t> clip[2];  // -M -C: the clip points
-  // -NO: per pair, the read positions of the user's mate 2 that its mate 1 already calls (include/walt_amd.h, "overlap of
-  // a pair"); the user's mate 1 sits in slot 1 under -P.  The totals: pairs with an overlap, mate-2 bases left uncalled
-  vector<uint32_t> excl;
-  const int over_slot = pbat ? 0 : 1;  // the slot whose calls take the interval
-  // -I5 -I3 -I5R2 -I3R2: the bounds are given for the user's mate 1 and mate 2; under -P slot 0 holds the user's mate 2
-  const uint32_t* const trim_slot[2] = {o.ignore + (pbat ? 2 : 0), o.ignore + (pbat ? 0 : 2)};
-  uint64_t overlap_total[2] = {0, 0};
-  walt_meth_stats meth_total[2];  // per slot
-  memset(meth_total, 0, sizeof meth_total);
+  // the slots of the user's mate 1 and mate 2: under -P slot 0 holds the user's mate 2.  -NO gives the interval words to
+  // the calls of the user's mate 2; -I5 -I3 -I5R2 -I3R2 are given for the user's mate 1 and mate 2
+  const int user_slot[2] = {pbat ? 1 : 0, pbat ? 0 : 1};
+  const int over_slot = user_slot[1];
+  const uint32_t* const trim_slot[2] = {o.ignore + 2 * user_slot[0], o.ignore + 2 * user_slot[1]};
   vector<Sink> sinks((size_t)T * kSinks);
   vector<PeAcc> acc(T);
   Prefetch pre, unlock_idle;  // (the idle buffers of the last batch: see process_se)
@@ -1323,64 +1397,37 @@ static void process_pe(const Options& o, const string& file1, const string& file
       pre.start([&, cur]() { load_pair(bts[cur ^ 1]); });
     }
     total_pairs += n;
-    if (pr_cap < n) {
-      walt_host_free(pr);
-      pr = nullptr;
-      pr_cap = n + n / 8;
-      check(walt_host_alloc(pr_cap * sizeof(walt_pair_result), (void**)&pr));
-    }
+    reserve_records(pr, pr_cap, n);
     t0 = now_s();
     // the best pair's two candidates come back inside walt_pair_result (m1/m2), so the ranked lists stay on the GPU
     vector<uint64_t> short1(dev.size(), 0), short2(dev.size(), 0);
-    if (rp && conv.size() < 2 * (size_t)n) conv.resize(2 * (size_t)n);
-    vector<walt_meth_stats> meth_of(2 * dev.size());
-    memset(meth_of.data(), 0, meth_of.size() * sizeof(walt_meth_stats));
-    for (int k = 0; k < 2 && calling; ++k) {
-      if (o.meth && o.sam && calls[k].size() < bt[k].offsets[n]) calls[k].resize(bt[k].offsets[n]);
-      if (!adaptors[k].empty()) clip_points(bt[k], adaptors[k], T, clip[k]);
-    }
+    cs.start_batch(o, bt, adaptors, rp, T);
     auto map_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       walt_batch_stats bs[2];
       const int rc = rp ? walt_map_pe_rpbat_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo,
                                                   hi - lo, o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo,
-                                                  conv.data() + 2 * (size_t)lo, bs)
+                                                  cs.conv.data() + 2 * (size_t)lo, bs)
                         : walt_map_pe_batch(dev.idx[d], bt[0].bases, bt[0].offsets + lo, bt[1].bases, bt[1].offsets + lo, hi - lo,
                                             o.max_mismatches, o.b, o.top_k, o.frag_range, pr + lo, nullptr, nullptr, nullptr, nullptr, bs);
       short1[d] = bs[0].too_short;
       short2[d] = bs[1].too_short;
       return rc;
     };
-    vector<uint64_t> overlap_of;  // -NO: the totals of each device's share
-    if (o.no_overlap) {
-      overlap_of.assign(2 * dev.size(), 0);
-      if (excl.size() < n) excl.resize(n);
-    }
-    // The calls of a share, on the device that mapped it.  -NO: first the share's intervals from the records in user order.
-    // Then both slots through one call that takes whatever the options give it -- the pile-up (-MC: both mates into the
-    // device's), the verdicts as skip bytes (-D), the interval words for the user's mate 2 (-NO; none for mate 1: the call
-    // it always got), the bias set (-MB: table k takes slot k), the pair table (-MA), the window table (-ME) -- each null without its option -- and the slot's ignored
-    // read ends (0 without -I5 -I3 -I5R2 -I3R2: the kernels a run always launched).  Slot 0 was mapped C->T,
-    // slot 1 G->A (-RP: as conv says).
-    // -F -FC -FP: before all that the verdicts of the share's two slots (each mate's whole read up to its clip point), the
-    // pair rule over them, and the skip bytes: the verdicts ORed with -D's
-    if (flt.on()) flt.start(2 * (size_t)n);
+    // Slot 0 was mapped C->T, slot 1 G->A (-RP: as conv says).  -F -FC -FP: first the verdicts of the share's two slots and
+    // the pair rule over them, ORed into the skip bytes beside -D's.  -NO: then the share's intervals, from the records in
+    // user order.  Then the calls of both slots.
     auto meth_share = [&](size_t d, uint32_t lo, uint32_t hi) {
       int rc = WALT_OK;
-      if (!calling) return rc;
-      const uint8_t* skip = dups.on() ? dups.dup.data() : nullptr;
-      if (flt.on()) {
-        for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-          rc = walt_meth_nonconv_batch(dev.idx[d], bt[k].bases, bt[k].offsets + lo, hi - lo, k ? &pr[lo].m2 : &pr[lo].m1,
-                                       sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr, 2, k ? 'A' : 'T',
-                                       clip[k].empty() ? nullptr : clip[k].data() + lo, nullptr, &flt.rule,
-                                       flt.filt.data() + 2 * (size_t)lo + k, 2, nullptr);
-        if (rc == WALT_OK) rc = walt_nonconv_pairs_batch(dev.idx[d], pr + lo, hi - lo, flt.filt.data() + 2 * (size_t)lo);
+      SlotView v[2] = {cs.view(o, d, lo, 0, bt[0], &pr[lo].m1, sizeof(walt_pair_result), rp, 'T', trim_slot[0]),
+                       cs.view(o, d, lo, 1, bt[1], &pr[lo].m2, sizeof(walt_pair_result), rp, 'A', trim_slot[1])};
+      if (cs.flt.on()) {
+        for (int k = 0; k < 2 && rc == WALT_OK; ++k) rc = cs.call_slot(d, hi - lo, v[k], &cs.flt.rule);
+        if (rc == WALT_OK) rc = walt_nonconv_pairs_batch(dev.idx[d], pr + lo, hi - lo, cs.flt.filt.data() + 2 * (size_t)lo);
         if (rc != WALT_OK) return rc;
-        flt.merge(2 * (size_t)lo, 2 * (size_t)hi, skip);
-        skip = flt.skip.data();
+        cs.flt.merge(2 * (size_t)lo, 2 * (size_t)hi, cs.dup_bytes());
       }
       if (o.no_overlap) {
-        const int u1 = 1 - over_slot;
+        const int u1 = user_slot[0];
         vector<walt_pair_result> user;  // -P: mate 1 of the records is the user's mate 2
         if (pbat) {
           user.assign(pr + lo, pr + hi);
@@ -1388,33 +1435,15 @@ static void process_pe(const Options& o, const string& file1, const string& file
         }
         // (with ignored read ends, mate 1's called span is what they leave of it; mate 2's enter the second total)
         rc = walt_pair_overlap_batch_trim(dev.idx[d], pbat ? user.data() : pr + lo, bt[u1].offsets + lo, bt[over_slot].offsets + lo, hi - lo,
-                                          clip[u1].empty() ? nullptr : clip[u1].data() + lo,
-                                          clip[over_slot].empty() ? nullptr : clip[over_slot].data() + lo, excl.data() + lo,
-                                          &overlap_of[2 * d], o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
+                                          v[u1].clip, v[over_slot].clip, cs.excl.data() + lo, &cs.overlap_of[2 * d], o.ignore[0],
+                                          o.ignore[1], o.ignore[2], o.ignore[3]);
+        v[over_slot].excl = cs.excl.data() + lo;
       }
-      for (int k = 0; k < 2 && rc == WALT_OK; ++k)
-        rc = walt_meth_pileup_batch_epi(dev.idx[d], o.piling() ? pile.p[d] : nullptr, bt[k].bases, bt[k].offsets + lo, hi - lo,
-                                         k ? &pr[lo].m2 : &pr[lo].m1, sizeof(walt_pair_result), rp ? conv.data() + 2 * (size_t)lo + k : nullptr,
-                                         2, k ? 'A' : 'T', clip[k].empty() ? nullptr : clip[k].data() + lo,
-                                         o.meth && o.sam ? calls[k].data() : nullptr, nullptr, o.meth ? &meth_of[2 * d + k] : nullptr,
-                                         skip ? skip + 2 * (size_t)lo + k : nullptr, 2,
-                                         o.no_overlap && k == over_slot ? excl.data() + lo : nullptr, mbs.of(d), (uint32_t)k,
-                                         trim_slot[k][0], trim_slot[k][1], pairs.of(d), epi.of(d));
+      for (int k = 0; k < 2 && rc == WALT_OK; ++k) rc = cs.call_slot(d, hi - lo, v[k], nullptr);
       return rc;
     };
-    if (!dups.on()) {
-      dev.for_each_share(n, [&](size_t d, uint32_t lo, uint32_t hi) {
-        const int rc = map_share(d, lo, hi);
-        return rc == WALT_OK ? meth_share(d, lo, hi) : rc;
-      });
-    } else {  // -D: every share mapped, then the whole batch's pairs through the set in input order, then the calls
-      dev.for_each_share(n, map_share);
-      dups.feed_pe(pr, rp ? conv.data() : nullptr, n);
-      if (calling) dev.for_each_share(n, meth_share);
-    }
-    if (flt.on()) flt.count_pe(pr, dups.on() ? dups.dup.data() : nullptr, n);
-    for (size_t d = 0; d < dev.size(); ++d) { add_meth(meth_total[0], meth_of[2 * d]); add_meth(meth_total[1], meth_of[2 * d + 1]); }
-    for (size_t d = 0; 2 * d < overlap_of.size(); ++d) { overlap_total[0] += overlap_of[2 * d]; overlap_total[1] += overlap_of[2 * d + 1]; }
+    run_batch(cs, n, map_share, [&]() { cs.dups.feed_pe(pr, rp ? cs.conv.data() : nullptr, n); }, meth_share);
+    if (cs.flt.on()) cs.flt.count_pe(pr, cs.dup_bytes(), n);
     for (size_t d = 0; d < dev.size(); ++d) { st1.too_short += (uint32_t)short1[d]; st2.too_short += (uint32_t)short2[d]; }
     t_map += now_s() - t0;
     if (!more) unlock_idle.start([&, cur]() { bts[cur ^ 1][0].release(); bts[cur ^ 1][1].release(); });
@@ -1432,11 +1461,11 @@ static void process_pe(const Options& o, const string& file1, const string& file
         walt_best_match bm1 = {0, 0, '+', {0, 0, 0}, o.max_mismatches}, bm2 = bm1;
         bool is_paired = false;
         int len = 0;
-        const bool ag1 = rp && conv[2 * (size_t)j] == 'A', ag2 = !rp || conv[2 * (size_t)j + 1] == 'A';
+        const bool ag1 = rp && cs.conv[2 * (size_t)j] == 'A', ag2 = !rp || cs.conv[2 * (size_t)j + 1] == 'A';
         // -D: a duplicate's MR line is not written (the one fragment line of a duplicate pair), its SAM lines get 0x400
-        const bool dup1 = dups.on() && dups.dup[2 * (size_t)j], dup2 = dups.on() && dups.dup[2 * (size_t)j + 1];
+        const bool dup1 = cs.dups.on() && cs.dups.dup[2 * (size_t)j], dup2 = cs.dups.on() && cs.dups.dup[2 * (size_t)j + 1];
         // -F -FC -FP: the same for a filtered record, with 0x200 (a unique pair's two bytes are equal: the pair rule)
-        const bool gone1 = flt.on() && flt.filt[2 * (size_t)j], gone2 = flt.on() && flt.filt[2 * (size_t)j + 1];
+        const bool gone1 = cs.flt.on() && cs.flt.filt[2 * (size_t)j], gone2 = cs.flt.on() && cs.flt.filt[2 * (size_t)j + 1];
         if (p.best_times == 1) {
           a.unique_pairs++;
           walt_candidate r1 = {p.m1.genome_pos, p.m1.strand, {0, 0, 0}, p.m1.mismatch};
@@ -1467,8 +1496,8 @@ static void process_pe(const Options& o, const string& file1, const string& file
           fl2 += (dup2 ? 0x400 : 0) + (gone2 ? 0x200 : 0);
           out_paired_sam(bm1, bm2, g, name, q1, k1, q2, k2, len, fl1, fl2, o.ambiguous, o.unmapped, pbat, s[kMain],
                          rp ? (ag1 ? "\tCV:A:A" : "\tCV:A:T") : nullptr, rp ? (ag2 ? "\tCV:A:A" : "\tCV:A:T") : nullptr,
-                         o.meth ? View{calls[0].data() + bt[0].offsets[j], q1.len} : View{nullptr, 0},
-                         o.meth ? View{calls[1].data() + bt[1].offsets[j], q2.len} : View{nullptr, 0});
+                         o.meth ? View{cs.calls[0].data() + bt[0].offsets[j], q1.len} : View{nullptr, 0},
+                         o.meth ? View{cs.calls[1].data() + bt[1].offsets[j], q2.len} : View{nullptr, 0});
         }
       }
       acc[t] = std::move(a);
@@ -1514,38 +1543,9 @@ static void process_pe(const Options& o, const string& file1, const string& file
     }
     snprintf(num, sizeof num, "%g", weighted / pairs_in_hist);
     ms.lit("frag_len_mean: "); ms.lit(num); ms.ch('\n');
-    OutFile mf;
-    if (!mf.open_append(out_file + ".mapstats")) die("cannot open input file " + out_file + ".mapstats");
-    mf.write(ms.p, ms.n);
-    mf.close();
+    Append(out_file, kMapstats).write(ms);
   }
-  if (o.meth) {  // in the user's order (-P: the user's mate 1 sits in slot 1)
-    Sink ms;
-    ms.lit("mate1\n"); put_meth_block(ms, meth_total[pbat ? 1 : 0]);
-    ms.lit("mate2\n"); put_meth_block(ms, meth_total[pbat ? 0 : 1]);
-    if (o.no_overlap) {  // over all unique proper pairs, duplicates (-D) included
-      char num[96];
-      snprintf(num, sizeof num, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
-      ms.lit(num);
-    }
-    if (o.ignoring()) hostio::put_ignore_line(ms, o.ignore, 4);
-    write_methstats(out_file, ms);
-  }
-  if (o.no_overlap && o.verbose)
-    fprintf(stderr, "overlap\t%llu\t%llu\n", (unsigned long long)overlap_total[0], (unsigned long long)overlap_total[1]);
-  if (o.ignoring() && o.verbose) fprintf(stderr, "ignore\t%u\t%u\t%u\t%u\n", o.ignore[0], o.ignore[1], o.ignore[2], o.ignore[3]);
-  if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
-  if (mbs.on()) {  // in the user's order, as <out>.methstats
-    Sink ms;
-    ms.lit("mate1\n"); mbs.block(ms, pbat ? 1 : 0);
-    ms.lit("mate2\n"); mbs.block(ms, pbat ? 0 : 1);
-    mbs.write(out_file, ms);
-    mbs.close();
-  }
-  if (pairs.on()) { write_allelic(out_file, pairs, g, o.verbose); pairs.close(); }
-  if (epi.on()) { write_epialleles(out_file, epi, g, o.epi_min, o.verbose); epi.close(); }
-  if (dups.on()) { dups.write_stats(out_file); dups.close(); }
-  if (flt.on()) flt.write_stats(out_file, o.verbose);
+  cs.finish(o, out_file, g, user_slot);  // in the user's order
   dev.close();
   if (o.verbose)
     fprintf(stderr, "[walt_amd: %d host threads, %zu GPU(s); index %.2f s, ingest not hidden behind the previous batch %.2f s, map %.2f s, "
@@ -1573,16 +1573,9 @@ int main(int argc, const char** argv) {
     vector<string> outs = split_csv(o.out_csv);
     if (outs.size() != 1 && outs.size() != se.size() + p1.size()) die("wrong number of output files: " + o.out_csv);
     if (outs.size() == 1) outs.assign(se.size() + p1.size(), outs[0]);
-    for (auto& f : outs) { std::ofstream out(f); std::ofstream stat(f + ".mapstats"); }  // walt.cpp:230-233
-    if (o.meth) for (auto& f : outs) { std::ofstream stat(f + ".methstats"); }
-    if (o.methcounts) for (auto& f : outs) { std::ofstream counts(f + ".methcounts"); }
-    if (o.levels) for (auto& f : outs) { std::ofstream levels(f + ".levels"); }
-    if (o.regions()) for (auto& f : outs) { std::ofstream regions(f + ".regions"); }
-    if (o.mbias) for (auto& f : outs) { std::ofstream bias(f + ".mbias"); }
-    if (o.allelic) for (auto& f : outs) { std::ofstream allelic(f + ".allelic"); }
-    if (o.epialleles) for (auto& f : outs) { std::ofstream epialleles(f + ".epialleles"); }
-    if (o.dedup) for (auto& f : outs) { std::ofstream stat(f + ".dupstats"); }
-    if (o.filtering()) for (auto& f : outs) { std::ofstream stat(f + ".filterstats"); }
+    for (auto& f : outs) { std::ofstream out(f); }  // walt.cpp:230-233
+    for (const auto& side : kOutput)
+      if (side.on(o)) for (auto& f : outs) { std::ofstream stat(f + side.suffix); }
     if (o.batch_size > 100000000) die("batch size may not exceed100000000");
     if (o.top_k < 2 || o.top_k > 300) die("paired-end candidates must be in [2, 300]");
     size_t k = 0;

@@ -976,6 +976,97 @@ int walt_meth_pileup_batch_epi_device(walt_index* idx, walt_pileup* p, const voi
                                       uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
                                       void* stream);
 
+/* ---- opposite-strand evidence: C>T variant sites found from the reads of the other strand, and kept out of the counts ------
+ * The reference has no such mode (MethPipe's methcounts tags a site as mutated, CpGx, when fewer than half of the
+ * opposite-strand reads show the expected base; MethylDackel drops such sites, --maxVariantFrac / --minOppositeDepth; both
+ * over sorted SAM); the contract is defined here.  Bisulfite turns an unmethylated C into T, so a sample that has T where
+ * the reference has C piles up as a fully unmethylated cytosine.  A read of the other strand covers the same position and
+ * bisulfite leaves it alone there: it shows G for a real C and A for a C>T variant.
+ *
+ * Evidence.  Use the same reference arrays the calling uses: G = R for a '+' record and G = R' for a '-' record.  Use the
+ * same validity rule as the pile-up: times == 1; skip byte 0; genome_pos < genome_len; conversion 'T' or 'A'; read length
+ * 1 to 1024.  A record that passes, at read position i < min(length, call_len) with q = genome_pos + i < hi, adds
+ * evidence as follows.
+ *   conversion 'T': an evidence position is one with G[q] == 'G'; match: the read base is G; other: any other base;
+ *   conversion 'A': an evidence position is one with G[q] == 'C'; match: the read base is C; other: any other base.
+ * This is the calling rule with the conversion exchanged, and with "anything but the reference base" in place of "the
+ * converted base".  A byte that is not A, C, G or T counts as the letter whose bits 2..1 it shares, as in
+ * meth_read_fields.
+ *   The evidence lands on the forward position that pile_forward gives, f = q or f = lo + hi - 1 - q.  Evidence from
+ * ('+','T') and ('-','A') records therefore lands on forward G's, and evidence from ('+','A') and ('-','T') records lands
+ * on forward C's.  Each lands on the site whose methylation calls come from the other two kinds of record.
+ *   -C acts on the evidence through call_len.  -D and -F act on it through skip.  -I5, -I3 and -NO do not act on it: they
+ * are about methylation bias, not about which base was read.  Each mate counts by itself.
+ *   Evidence landing on a forward A or T of R (the N-fill case of "methylation pile-up") is never read.
+ *
+ * Storage.  The evidence lives in a second walt_pileup of the same index: plane 0 (what walt_pileup_read returns as
+ * meth) is match, plane 1 (unmeth) is other; exact 32-bit counters, wrapping beyond 2^32 - 1.  walt_pileup_create,
+ * _clear, _read and _add serve it as they serve the calls, and _read / _add give the fold over several devices.  It takes
+ * 8 x genome_len more bytes of device memory (25 GB at 3.1 Gbp); WALT_ENOMEM as there.
+ *
+ * Rule.  A forward position f with R[f] C or G is judged when match[f] + other[f] >= min_depth.  It is flagged when it is
+ * judged and 100 * other[f] > max_percent * (match[f] + other[f]), computed in 64 bits.  min_depth is 1 to 2^32 - 1,
+ * max_percent 0 to 99 (WALT_EINVAL otherwise).  With max_percent = 50 this is MethPipe's rule exactly.
+ *
+ * walt_meth_evidence_batch[_device] run the evidence kernel alone over a batch given as walt_meth_call_batch[_device]
+ * takes it, plus skip as walt_meth_pileup_batch_skip takes it: strides, refusals, alignment and stream ordering as there;
+ * nothing but the evidence is written.  WALT_EINVAL for a null evidence object or one of another index.  Two streams may
+ * feed one object.
+ *
+ * walt_meth_pileup_batch_ev[_device] are walt_meth_pileup_batch_epi[_device] plus ev: the evidence kernel runs behind the
+ * calling kernel on the same stream, over the batch as staged once.  ev == NULL is exactly the epi form.  WALT_EINVAL when
+ * ev belongs to another index or when ev == p.  Every older entry point is this call with ev == NULL and launches what it
+ * always launched.
+ *
+ * walt_pileup_variants[_device] return the flagged positions of [pos_lo, pos_hi) in ascending order as walt_variant_site
+ * records: strand and context as the extraction gives them, meth and unmeth from p (both may be 0), match and other from
+ * ev.  cap and *n_out behave as in walt_pileup_extract[_device]: nothing is written when the result is over cap (host
+ * form: WALT_EINVAL naming both numbers; device form: *d_n_out > cap says so).  d_out and d_n_out 8-byte aligned.  The
+ * result does not depend on the launch shape (option pile_extract_blocks).
+ *
+ * walt_pileup_mask_variants[_device] zero meth[f] and unmeth[f] of every flagged position of the range in p and give
+ * out[5] = {judged, flagged, masked sites (flagged with a call), methylated calls removed, unmethylated calls removed}.
+ * Masked sites and calls removed are what this call removed: a second call over the same range returns the same judged
+ * and flagged, and zeros for the other three.  All folds are integer and commutative.  d_out: uint64_t[5], 8-byte aligned.
+ *
+ * Both passes: WALT_EINVAL for a null object, for ev == p, for an ev of another index and for a range outside the genome.
+ * They use the table of ev: one of them at a time per evidence object, ordered after the adds of its stream; the host
+ * forms wait for all work on the device first. */
+typedef struct {
+  uint32_t pos, meth, unmeth;
+  uint8_t strand;  /* '+' or '-' */
+  uint8_t context; /* 0 CpG, 1 CHG, 2 CHH, 3 unknown */
+  uint16_t reserved; /* written as 0 */
+  uint32_t match, other; /* the opposite-strand reads that show the reference base / another base */
+} walt_variant_site; /* 24 bytes */
+int walt_meth_evidence_batch(walt_index* idx, walt_pileup* ev, const char* bases, const uint64_t* offsets, uint32_t n,
+                             const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                             int conversion, const uint32_t* call_len, const uint8_t* skip, size_t skip_stride);
+int walt_meth_evidence_batch_device(walt_index* idx, walt_pileup* ev, const void* d_bases, const void* d_offsets, uint32_t n,
+                                    const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                    int conversion, const void* d_call_len, const void* d_skip, size_t skip_stride,
+                                    void* stream);
+int walt_meth_pileup_batch_ev(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                              const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                              int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                              walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                              walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap,
+                              walt_epialleles* ep, walt_pileup* ev);
+int walt_meth_pileup_batch_ev_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                     const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                     int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                     const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                     uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                     walt_pileup* ev, void* stream);
+int walt_pileup_variants(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_depth,
+                         uint32_t max_percent, walt_variant_site* out, uint64_t cap, uint64_t* n_out);
+int walt_pileup_variants_device(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_depth,
+                                uint32_t max_percent, void* d_out, uint64_t cap, void* d_n_out, void* stream);
+int walt_pileup_mask_variants(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_depth,
+                              uint32_t max_percent, uint64_t* out /*[5]*/);
+int walt_pileup_mask_variants_device(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_depth,
+                                     uint32_t max_percent, void* d_out, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

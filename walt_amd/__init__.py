@@ -87,6 +87,10 @@ METH_CONTEXTS = ("CpG", "CHG", "CHH", "unknown")
 meth_site_dtype = np.dtype([("pos", "<u4"), ("meth", "<u4"), ("unmeth", "<u4"), ("strand", "u1"), ("context", "u1"),
                             ("reserved", "<u2")])
 assert meth_site_dtype.itemsize == 16
+# walt_variant_site: a position the opposite-strand evidence flags (include/walt_amd.h, "opposite-strand evidence")
+variant_site_dtype = np.dtype([("pos", "<u4"), ("meth", "<u4"), ("unmeth", "<u4"), ("strand", "u1"), ("context", "u1"),
+                               ("reserved", "<u2"), ("match", "<u4"), ("other", "<u4")])
+assert variant_site_dtype.itemsize == 24
 # walt_levels: the genome-wide summary of a pile-up (include/walt_amd.h, "methylation levels"); rows CpG, CHG, CHH,
 # unknown (METH_CONTEXTS) and CpG pairs
 level_row_dtype = np.dtype([("sites", "<u8"), ("covered", "<u8"), ("meth", "<u8"), ("unmeth", "<u8"), ("max_depth", "<u8"),
@@ -327,6 +331,16 @@ def lib(pattern=None):
                                              c.c_size_t, vp, vp, u32, u32, u32, vp, vp]
     L.walt_meth_pileup_batch_epi_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                     vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.walt_meth_evidence_batch.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, c.c_size_t]
+    L.walt_meth_evidence_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, c.c_size_t, vp]
+    L.walt_meth_pileup_batch_ev.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                            c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp]
+    L.walt_meth_pileup_batch_ev_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                   vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.walt_pileup_variants.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, c.POINTER(u64)]
+    L.walt_pileup_variants_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
+    L.walt_pileup_mask_variants.argtypes = [vp, vp, u32, u32, u32, u32, vp]
+    L.walt_pileup_mask_variants_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp]
     L.walt_index_set_option.argtypes = [vp, c.c_char_p, c.c_longlong]
     L.walt_index_get_option.argtypes = [vp, c.c_char_p, c.POINTER(c.c_longlong)]
     L.walt_makedb.argtypes = [c.c_char_p, c.c_char_p, ci]
@@ -433,27 +447,29 @@ def _rule_arg(rule):
     return rule
 
 
-def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None, epi=None):
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None, epi=None, ev=None):
     """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
-    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), epi = (handle,), each None when the caller
-    gave none.  The
+    stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), epi = (handle,), ev = (handle,),
+    each None when the caller gave none.  The
     narrowest form that takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a
     call with skip only.  Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
-    widest = "epi" if epi else "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    widest = "ev" if ev else "epi" if epi else "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
     if widest is None:
         name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
     else:  # (these three take a null pile-up, a null skip and a null excl)
         name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
         if widest != "skip":
             tail += excl or (None,)
-        if widest in ("mbias", "trim", "pairs", "epi"):
+        if widest in ("mbias", "trim", "pairs", "epi", "ev"):
             tail += mbias or (None, 0)
-        if widest in ("trim", "pairs", "epi"):
+        if widest in ("trim", "pairs", "epi", "ev"):
             tail += trim or (0, 0)
-        if widest in ("pairs", "epi"):
+        if widest in ("pairs", "epi", "ev"):
             tail += pairs or (None,)
-        if widest == "epi":
-            tail += epi
+        if widest in ("epi", "ev"):
+            tail += epi or (None,)
+        if widest == "ev":
+            tail += ev
     return getattr(L, name + ("_device" if device else "")), head, tail
 
 
@@ -544,6 +560,25 @@ def _keyword_only_epi(plain):
         named = dict(bound.arguments)
         del named["self"]
         return self._meth_batch(None, epi=epi, **named)
+
+    return call
+
+
+def _keyword_only_evidence(plain):
+    """Pileup.add_batch[_device] with one more, keyword-only argument evidence=, in the way _keyword_only_epi adds epi=: the
+    end of their parameter lists is pinned too (tests/test_epialleles_cpu.py), so inspect.signature goes on showing the
+    lists as they were.  The method "_" + plain's name takes the evidence object's handle in front of plain's parameters."""
+    signature = inspect.signature(plain)
+
+    @functools.wraps(plain)
+    def call(self, *args, evidence=None, **kw):
+        if evidence is None:
+            return plain(self, *args, **kw)
+        bound = signature.bind(self, *args, **kw)
+        bound.apply_defaults()
+        named = dict(bound.arguments)
+        del named["self"]
+        return getattr(self, "_" + plain.__name__)(evidence.handle, **named)
 
     return call
 
@@ -885,7 +920,7 @@ class Index:
 
     def _meth_batch(self, pile, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
                     stats=None, want_stats=True, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None,
-                    epi=None):
+                    epi=None, ev=None):
         """Index.meth_call_batch; pile: null, or the handle of a pile-up that takes the calls too; skip: null, or the
         records that are not counted (walt_meth_pileup_batch_skip, which takes a null pile-up); excl: null, or the read
         positions that get no call (walt_meth_pileup_batch_excl, which takes a null pile-up and a null skip)."""
@@ -913,7 +948,8 @@ class Index:
         form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
                                       excl is not None and (_ptr(excl_arr) if n else None,),
                                       mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3),
-                                      pairs=pairs is not None and (pairs.handle,), epi=epi is not None and (epi.handle,))
+                                      pairs=pairs is not None and (pairs.handle,), epi=epi is not None and (epi.handle,),
+                                      ev=ev is not None and (ev,))
         self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
                       conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
@@ -933,14 +969,14 @@ class Index:
         self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs, epi)
 
     def _meth_batch_device(self, pile, skip_alone, batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5=0,
-                           trim3=0, pairs=None, epi=None):
+                           trim3=0, pairs=None, epi=None, ev=None):
         """Index.meth_call_batch_device (pile null) and Pileup.add_batch_device.  batch: the C arguments from d_bases to
         d_stats; skip_alone: the form a call with d_skip only goes to (the index's: walt_meth_pileup_batch_excl_device, a
         pile-up's: walt_meth_pileup_batch_skip_device)."""
         form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
                                       d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
                                       skip_alone, _trim_arg(trim5, trim3), pairs is not None and (pairs.handle,),
-                                      epi is not None and (epi.handle,))
+                                      epi is not None and (epi.handle,), ev is not None and (ev,))
         self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
@@ -1037,23 +1073,99 @@ class Pileup:
         index._ck(self._L.walt_pileup_create(index._h, ctypes.byref(h)))
         self._h = h
 
+    @_keyword_only_evidence
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
                   want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, *, epi=None):
-        """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns."""
-        return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
-                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs, epi)
+        """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns.  evidence (keyword
+        only): another Pileup of the index that takes the batch's opposite-strand evidence (include/walt_amd.h,
+        "opposite-strand evidence": walt_meth_pileup_batch_ev; only when given)."""
+        return self._add_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats, pairs,
+                               skip, excl, mbias, mbias_table, trim5, trim3, epi=epi)
 
+    def _add_batch(self, ev, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats, pairs, skip, excl,
+                   mbias, mbias_table, trim5, trim3, epi):
+        """add_batch; ev: null, or the handle of the evidence object"""
+        return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
+                                       want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs, epi, ev)
+
+    @_keyword_only_evidence
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
                          skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None, *, epi=None):
         """Index.meth_call_batch_device with the pile-up as one more destination; asynchronous.  d_skip: one byte per
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
         MBias set whose table mbias_table takes the calls too (d_calls must be given); pairs: a CpgPairs table of the
-        index that takes them as well; epi: an Epialleles table of the index, likewise."""
+        index that takes them as well; epi: an Epialleles table of the index, likewise; evidence (keyword only): as in
+        add_batch (walt_meth_pileup_batch_ev_device)."""
+        self._add_batch_device(None, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
+                               d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3,
+                               pairs, epi=epi)
+
+    def _add_batch_device(self, ev, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
+                          d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs,
+                          epi):
+        """add_batch_device; ev: null, or the handle of the evidence object"""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
         self._index._meth_batch_device(self._h, "skip", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3,
-                                       pairs, epi)
+                                       pairs, epi, ev)
+
+    # -- opposite-strand evidence (include/walt_amd.h states the rules): this object holds the evidence ----------------
+    def add_evidence_batch(self, bases, offsets, records, conv="T", call_len=None, skip=None):
+        """The evidence kernel alone (walt_meth_evidence_batch): the batch as Index.meth_call_batch takes it; this object's
+        plane 0 counts the matches, plane 1 the other bases.  Nothing is returned."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        records, rec_ptr, rec_stride = _records_arg(records, n)
+        conv_arr, conv_ptr, conv_stride, conversion = _conv_arg(conv, n)
+        cl = None if call_len is None else np.ascontiguousarray(call_len, dtype=np.uint32)
+        if cl is not None and cl.size != n:
+            raise ValueError("call_len: one element per read")
+        skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
+        self._index._ck(self._L.walt_meth_evidence_batch(self._index._h, self._h, bases.ctypes.data, _ptr(offsets), n, rec_ptr,
+                                                         rec_stride, conv_ptr, conv_stride, conversion, _ptr(cl), skip_ptr,
+                                                         skip_stride))
+
+    def add_evidence_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
+                                  conversion="T", d_call_len=None, d_skip=None, skip_stride=1, stream=0):
+        """Device-pointer form (walt_meth_evidence_batch_device); asynchronous."""
+        self._index._ck(self._L.walt_meth_evidence_batch_device(self._index._h, self._h, d_bases, d_offsets, int(n), d_records,
+                                                                int(record_stride), d_conv, int(conv_stride), ord(conversion),
+                                                                d_call_len, d_skip, int(skip_stride), stream))
+
+    def variants(self, ev, pos_lo=0, pos_hi=None, min_depth=5, max_percent=50):
+        """The positions of [pos_lo, pos_hi) that the evidence object `ev` flags (walt_pileup_variants), ascending:
+        variant_site_dtype[n], meth / unmeth from this pile-up, match / other from ev."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        args = (self._h, ev.handle, int(pos_lo), int(pos_hi), int(min_depth), int(max_percent))
+        n = ctypes.c_uint64(0)
+        rc = self._L.walt_pileup_variants(*args, None, 0, ctypes.byref(n))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        out = np.zeros(n.value, dtype=variant_site_dtype)
+        if n.value:
+            self._index._ck(self._L.walt_pileup_variants(*args, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def variants_device(self, ev, pos_lo, pos_hi, min_depth, max_percent, d_out, cap, d_n_out, stream=0):
+        """Device-pointer form (walt_pileup_variants_device); asynchronous."""
+        self._index._ck(self._L.walt_pileup_variants_device(self._h, ev.handle, int(pos_lo), int(pos_hi), int(min_depth),
+                                                            int(max_percent), d_out, int(cap), d_n_out, stream))
+
+    def mask_variants(self, ev, pos_lo=0, pos_hi=None, min_depth=5, max_percent=50):
+        """Zeroes this pile-up's counters at the positions of [pos_lo, pos_hi) that `ev` flags (walt_pileup_mask_variants);
+        returns uint64[5]: judged, flagged, masked sites, methylated calls removed, unmethylated calls removed."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        out = np.zeros(5, dtype=np.uint64)
+        self._index._ck(self._L.walt_pileup_mask_variants(self._h, ev.handle, int(pos_lo), int(pos_hi), int(min_depth),
+                                                          int(max_percent), _ptr(out)))
+        return out
+
+    def mask_variants_device(self, ev, pos_lo, pos_hi, min_depth, max_percent, d_out, stream=0):
+        """Device-pointer form (walt_pileup_mask_variants_device): 40 bytes at d_out; asynchronous."""
+        self._index._ck(self._L.walt_pileup_mask_variants_device(self._h, ev.handle, int(pos_lo), int(pos_hi), int(min_depth),
+                                                                 int(max_percent), d_out, stream))
 
     def extract(self, pos_lo=0, pos_hi=None):
         """(sites meth_site_dtype[n] of the forward positions [pos_lo, pos_hi), ascending; offref uint64[2]: the

@@ -127,6 +127,12 @@ struct walt_pileup {
   unsigned long long* table = nullptr;
   uint64_t device_bytes = 0;
 };
+namespace walt {
+constexpr uint32_t kPileMaxBlocks = 65536;     // blocks of an extraction at most
+constexpr uint64_t kPileTableBytes = 1u << 20; // block offsets [kPileMaxBlocks + 1], the totals in the last words
+constexpr uint32_t kPileTotals = (uint32_t)(kPileTableBytes / 8) - 8;  // n_sites, off-reference meth, unmeth
+constexpr uint32_t kPileTile = 4096;           // positions per block the default grid aims at
+}  // namespace walt
 
 // Methylation bias by read position (mbias.hip): n_tables x kMbiasReplicas replica tables of 64-bit counters,
 // count[4][2][1024] each; a block of the bias kernel flushes into replica blockIdx % kMbiasReplicas of its table.
@@ -186,6 +192,27 @@ int mbias_launch(walt_mbias* mb, uint32_t table, const CallsBatch& b, hipStream_
 // cpgpairs.hip: the fold kernel of either table over the same batch on `stream` of the table's index's device
 int cpgpairs_launch(walt_cpgpairs* ap, const CallsBatch& b, hipStream_t stream);
 int epialleles_launch(walt_epialleles* ep, const CallsBatch& b, hipStream_t stream);
+
+// pileup.hip: k_pile_scan over n_blocks counts at the front of `table` (a pile-up's): the exclusive scan in place, the
+// total behind it, in table[kPileTotals] and, when given, at d_total; d_offref (when given): table[kPileTotals + 1 .. 2]
+int pile_scan_launch(unsigned long long* table, uint32_t n_blocks, unsigned long long* d_total, unsigned long long* d_offref,
+                     hipStream_t stream);
+
+// variants.hip: one batch of reads as the evidence kernel reads it (device arrays; the calling kernel's), and the kernel
+// on `stream` of ev's index's device
+struct EvBatch {
+  const void *bases, *offsets;
+  uint32_t n;
+  const void* records;
+  size_t rec_stride;
+  const void* conv;      // null: `conversion` for every read
+  size_t conv_stride;
+  int conversion;
+  const void* call_len;  // null: the whole read
+  const void* skip;      // null: none
+  size_t skip_stride;
+};
+int evidence_launch(walt_pileup* ev, const EvBatch& b, hipStream_t stream);
 
 // nonconv.hip: one batch of calls as the judging kernel reads it (device arrays; tally null: not wanted), the kernel on
 // `stream` of idx's device, what every form refuses of a rule and a filt array (empty: nothing), and the end of a host

@@ -826,5 +826,38 @@ inline uint64_t epiallele_row_total(const EpialleleRow& r) {
   return t;
 }
 
+
+// ---------------------------------------------------------------- <out>.variants, <out>.variantstats (bin/walt -MV)
+// The value of -MVD (lo 1, hi 1,000,000) or -MVP (lo 0, hi 99): a decimal integer, nothing in front of or behind its digits.
+constexpr uint32_t kMaxVariantDepth = 1000000;
+inline bool parse_variant_value(const std::string& text, uint32_t lo, uint32_t hi, uint32_t& out) {
+  if (text.empty() || text.size() > 7) return false;
+  uint32_t v = 0;
+  for (const char c : text) {
+    if (c < '0' || c > '9') return false;
+    v = v * 10 + (uint32_t)(c - '0');
+  }
+  if (v < lo || v > hi) return false;
+  out = v;
+  return true;
+}
+// One flagged position (include/walt_amd.h, "opposite-strand evidence") as a line, tab-separated:
+//   chrom  pos  strand  context  meth  unmeth  opp_match  opp_other
+// pos 0-based within the chromosome; the first six columns are those of <out>.methcounts.
+inline void put_variant_line(Sink& out, const std::string& chrom, uint32_t chrom_start, const walt_variant_site& s) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  out.put(chrom); out.ch('\t'); out.u32(s.pos - chrom_start); out.ch('\t'); out.ch((char)s.strand); out.ch('\t');
+  out.lit(ctx[s.context & 3]); out.ch('\t'); out.u32(s.meth); out.ch('\t'); out.u32(s.unmeth); out.ch('\t');
+  out.u32(s.match); out.ch('\t'); out.u32(s.other); out.ch('\n');
+}
+// One read file's block of <out>.variantstats: the five totals of walt_pileup_mask_variants and the rule.
+inline void put_variant_block(Sink& out, const uint64_t tot[5], uint32_t min_depth, uint32_t max_percent) {
+  char num[320];
+  snprintf(num, sizeof num, "judged: %llu\nflagged: %llu\nmasked sites: %llu\nmasked meth: %llu\nmasked unmeth: %llu\nrule\t%u\t%u\n",
+           (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)tot[2], (unsigned long long)tot[3],
+           (unsigned long long)tot[4], min_depth, max_percent);
+  out.lit(num);
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

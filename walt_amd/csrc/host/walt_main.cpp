@@ -60,8 +60,8 @@ struct Options {
   bool levels = false;  // -ML: genome-wide methylation levels of the pile-up (walt_pileup_levels): <out>.levels
   string regions_file;  // -MR: methylation levels per region of a BED file (walt_pileup_regions): <out>.regions
   bool regions() const { return !regions_file.empty(); }
-  bool piling() const { return methcounts || levels || regions(); }  // the run keeps pile-ups
-  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic || epialleles; }  // something takes the methylation calls
+  bool piling() const { return methcounts || levels || regions() || variants; }  // the run keeps pile-ups
+  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic || epialleles || variants; }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
@@ -69,6 +69,11 @@ struct Options {
   bool epialleles = false;  // -ME: four-CpG epiallele patterns per read (walt_meth_pileup_batch_epi): <out>.epialleles
   uint32_t epi_min = 1;     // -MEN: the fewest reads of a window that is written
   bool epi_min_given = false;
+  // -MV: opposite-strand evidence beside the pile-up (walt_meth_pileup_batch_ev); the flagged positions go to <out>.variants,
+  // the totals to <out>.variantstats, and their counters are zeroed before .methcounts, .levels and .regions are written
+  bool variants = false;
+  uint32_t variant_depth = 5, variant_percent = 50;  // -MVD, -MVP: min_depth and max_percent of the rule
+  bool variant_depth_given = false, variant_percent_given = false;
   // -I5 -I3 -I5R2 -I3R2: the first / last bases of a read that get no methylation call (walt_meth_pileup_batch_trim), of
   // the reads of -r or -1 ([0], [1]) and of the reads of -2 ([2], [3]); the user's order, also under -P and -RP
   uint32_t ignore[4] = {0, 0, 0, 0};
@@ -134,6 +139,19 @@ static Options parse(int argc, const char** argv) {
         die(a + " (epialleles) wants a number of reads from 1 to 1000000, not \"" + v + "\"");
       o.epi_min_given = true;
     }
+    else if (is_opt(a, "MV", "variants") || a == "--mask-variants") o.variants = true;  // extension: C>T variant sites kept out of the counts
+    else if (is_opt(a, "MVD", "variant-min-depth")) {  // extension: the fewest opposite-strand reads a position is judged by
+      const string v = val();
+      if (!hostio::parse_variant_value(v, 1, hostio::kMaxVariantDepth, o.variant_depth))
+        die(a + " (variant sites) wants a number of reads from 1 to 1000000, not \"" + v + "\"");
+      o.variant_depth_given = true;
+    }
+    else if (is_opt(a, "MVP", "variant-max-percent")) {  // extension: the percentage of other bases a position may show
+      const string v = val();
+      if (!hostio::parse_variant_value(v, 0, 99, o.variant_percent))
+        die(a + " (variant sites) wants a percentage from 0 to 99, not \"" + v + "\"");
+      o.variant_percent_given = true;
+    }
     else if (is_opt(a, "I5", "ignore") || is_opt(a, "I3", "ignore-3prime") || is_opt(a, "I5R2", "ignore-r2") ||
              is_opt(a, "I3R2", "ignore-3prime-r2")) {  // extension: read ends kept out of the methylation calls
       const int k = is_opt(a, "I5", "ignore") ? 0 : is_opt(a, "I3", "ignore-3prime") ? 1 : is_opt(a, "I5R2", "ignore-r2") ? 2 : 3;
@@ -183,17 +201,19 @@ static Options parse(int argc, const char** argv) {
   if (o.no_overlap && !o.se_csv.empty())
     die("-NO (no overlap) is about the two mates of a pair: it is paired-end only and cannot be combined with -r");
   if (o.no_overlap && !o.consumer())
-    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML, -MR, -MA) there is nothing for it to do");
+    die("-NO (no overlap) changes methylation calls only: without -M or -MC (or -MB, -ML, -MR, -MA, -ME, -MV) there is nothing for it to do");
   if ((o.ignore_given[0] || o.ignore_given[1] || o.ignore_given[2] || o.ignore_given[3]) && !o.consumer())
-    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB, -ML, -MR or -MA there is nothing for them to do");
+    die("-I5 / -I3 / -I5R2 / -I3R2 (ignored read ends) change methylation calls only: without -M, -MC, -MB, -ML, -MR, -MA, -ME or -MV there is nothing for them to do");
   if ((o.ignore_given[2] || o.ignore_given[3]) && !o.se_csv.empty())
     die("-I5R2 / -I3R2 (ignored read ends of mate 2) are about the reads of -2: they cannot be combined with -r (use -I5 / -I3)");
   if (o.filter_given[3] && !o.filter_given[2])
     die("-FM (the fewest non-CpG calls a read is judged by its percentage with) goes with -FP: without it there is nothing for it to do");
   if ((o.filtering() || o.filter_given[3]) && !o.consumer())
-    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML, -MR or -MA there is nothing for them to do");
+    die("-F / -FC / -FP / -FM (non-converted reads) change methylation calls only: without -M, -MC, -MB, -ML, -MR, -MA, -ME or -MV there is nothing for them to do");
   if (o.epi_min_given && !o.epialleles)
     die("-MEN (the fewest reads of a written window) goes with -ME: without it there is nothing for it to do");
+  if ((o.variant_depth_given || o.variant_percent_given) && !o.variants)
+    die("-MVD / -MVP (the rule that flags a variant site) go with -MV: without it there is nothing for them to do");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -295,7 +315,7 @@ struct SideFiles {  // the _ambiguous / _unmapped files of StatSingleReads (mapp
 
 // The files a run writes beside its main output, <out><suffix>: main truncates those whose option is on (walt.cpp:230-233
 // for the first), and the end of every read file appends its block to each.
-enum { kMapstats, kMethstats, kMethcounts, kLevels, kRegions, kMbias, kAllelic, kEpialleles, kDupstats, kFilterstats, kOutputs };
+enum { kMapstats, kMethstats, kMethcounts, kLevels, kRegions, kMbias, kAllelic, kEpialleles, kDupstats, kFilterstats, kVariants, kVariantstats, kOutputs };
 static const struct { bool (*on)(const Options&); const char* suffix; } kOutput[kOutputs] = {
     {[](const Options&) { return true; }, ".mapstats"},
     {[](const Options& o) { return o.meth; }, ".methstats"},
@@ -307,6 +327,8 @@ static const struct { bool (*on)(const Options&); const char* suffix; } kOutput[
     {[](const Options& o) { return o.epialleles; }, ".epialleles"},
     {[](const Options& o) { return o.dedup; }, ".dupstats"},
     {[](const Options& o) { return o.filtering(); }, ".filterstats"},
+    {[](const Options& o) { return o.variants; }, ".variants"},
+    {[](const Options& o) { return o.variants; }, ".variantstats"},
 };
 struct Append {  // one of them, open for appending
   OutFile f;
@@ -576,17 +598,62 @@ static void write_regions(const string& out_file, PileUps& ps) {
   Append(out_file, kRegions).write(out);
 }
 
-// the end of a read file: <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the
-// counters cleared
-static void end_of_file_pileups(const Options& o, const string& out_file, PileUps& ps, const GenomeInfo& g) {
+// ---------------------------------------------------------------- -MV: C>T variant sites kept out of the counts
+// Whether a position is flagged depends on all of its evidence: the other devices' counters and evidence are folded into
+// the first device's (fold_pileups, as -ML does), and everything that follows reads the first device alone.  The flagged
+// positions go to <out>.variants window by window, in genome order; then one masking pass, and its totals to
+// <out>.variantstats.
+static void write_variants(const Options& o, const string& out_file, walt_pileup* p, walt_pileup* ev, const GenomeInfo& g) {
+  const uint64_t genome_len = g.start.back();
+  const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+  vector<walt_variant_site> buf((size_t)window);
+  {
+    Append vf(out_file, kVariants);
+    uint32_t chr = 0;
+    Sink out;
+    for_each_window(genome_len, window, [&](uint32_t lo, uint32_t hi) {
+      uint64_t n = 0;
+      check(walt_pileup_variants(p, ev, lo, hi, o.variant_depth, o.variant_percent, buf.data(), window, &n));
+      out.clear();
+      for (uint64_t k = 0; k < n; ++k) {
+        while (buf[k].pos >= g.start[chr + 1]) ++chr;  // (ascending positions)
+        hostio::put_variant_line(out, g.name[chr], g.start[chr], buf[k]);
+      }
+      vf.write(out);
+    });
+  }
+  uint64_t tot[5] = {0, 0, 0, 0, 0};
+  check(walt_pileup_mask_variants(p, ev, 0, (uint32_t)genome_len, o.variant_depth, o.variant_percent, tot));
+  Sink block;
+  hostio::put_variant_block(block, tot, o.variant_depth, o.variant_percent);
+  Append(out_file, kVariantstats).write(block);
+  if (o.verbose) fwrite(block.p, 1, block.n, stderr);
+}
+
+// the end of a read file: under -MV the variant sites first (ev: the evidence, as many objects as pile-ups); then
+// <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the counters cleared
+static void end_of_file_pileups(const Options& o, const string& out_file, PileUps& ps, PileUps& ev, const GenomeInfo& g) {
+  bool folded = false;
+  if (o.variants) {
+    fold_pileups(ps, g.start.back());
+    fold_pileups(ev, g.start.back());
+    folded = true;
+    write_variants(o, out_file, ps.p[0], ev.p[0], g);
+  }
   if (o.methcounts) {
     SiteTable t = {{0, 0}};
-    write_window_table(t, ps, out_file, g, o.verbose);
+    if (folded) {  // the first device's counters hold every device's: a view of that one handle, which stays ps's
+      struct { vector<walt_pileup*> p; } first = {{ps.p[0]}};
+      write_window_table(t, first, out_file, g, o.verbose);
+    } else {
+      write_window_table(t, ps, out_file, g, o.verbose);
+    }
   }
-  if (o.levels || o.regions()) fold_pileups(ps, g.start.back());
+  if ((o.levels || o.regions()) && !folded) fold_pileups(ps, g.start.back());
   if (o.levels) write_levels(out_file, ps, g, o.verbose);
   if (o.regions()) write_regions(out_file, ps);
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
+  for (walt_pileup* q : ev.p) check(walt_pileup_clear(q));
 }
 
 // ---------------------------------------------------------------- -MB: methylation bias by read position
@@ -903,6 +970,7 @@ struct Consumers {
   bool calling = false;  // something takes the calls
   int n_slots = 1;
   PileUps pile;        // both mates into the device's pile-up
+  PileUps evid;        // -MV: both mates' opposite-strand evidence, a second pile-up per device
   MbiasSet mbs;
   PairTables pairs;    // both mates into the same table, each by itself
   WindowTables epi;    // likewise
@@ -927,6 +995,7 @@ struct Consumers {
     n_slots = slots;
     const size_t n = dev->size();
     if (o.piling()) pile.open(n, [&](size_t d, walt_pileup** h) { return walt_pileup_create(dev->idx[d], h); });
+    if (o.variants) evid.open(n, [&](size_t d, walt_pileup** h) { return walt_pileup_create(dev->idx[d], h); });
     if (o.mbias) mbs.open(n, [&](size_t d, walt_mbias** h) { return walt_mbias_create(dev->ids[d], (uint32_t)slots, h); });
     if (o.allelic) pairs.open(n, [&](size_t d, walt_cpgpairs** h) { return walt_cpgpairs_create(dev->idx[d], h); });
     if (o.epialleles) epi.open(n, [&](size_t d, walt_epialleles** h) { return walt_epialleles_create(dev->idx[d], h); });
@@ -976,16 +1045,16 @@ struct Consumers {
   // The calls of one slot of a share, on the device that mapped it.  With a rule (-F -FC -FP) the verdict pass: the calls
   // of the whole read up to its clip point, whatever -I5 / -I3 say, stay on the device and are judged there.  Without one
   // the pass that counts: one call takes whatever the options give it -- pile-up, skip bytes, interval words, bias set,
-  // pair table, window table -- each null without its option (all null: walt_meth_call_batch) and the ignored read ends
+  // pair table, window table, evidence -- each null without its option (all null: walt_meth_call_batch) and the ignored read ends
   // 0 without theirs, so that a run launches only the kernels its options ask for.
   int call_slot(size_t d, uint32_t n, const SlotView& v, const walt_nonconv_rule* rule) const {
     walt_index* idx = dev->idx[d];
     if (rule)
       return walt_meth_nonconv_batch(idx, v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride, v.conversion, v.clip,
                                      nullptr, rule, v.filt, v.stride, nullptr);
-    return walt_meth_pileup_batch_epi(idx, pile.of(d), v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride,
-                                      v.conversion, v.clip, v.calls, nullptr, v.stats, v.skip, v.stride, v.excl, mbs.of(d),
-                                      v.table, v.ignore5, v.ignore3, pairs.of(d), epi.of(d));
+    return walt_meth_pileup_batch_ev(idx, pile.of(d), v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride,
+                                     v.conversion, v.clip, v.calls, nullptr, v.stats, v.skip, v.stride, v.excl, mbs.of(d),
+                                     v.table, v.ignore5, v.ignore3, pairs.of(d), epi.of(d), evid.of(d));
   }
   // The end of a read file: <out>.methstats, the pile-up's files, <out>.mbias, .allelic, .epialleles, .dupstats and
   // .filterstats, each table cleared or closed behind its file.  slot_of_user_mate: null for single-end reads; for pairs
@@ -1011,7 +1080,7 @@ struct Consumers {
       Append(out_file, kMethstats).write(ms);
     }
     if (o.verbose && settings.n) fwrite(settings.p, 1, settings.n, stderr);
-    if (pile.on()) { end_of_file_pileups(o, out_file, pile, g); pile.close(); }
+    if (pile.on()) { end_of_file_pileups(o, out_file, pile, evid, g); pile.close(); evid.close(); }
     if (mbs.on()) {
       Sink ms;
       blocks(ms, [&](int slot) { mbias_block(mbs, ms, (uint32_t)slot); });
@@ -1557,7 +1626,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -MV -MVD <n> -MVP <p> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

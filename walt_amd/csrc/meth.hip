@@ -11,6 +11,7 @@
 
 #include "map_common.h"
 #include "meth_core.h"
+#include "pile_device.h"
 #include "pileup_core.h"
 
 namespace walt {
@@ -18,7 +19,6 @@ namespace walt {
 constexpr uint32_t kRefPadWords = 16;    // zero words behind a packed reference (meth_core.h meth_ref_ext reads three words)
 constexpr uint32_t kMethShards = 64;     // shards of the batch totals (one 128-byte line each, like map_common.h kStatShards)
 constexpr uint32_t kMethShardWords = 16;
-constexpr uint32_t kMethGroup = 8;       // lanes that share a read
 constexpr uint32_t kMethTotals = 9;      // walt_meth_stats: reads, meth[4], unmeth[4]
 constexpr uint64_t kMaxReadLenAny = 1024;  // walt_max_read_len() of the widest pattern: 16-bit counts hold a read's calls
 
@@ -165,30 +165,6 @@ struct MethArgs {
   const uint32_t* excl;        // null: none; else excl[r] = ex_lo | ex_hi << 16, read positions of record r that get no call
   uint32_t trim5, trim3;       // the ignored read ends of the batch (include/walt_amd.h, "ignored read ends"); read by the kTrim instances alone
 };
-
-// One call of the pile-up: a 32-bit add whose result nobody reads (no value comes back from the memory side).
-__device__ __forceinline__ void pile_add(uint32_t* __restrict__ plane, uint32_t f) {
-  (void)__hip_atomic_fetch_add(plane + f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// kPile = 2: the eight slices of a group's trip taken one after the other, lane t of the group adding the calls at
-// slice positions t and t + 8: the lanes of one instruction hold neighbouring positions (8 x 4 bytes of one plane),
-// where kPile = 1 has every lane walk its own slice (16 positions apart from its neighbour's).  All eight lanes of a
-// group arrive together (the trip count is the group's); q0 = the genome position of slice 0, position 0.
-__device__ __forceinline__ void pile_rows(uint32_t cm, uint32_t cu, long long q0, uint32_t sub, bool minus, uint32_t lo,
-                                          uint32_t hi, uint32_t* const plane[2]) {
-#pragma unroll
-  for (uint32_t s = 0; s < kMethGroup; ++s) {
-    const uint32_t bm = (uint32_t)__shfl((int)cm, (int)s, kMethGroup), bu = (uint32_t)__shfl((int)cu, (int)s, kMethGroup);
-    if (!(bm | bu)) continue;  // (the same for the whole group)
-#pragma unroll
-    for (uint32_t half = 0; half < 2; ++half) {
-      const uint32_t k = sub + 8u * half;
-      const uint32_t f = pile_forward(q0 + 16 * (long long)s + k, minus, lo, hi);
-      if ((bm >> (2u * k)) & 1u) pile_add(plane[0], f);
-      if ((bu >> (2u * k)) & 1u) pile_add(plane[1], f);
-    }
-  }
-}
 
 // Eight lanes per read, one 16-base slice per lane and trip.  Slices are cut at the 16-byte boundaries of the CALLS
 // array, so a whole slice is one aligned 16-byte store and the eight lanes of a group write 128 contiguous bytes; the
@@ -363,6 +339,8 @@ struct MethCall {
   uint32_t trim5 = 0, trim3 = 0;   // the ignored read ends (include/walt_amd.h, "ignored read ends"); both 0: none
   walt_cpgpairs* ap = nullptr;     // the pair table that takes the calls too (include/walt_amd.h, "adjacent CpG pairs")
   walt_epialleles* ep = nullptr;   // the window table that takes the calls too (include/walt_amd.h, "four-CpG epialleles")
+  walt_pileup* ev = nullptr;       // the object that takes the batch's opposite-strand evidence (include/walt_amd.h, "opposite-strand evidence")
+  bool ev_required = false;        // walt_meth_evidence_batch[_device]: it must be given
   // the rule that judges the calls too (include/walt_amd.h, "non-converted reads"; null: none), and where the verdicts go
   bool rule_form = false;          // walt_meth_nonconv_batch[_device]: a rule must be given
   const walt_nonconv_rule* rule = nullptr;
@@ -379,6 +357,9 @@ static int meth_call_check(const MethCall& c, bool has_calls) {
   if (!c.idx) return fail(WALT_EINVAL, who + ": bad argument");
   if (!c.pile && c.pile_required) return fail(WALT_EINVAL, who + ": bad argument (null pile-up)");
   if (c.pile && c.pile->idx != c.idx) return fail(WALT_EINVAL, who + ": the pile-up belongs to another index");
+  if (!c.ev && c.ev_required) return fail(WALT_EINVAL, who + ": bad argument (null evidence)");
+  if (c.ev && c.ev->idx != c.idx) return fail(WALT_EINVAL, who + ": the evidence belongs to another index");
+  if (c.ev && c.ev == c.pile) return fail(WALT_EINVAL, who + ": the evidence and the pile-up are one object");
   if (!c.idx->ref[0])
     return fail(WALT_EINVAL, who + ": the index holds no reference (open it with WALT_WITH_REFERENCE or "
                                    "call walt_index_enable_reference)");
@@ -422,10 +403,15 @@ static int meth_nonconv_check(const MethCall& c, bool has_calls) {
 
 // c: a checked call whose arrays are on the device.  The calling kernel and, with a bias set (which comes with calls),
 // the bias kernel from the calls just written: behind it on the same stream.  Likewise the pair kernel with a pair table,
-// the window kernel with an epiallele table and the judging kernel with a rule.
+// the window kernel with an epiallele table and the judging kernel with a rule.  With an evidence object the evidence
+// kernel runs right behind the calling kernel, over the same device arrays; alone when nothing else is wanted.
 static int meth_launch(const MethCall& c) {
   walt_index* const idx = c.idx;
-  if (c.n == 0 || (!c.calls && !c.counts && !c.stats && !c.pile)) return WALT_OK;
+  if (c.n == 0) return WALT_OK;
+  const EvBatch evidence = {c.bases, c.offsets, c.n, c.records, c.record_stride, c.conv, c.conv_stride, c.conversion,
+                            c.call_len, c.skip, c.skip_stride};
+  if (!c.calls && !c.counts && !c.stats && !c.pile)
+    return c.ev ? evidence_launch(c.ev, evidence, reinterpret_cast<hipStream_t>(c.stream)) : WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
   const hipStream_t stream = reinterpret_cast<hipStream_t>(c.stream);
   MethArgs a;
@@ -466,6 +452,8 @@ static int meth_launch(const MethCall& c) {
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
                        static_cast<unsigned long long*>(c.stats));
   WALT_HIP(hipGetLastError());
+  if (c.ev)
+    if (const int rc = evidence_launch(c.ev, evidence, stream)) return rc;
   if (c.mb)
     if (const int rc = mbias_launch(c.mb, c.table, {c.calls, c.offsets, c.n, c.records, c.record_stride, c.skip, c.skip_stride}, stream))
       return rc;
@@ -506,7 +494,7 @@ static int meth_batch_host(const MethCall& c) {
   const std::string bad = call_reads_refusal(c.who, offsets, n, static_cast<const uint8_t*>(c.conv), c.conv_stride);
   if (!bad.empty()) return fail(WALT_EINVAL, bad);
   walt_meth_stats* stats = static_cast<walt_meth_stats*>(c.stats);
-  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb && !c.rule && !c.ap && !c.ep) return WALT_OK;
+  if (!c.calls && !c.counts && !stats && !c.pile && !c.mb && !c.rule && !c.ap && !c.ep && !c.ev) return WALT_OK;
   WALT_HIP(hipSetDevice(c.idx->device));
   const uint64_t nbytes = offsets[n] - offsets[0];
   const std::vector<walt_best_match> rec = pack_strided<walt_best_match>(c.records, c.record_stride, n);
@@ -754,6 +742,55 @@ int walt_meth_pileup_batch_epi(walt_index* idx, walt_pileup* p, const char* base
                           .calls = calls, .counts = counts, .stats = stats,
                           .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
                           .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep});
+}
+
+// the epi forms plus an evidence object (include/walt_amd.h, "opposite-strand evidence"); ev null: the epi form
+int walt_meth_pileup_batch_ev_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                     const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                     int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                     const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                     uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                     walt_pileup* ev, void* stream) {
+  return meth_batch_device({.who = "walt_meth_pileup_batch_ev_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .mb = mb, .table = table,
+                            .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .ev = ev, .stream = stream});
+}
+
+int walt_meth_pileup_batch_ev(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                              const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                              int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                              walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                              walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap,
+                              walt_epialleles* ep, walt_pileup* ev) {
+  return meth_batch_host({.who = "walt_meth_pileup_batch_ev", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
+                          .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .ev = ev});
+}
+
+// the evidence kernel alone: the batch as the calling call takes it, nothing written but the evidence
+int walt_meth_evidence_batch_device(walt_index* idx, walt_pileup* ev, const void* d_bases, const void* d_offsets, uint32_t n,
+                                    const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                    int conversion, const void* d_call_len, const void* d_skip, size_t skip_stride,
+                                    void* stream) {
+  return meth_batch_device({.who = "walt_meth_evidence_batch_device", .idx = idx,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .skip = d_skip, .skip_stride = skip_stride, .ev = ev, .ev_required = true, .stream = stream});
+}
+
+int walt_meth_evidence_batch(walt_index* idx, walt_pileup* ev, const char* bases, const uint64_t* offsets, uint32_t n,
+                             const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                             int conversion, const uint32_t* call_len, const uint8_t* skip, size_t skip_stride) {
+  return meth_batch_host({.who = "walt_meth_evidence_batch", .idx = idx,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .skip = skip, .skip_stride = skip_stride, .ev = ev, .ev_required = true});
 }
 
 // the calling call plus the verdict on its calls (include/walt_amd.h, "non-converted reads"): no pile-up, no statistics

@@ -13,10 +13,6 @@
 namespace walt {
 
 constexpr uint32_t kRefPadWords = 16;          // as meth.hip: zero words behind a packed reference
-constexpr uint32_t kPileMaxBlocks = 65536;     // blocks of an extraction at most
-constexpr uint64_t kPileTableBytes = 1u << 20; // block offsets [kPileMaxBlocks + 1], the totals in the last words
-constexpr uint32_t kPileTotals = (uint32_t)(kPileTableBytes / 8) - 8;  // n_sites, off-reference meth, unmeth
-constexpr uint32_t kPileTile = 4096;           // positions per block the default grid aims at
 constexpr uint32_t kPileLevels = kPileTotals - 128;  // a summary's accumulator: walt_levels, kLevelWords words
 constexpr uint32_t kLevelCols = 32;            // LDS columns of a histogram bin (k_pile_levels)
 constexpr uint32_t kPileAddWindow = 1u << 22;  // positions walt_pileup_add stages on the device at a time
@@ -479,7 +475,19 @@ static int pile_range_check(const walt_pileup* p, const char* who, uint32_t pos_
 static int pile_count_launch(const PileArgs& a, uint32_t n_blocks, hipStream_t stream) {
   WALT_HIP(hipMemsetAsync(a.table + kPileTotals, 0, 3 * sizeof(unsigned long long), stream));
   hipLaunchKernelGGL(k_pile_count, dim3(n_blocks), dim3(kBlock), 0, stream, a);
-  hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, stream, a, n_blocks);
+  return pile_scan_launch(a.table, n_blocks, a.n_sites_out, a.offref_out, stream);
+}
+
+// the scan of n_blocks counts in `table`: the pile-up's extraction and the regions' sums here, the flagged positions in
+// variants.hip
+int pile_scan_launch(unsigned long long* table, uint32_t n_blocks, unsigned long long* d_total, unsigned long long* d_offref,
+                     hipStream_t stream) {
+  PileArgs scan;
+  memset(&scan, 0, sizeof scan);
+  scan.table = table;
+  scan.n_sites_out = d_total;
+  scan.offref_out = d_offref;
+  hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, stream, scan, n_blocks);
   WALT_HIP(hipGetLastError());
   return WALT_OK;
 }
@@ -643,15 +651,12 @@ static int pile_regions_launch(walt_pileup* p, const void* d_regions, uint32_t n
   a.prefix = static_cast<unsigned long long*>(d_work);
   a.table = p->table;
   a.out = static_cast<walt_region_levels*>(d_out);
-  PileArgs scan;
-  memset(&scan, 0, sizeof scan);
-  scan.table = p->table;
   const uint32_t n_sums = (n + kBlock - 1) / kBlock;
   const uint64_t want = idx->opt.pile_extract_blocks ? (uint64_t)idx->opt.pile_extract_blocks : (uint64_t)idx->n_cu * 8;
   const uint32_t n_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, kPileMaxBlocks));
   WALT_HIP(hipMemsetAsync(d_out, 0, (uint64_t)n * sizeof(walt_region_levels), stream));
   hipLaunchKernelGGL(k_region_sums, dim3(n_sums), dim3(kBlock), 0, stream, a);
-  hipLaunchKernelGGL(k_pile_scan, dim3(1), dim3(1024), 0, stream, scan, n_sums);
+  if (const int rc = pile_scan_launch(p->table, n_sums, nullptr, nullptr, stream)) return rc;
   hipLaunchKernelGGL(k_region_apply, dim3(n_sums), dim3(kBlock), 0, stream, a);
   hipLaunchKernelGGL(k_pile_regions, dim3(n_blocks), dim3(kBlock), 0, stream, a);
   WALT_HIP(hipGetLastError());

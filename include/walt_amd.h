@@ -1067,6 +1067,57 @@ int walt_pileup_mask_variants(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, 
 int walt_pileup_mask_variants_device(walt_pileup* p, walt_pileup* ev, uint32_t pos_lo, uint32_t pos_hi, uint32_t min_depth,
                                      uint32_t max_percent, void* d_out, void* stream);
 
+/* ---- minimum base quality: read bases below a quality floor get no call and give no evidence -----------------
+ *
+ * A sequencing error C<->T at a cytosine looks like a methylation state; the base qualities say where one is likely.
+ * (bin/walt also gives every non-ACGT read character a random base for mapping; such bases come with the lowest
+ * quality, and a floor is what keeps them out of the counts.)
+ *
+ * quals     one byte per base, at the same offsets and in the same order as `bases`: the read as sequenced.
+ * min_qual  uniform over the call, 0 to 127, compared with the raw byte, unsigned: the caller adds the Phred offset.
+ *           A larger value: WALT_EINVAL.  A byte of 128 or more passes every legal floor.
+ *
+ * Read position i of a record may get a call exactly when quals[off + i] >= min_qual AND every other rule allows it
+ * (call_len, the chromosome, excl, trim5 / trim3, the record rules): the masks compose by AND.  A masked position is
+ * treated exactly like one at or beyond call_len: the letter is '.', no count in walt_meth_counts, no total in
+ * walt_meth_stats, no add to the pile-up, nothing in the bias, pair and window tables (they are counted from the calls;
+ * the '.' breaks a run of neighbouring CpGs like any other), and `reads` is unchanged.
+ *   opposite-strand evidence  a masked position adds neither match nor other: this is about which base was read, so
+ *                             unlike trim5 / trim3 and excl it does act on the evidence.
+ *   non-conversion verdict    made from the masked calls: a base that was not read reliably is no evidence of a
+ *                             failed conversion.
+ *   overlap of a pair         the interval of walt_pair_overlap_batch[_trim] does not change: a position where mate 1 is
+ *                             masked and mate 2 is excluded is called by neither.
+ * quals == NULL requires min_qual == 0 (else WALT_EINVAL) and is the call as it was; quals != NULL with min_qual == 0
+ * gives what the call without qualities gives, byte for byte.
+ *
+ * walt_meth_pileup_batch_qual[_device] is walt_meth_pileup_batch_ev[_device] plus quals, min_qual: the pile-up, evidence,
+ * bias set, pair table, window table, skip, excl and calls may each be NULL; with only an evidence object it runs the
+ * evidence kernel alone.  walt_meth_nonconv_batch_qual[_device] is walt_meth_nonconv_batch[_device] plus the two.
+ * Every older entry point is the new one with quals = NULL.  Device forms: d_quals needs no alignment and may differ
+ * from d_bases and d_calls modulo 16; nothing is read in front of d_quals[0] or at or beyond d_quals[offsets[n]]. */
+int walt_meth_pileup_batch_qual(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride,
+                                int conversion, const uint32_t* call_len, char* calls, walt_meth_counts* counts,
+                                walt_meth_stats* stats, const uint8_t* skip, size_t skip_stride, const uint32_t* excl,
+                                walt_mbias* mb, uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap,
+                                walt_epialleles* ep, walt_pileup* ev, const uint8_t* quals, uint32_t min_qual);
+int walt_meth_pileup_batch_qual_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                       uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                       walt_pileup* ev, const void* d_quals, uint32_t min_qual, void* stream);
+int walt_meth_nonconv_batch_qual(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                                 size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                                 const uint32_t* call_len, char* calls, const walt_nonconv_rule* rule, uint8_t* filt,
+                                 size_t filt_stride, walt_nonconv_tally* tally, const uint8_t* quals, uint32_t min_qual);
+int walt_meth_nonconv_batch_qual_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                        int conversion, const void* d_call_len, void* d_calls, const walt_nonconv_rule* rule,
+                                        void* d_filt, size_t filt_stride, void* d_tally, const void* d_quals, uint32_t min_qual,
+                                        void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

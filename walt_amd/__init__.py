@@ -17,6 +17,7 @@ import ctypes
 import functools
 import inspect
 import os
+import threading
 
 import numpy as np
 
@@ -337,6 +338,14 @@ def lib(pattern=None):
                                             c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp]
     L.walt_meth_pileup_batch_ev_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
                                                    vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+    L.walt_meth_pileup_batch_qual.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, vp,
+                                              c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32]
+    L.walt_meth_pileup_batch_qual_device.argtypes = [vp, vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                     vp, c.c_size_t, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp]
+    L.walt_meth_nonconv_batch_qual.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp, c.c_size_t, vp,
+                                               vp, u32]
+    L.walt_meth_nonconv_batch_qual_device.argtypes = [vp, vp, vp, u32, vp, c.c_size_t, vp, c.c_size_t, ci, vp, vp, vp, vp,
+                                                      c.c_size_t, vp, vp, u32, vp]
     L.walt_pileup_variants.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, c.POINTER(u64)]
     L.walt_pileup_variants_device.argtypes = [vp, vp, u32, u32, u32, u32, vp, u64, vp, vp]
     L.walt_pileup_mask_variants.argtypes = [vp, vp, u32, u32, u32, u32, vp]
@@ -447,29 +456,32 @@ def _rule_arg(rule):
     return rule
 
 
-def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None, epi=None, ev=None):
+def _meth_form(L, device, pile, skip=None, excl=None, mbias=None, skip_alone="skip", trim=None, pairs=None, epi=None, ev=None,
+               qual=None):
     """The C form of a methylation call, by what the call is composed with: pile (a handle or None), skip = (address,
     stride), excl = (address,), mbias = (handle, table), trim = (trim5, trim3), pairs = (handle,), epi = (handle,), ev = (handle,),
-    each None when the caller gave none.  The
+    qual = (address, min_qual), each None when the caller gave none.  The
     narrowest form that takes them all is the one called -- its name is what a refusal shows; skip_alone: the form of a
     call with skip only.  Returns (the function, its arguments between the index and bases, its arguments behind stats)."""
-    widest = "ev" if ev else "epi" if epi else "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
+    widest = "qual" if qual else "ev" if ev else "epi" if epi else "pairs" if pairs else "trim" if trim else "mbias" if mbias else "excl" if excl else skip_alone if skip else None
     if widest is None:
         name, head, tail = ("walt_meth_pileup_batch", (pile,), ()) if pile is not None else ("walt_meth_call_batch", (), ())
     else:  # (these three take a null pile-up, a null skip and a null excl)
         name, head, tail = "walt_meth_pileup_batch_" + widest, (pile,), skip or (None, 1)
         if widest != "skip":
             tail += excl or (None,)
-        if widest in ("mbias", "trim", "pairs", "epi", "ev"):
+        if widest in ("mbias", "trim", "pairs", "epi", "ev", "qual"):
             tail += mbias or (None, 0)
-        if widest in ("trim", "pairs", "epi", "ev"):
+        if widest in ("trim", "pairs", "epi", "ev", "qual"):
             tail += trim or (0, 0)
-        if widest in ("pairs", "epi", "ev"):
+        if widest in ("pairs", "epi", "ev", "qual"):
             tail += pairs or (None,)
-        if widest in ("epi", "ev"):
+        if widest in ("epi", "ev", "qual"):
             tail += epi or (None,)
-        if widest == "ev":
-            tail += ev
+        if widest in ("ev", "qual"):
+            tail += ev or (None,)
+        if widest == "qual":
+            tail += qual
     return getattr(L, name + ("_device" if device else "")), head, tail
 
 
@@ -481,6 +493,13 @@ def pack_reads(seqs):
         offsets[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
     bases = np.frombuffer(b"".join(bs), dtype=np.uint8).copy() if bs else np.zeros(0, dtype=np.uint8)
     return bases, offsets
+
+
+def pack_quals(quals):
+    """list of str/bytes, the quality lines of the reads given to pack_reads in the same order -> quals uint8[total]: one
+    raw byte per base at the offsets pack_reads returns (include/walt_amd.h, "minimum base quality")."""
+    bs = [q.encode("latin-1") if isinstance(q, str) else bytes(q) for q in quals]
+    return np.frombuffer(b"".join(bs), dtype=np.uint8).copy() if bs else np.zeros(0, dtype=np.uint8)
 
 
 def se_rpbat_workspace_bytes(n, max_read_len):
@@ -581,6 +600,50 @@ def _keyword_only_evidence(plain):
         return getattr(self, "_" + plain.__name__)(evidence.handle, **named)
 
     return call
+
+
+# The base qualities of the call in progress on this thread, (quals, min_qual), or None: set by _keyword_only_quals, read
+# where the C call is composed (Index._qual_arg).
+_qual_call = threading.local()
+
+
+def _keyword_only_quals(plain):
+    """A methylation call with two more, keyword-only arguments quals=None, min_qual=0 (include/walt_amd.h, "minimum base
+    quality"), in the way _keyword_only_epi adds epi=: the parameter lists are pinned, so inspect.signature goes on
+    showing them as they were.  quals: a uint8 array with offsets[n] elements (walt_amd.pack_quals), or for a device form
+    the address of one; min_qual: 0 .. 127, compared with the raw byte.  Without the two the call is the old one."""
+
+    @functools.wraps(plain)
+    def call(self, *args, quals=None, min_qual=0, **kw):
+        if quals is None and not min_qual:
+            return plain(self, *args, **kw)
+        if getattr(_qual_call, "now", None) is not None:
+            raise RuntimeError("a methylation call with quals= inside another")
+        _qual_call.now = (quals, int(min_qual))
+        try:
+            return plain(self, *args, **kw)
+        finally:
+            _qual_call.now = None
+
+    return call
+
+
+def _qual_arg(total=None, first=0):
+    """The (address, min_qual) of the call in progress, or None without quals= / min_qual=.  total: a host form's
+    offsets[n] (the array's length is checked; first = offsets[0] .. total are the bytes read); None: a device form, quals an address.
+    -> (array to keep alive, (address or None, min_qual))"""
+    now = getattr(_qual_call, "now", None)
+    if now is None:
+        return None, None
+    quals, min_qual = now
+    if not 0 <= min_qual < 1 << 32:
+        raise ValueError("min_qual: 0 .. 127")
+    if quals is None or total is None:
+        return None, (quals, min_qual)
+    arr = np.ascontiguousarray(quals)
+    if arr.dtype != np.uint8 or arr.ndim != 1 or arr.shape[0] != total:
+        raise ValueError("quals: a 1-d uint8 array with offsets[n] = %d elements, one per base (walt_amd.pack_quals)" % total)
+    return arr, (arr.ctypes.data, min_qual)
 
 
 class Index:
@@ -779,6 +842,7 @@ class Index:
         """Builds the unconverted reference on an index that holds all four strands (walt_index_enable_reference)."""
         self._ck(self._L.walt_index_enable_reference(self._h))
 
+    @_keyword_only_quals
     @_keyword_only_epi
     def meth_call_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True,
                         stats=None, want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0):
@@ -795,7 +859,9 @@ class Index:
         positions and the last trim3 before the clip point get no call (include/walt_amd.h, "ignored read ends":
         walt_meth_pileup_batch_trim; only when one is non-zero).  pairs: a CpgPairs table of this index; the calls of the
         batch are folded into it under the same skip (walt_meth_pileup_batch_pairs; only when given; want_calls may be
-        False).  epi (keyword only): an Epialleles table of this index, likewise (walt_meth_pileup_batch_epi)."""
+        False).  epi (keyword only): an Epialleles table of this index, likewise (walt_meth_pileup_batch_epi).  quals,
+        min_qual (keyword only): one quality byte per base (walt_amd.pack_quals) and the floor below which a base gets no
+        call (include/walt_amd.h, "minimum base quality": walt_meth_pileup_batch_qual; only when given)."""
         return self._meth_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats,
                                 skip, excl, mbias, mbias_table, trim5, trim3, pairs)
 
@@ -837,9 +903,11 @@ class Index:
         """Device-pointer form of the pair rule; asynchronous."""
         self._ck(self._L.walt_nonconv_pairs_batch_device(self._h, d_pairs, int(n), d_filt, stream))
 
+    @_keyword_only_quals
     def meth_nonconv_batch(self, bases, offsets, records, rule, conv="T", call_len=None, want_calls=False, want_tally=True):
         """Calls and judges in one step (walt_meth_nonconv_batch): the arguments of meth_call_batch plus the rule.  Returns
-        (filt uint8[n], tally nonconv_tally_dtype[n] or None, calls uint8[total bases] or None)."""
+        (filt uint8[n], tally nonconv_tally_dtype[n] or None, calls uint8[total bases] or None).  quals, min_qual (keyword
+        only): as in meth_call_batch; the verdict is made from the masked calls (walt_meth_nonconv_batch_qual)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         rule = _rule_arg(rule)
@@ -854,19 +922,23 @@ class Index:
         calls_ptr = None if calls is None else calls.ctypes.data - int(offsets[0]) if n else calls.ctypes.data
         filt = np.zeros(n, dtype=np.uint8)
         tally = np.zeros(n, dtype=nonconv_tally_dtype) if want_tally else None
-        self._ck(self._L.walt_meth_nonconv_batch(self._h, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr,
-                                                 conv_stride, conversion, _ptr(cl), calls_ptr, _ptr(rule),
-                                                 _ptr(filt) if n else None, 1, _ptr(tally) if n else None))
+        quals_arr, qual = _qual_arg(int(offsets[n]) if n else 0)
+        form = self._L.walt_meth_nonconv_batch_qual if qual else self._L.walt_meth_nonconv_batch
+        self._ck(form(self._h, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride, conversion,
+                      _ptr(cl), calls_ptr, _ptr(rule), _ptr(filt) if n else None, 1, _ptr(tally) if n else None, *(qual or ())))
         return filt, tally, calls
 
+    @_keyword_only_quals
     def meth_nonconv_batch_device(self, d_bases, d_offsets, n, d_records, rule, d_calls, d_filt, record_stride=16, d_conv=None,
                                   conv_stride=1, conversion="T", d_call_len=None, filt_stride=1, d_tally=None, stream=0):
         """Device-pointer form: the calling kernel, then the judging kernel on the calls it wrote, on `stream`; d_calls
-        must be given."""
+        must be given.  quals, min_qual (keyword only): the address of the device array of quality bytes and the floor
+        (walt_meth_nonconv_batch_qual_device; only when given)."""
         rule = _rule_arg(rule)
-        self._ck(self._L.walt_meth_nonconv_batch_device(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv,
-                                                        int(conv_stride), ord(conversion), d_call_len, d_calls, _ptr(rule), d_filt,
-                                                        int(filt_stride), d_tally, stream))
+        _, qual = _qual_arg()  # (quals: the address of the device array)
+        form = self._L.walt_meth_nonconv_batch_qual_device if qual else self._L.walt_meth_nonconv_batch_device
+        self._ck(form(self._h, d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride),
+                      ord(conversion), d_call_len, d_calls, _ptr(rule), d_filt, int(filt_stride), d_tally, *(qual or ()), stream))
 
     # -- overlap of a pair (include/walt_amd.h states the rules) --------------------------------------------------
     def pair_overlap(self, pairs, offsets1, offsets2, call_len1=None, call_len2=None, trim1=(0, 0), trim2=(0, 0)):
@@ -945,15 +1017,17 @@ class Index:
             excl_arr = np.ascontiguousarray(excl, dtype=np.uint32)
             if excl_arr.ndim != 1 or excl_arr.shape[0] != n:
                 raise ValueError("excl: a 1-d uint32 array with one word per read")
+        quals_arr, qual = _qual_arg(int(offsets[n]) if n else 0)
         form, head, tail = _meth_form(self._L, False, pile, skip is not None and (skip_ptr, skip_stride),
                                       excl is not None and (_ptr(excl_arr) if n else None,),
                                       mbias is not None and (mbias.handle, int(mbias_table)), trim=_trim_arg(trim5, trim3),
                                       pairs=pairs is not None and (pairs.handle,), epi=epi is not None and (epi.handle,),
-                                      ev=ev is not None and (ev,))
+                                      ev=ev is not None and (ev,), qual=qual)
         self._ck(form(self._h, *head, bases.ctypes.data, _ptr(offsets), n, rec_ptr, rec_stride, conv_ptr, conv_stride,
                       conversion, _ptr(cl), calls_ptr, _ptr(counts), _ptr(stats), *tail))
         return calls, counts, stats
 
+    @_keyword_only_quals
     def meth_call_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                                conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0,
                                d_skip=None, skip_stride=1, d_excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, pairs=None,
@@ -963,7 +1037,8 @@ class Index:
         must be given); d_skip / d_excl: as in Pileup.add_batch_device (walt_meth_pileup_batch_excl_device with a null
         pile-up); trim5 / trim3: as in meth_call_batch (walt_meth_pileup_batch_trim_device); pairs: a CpgPairs table of
         this index that takes the calls too (walt_meth_pileup_batch_pairs_device; d_calls must be given); epi: an Epialleles
-        table of this index, likewise (walt_meth_pileup_batch_epi_device)."""
+        table of this index, likewise (walt_meth_pileup_batch_epi_device).  quals, min_qual (keyword only): the address of the
+        device array of quality bytes, one per base, and the floor (walt_meth_pileup_batch_qual_device; only when given)."""
         batch = (d_bases, d_offsets, int(n), d_records, int(record_stride), d_conv, int(conv_stride), ord(conversion), d_call_len,
                  d_calls, d_counts, d_stats)
         self._meth_batch_device(None, "excl", batch, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3, pairs, epi)
@@ -976,7 +1051,7 @@ class Index:
         form, head, tail = _meth_form(self._L, True, pile, d_skip is not None and (d_skip, int(skip_stride)),
                                       d_excl is not None and (d_excl,), mbias is not None and (mbias.handle, int(mbias_table)),
                                       skip_alone, _trim_arg(trim5, trim3), pairs is not None and (pairs.handle,),
-                                      epi is not None and (epi.handle,), ev is not None and (ev,))
+                                      epi is not None and (epi.handle,), ev is not None and (ev,), _qual_arg()[1])
         self._ck(form(self._h, *head, *batch, *tail, stream))
 
     # -- options: tuning values and test hooks (include/walt_amd.h; the library reads no environment on the mapping path)
@@ -1073,12 +1148,15 @@ class Pileup:
         index._ck(self._L.walt_pileup_create(index._h, ctypes.byref(h)))
         self._h = h
 
+    @_keyword_only_quals
     @_keyword_only_evidence
     def add_batch(self, bases, offsets, records, conv="T", call_len=None, want_calls=True, want_counts=True, stats=None,
                   want_stats=True, pairs=None, skip=None, excl=None, mbias=None, mbias_table=0, trim5=0, trim3=0, *, epi=None):
         """Index.meth_call_batch with the pile-up as one more destination: same arguments, same returns.  evidence (keyword
         only): another Pileup of the index that takes the batch's opposite-strand evidence (include/walt_amd.h,
-        "opposite-strand evidence": walt_meth_pileup_batch_ev; only when given)."""
+        "opposite-strand evidence": walt_meth_pileup_batch_ev; only when given).  quals, min_qual (keyword only): as in
+        Index.meth_call_batch (walt_meth_pileup_batch_qual; only when given); in add_batch_device quals is the address of
+        the device array."""
         return self._add_batch(None, bases, offsets, records, conv, call_len, want_calls, want_counts, stats, want_stats, pairs,
                                skip, excl, mbias, mbias_table, trim5, trim3, epi=epi)
 
@@ -1088,6 +1166,7 @@ class Pileup:
         return self._index._meth_batch(self._h, bases, offsets, records, conv, call_len, want_calls, want_counts, stats,
                                        want_stats, skip, excl, mbias, mbias_table, trim5, trim3, pairs, epi, ev)
 
+    @_keyword_only_quals
     @_keyword_only_evidence
     def add_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                          conversion="T", d_call_len=None, d_calls=None, d_counts=None, d_stats=None, stream=0, d_skip=None,
@@ -1096,7 +1175,8 @@ class Pileup:
         record (a non-zero byte: not counted); d_excl: one uint32 per record (Index.pair_overlap_device's); mbias: an
         MBias set whose table mbias_table takes the calls too (d_calls must be given); pairs: a CpgPairs table of the
         index that takes them as well; epi: an Epialleles table of the index, likewise; evidence (keyword only): as in
-        add_batch (walt_meth_pileup_batch_ev_device)."""
+        add_batch (walt_meth_pileup_batch_ev_device); quals, min_qual (keyword only): the address of the device array of quality
+        bytes, one per base, and the floor (walt_meth_pileup_batch_qual_device)."""
         self._add_batch_device(None, d_bases, d_offsets, n, d_records, record_stride, d_conv, conv_stride, conversion, d_call_len,
                                d_calls, d_counts, d_stats, stream, d_skip, skip_stride, d_excl, mbias, mbias_table, trim5, trim3,
                                pairs, epi=epi)
@@ -1111,9 +1191,11 @@ class Pileup:
                                        pairs, epi, ev)
 
     # -- opposite-strand evidence (include/walt_amd.h states the rules): this object holds the evidence ----------------
+    @_keyword_only_quals
     def add_evidence_batch(self, bases, offsets, records, conv="T", call_len=None, skip=None):
         """The evidence kernel alone (walt_meth_evidence_batch): the batch as Index.meth_call_batch takes it; this object's
-        plane 0 counts the matches, plane 1 the other bases.  Nothing is returned."""
+        plane 0 counts the matches, plane 1 the other bases.  Nothing is returned.  quals, min_qual (keyword only): a base
+        below the floor adds to neither plane (walt_meth_pileup_batch_qual with this object as its only destination)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
@@ -1123,13 +1205,29 @@ class Pileup:
         if cl is not None and cl.size != n:
             raise ValueError("call_len: one element per read")
         skip_arr, skip_ptr, skip_stride = _skip_arg(skip, n)
+        quals_arr, qual = _qual_arg(int(offsets[n]) if n else 0)
+        if qual:
+            self._index._ck(self._L.walt_meth_pileup_batch_qual(self._index._h, None, bases.ctypes.data, _ptr(offsets), n, rec_ptr,
+                                                                rec_stride, conv_ptr, conv_stride, conversion, _ptr(cl), None, None,
+                                                                None, skip_ptr, skip_stride, None, None, 0, 0, 0, None, None,
+                                                                self._h, *qual))
+            return
         self._index._ck(self._L.walt_meth_evidence_batch(self._index._h, self._h, bases.ctypes.data, _ptr(offsets), n, rec_ptr,
                                                          rec_stride, conv_ptr, conv_stride, conversion, _ptr(cl), skip_ptr,
                                                          skip_stride))
 
+    @_keyword_only_quals
     def add_evidence_batch_device(self, d_bases, d_offsets, n, d_records, record_stride=16, d_conv=None, conv_stride=1,
                                   conversion="T", d_call_len=None, d_skip=None, skip_stride=1, stream=0):
-        """Device-pointer form (walt_meth_evidence_batch_device); asynchronous."""
+        """Device-pointer form (walt_meth_evidence_batch_device); asynchronous.  quals, min_qual (keyword only): the address
+        of the device array of quality bytes and the floor (walt_meth_pileup_batch_qual_device)."""
+        _, qual = _qual_arg()
+        if qual:
+            self._index._ck(self._L.walt_meth_pileup_batch_qual_device(self._index._h, None, d_bases, d_offsets, int(n), d_records,
+                                                                       int(record_stride), d_conv, int(conv_stride), ord(conversion),
+                                                                       d_call_len, None, None, None, d_skip, int(skip_stride), None,
+                                                                       None, 0, 0, 0, None, None, self._h, *qual, stream))
+            return
         self._index._ck(self._L.walt_meth_evidence_batch_device(self._index._h, self._h, d_bases, d_offsets, int(n), d_records,
                                                                 int(record_stride), d_conv, int(conv_stride), ord(conversion),
                                                                 d_call_len, d_skip, int(skip_stride), stream))

@@ -211,6 +211,8 @@ struct EvBatch {
   const void* call_len;  // null: the whole read
   const void* skip;      // null: none
   size_t skip_stride;
+  const void* quals = nullptr;  // null: none; else one byte per base (include/walt_amd.h, "minimum base quality")
+  uint32_t min_qual = 0;
 };
 int evidence_launch(walt_pileup* ev, const EvBatch& b, hipStream_t stream);
 

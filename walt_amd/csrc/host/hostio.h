@@ -151,7 +151,10 @@ struct Batch {
   std::vector<uint64_t> name_v, score_v, seq_v;  // (offset << 16) | length
   char* bases = nullptr;                 // sanitised sequences, packed; pinned host memory
   uint64_t* offsets = nullptr;           // n + 1
-  size_t bases_cap = 0, off_cap = 0;
+  // -MQ only: the quality bytes of the sequences as the file has them, packed at the offsets of `bases`; pinned host
+  // memory (include/walt_amd.h, "minimum base quality").  Null without -MQ: no allocation, no copy.
+  char* quals = nullptr;
+  size_t bases_cap = 0, off_cap = 0, quals_cap = 0;
   Batch() {}
   Batch(const Batch&) = delete;
   Batch& operator=(const Batch&) = delete;
@@ -160,8 +163,9 @@ struct Batch {
   // the last batch is formatted and written, walt_main.cpp)
   void release() {
     HOSTIO_FREE(bases); HOSTIO_FREE(offsets);
-    bases = nullptr; offsets = nullptr;
-    bases_cap = off_cap = 0;
+    if (quals) HOSTIO_FREE(quals);
+    bases = nullptr; offsets = nullptr; quals = nullptr;
+    bases_cap = off_cap = quals_cap = 0;
     n = 0;
   }
   static uint64_t pack(size_t off, size_t len) { return ((uint64_t)off << 16) | (uint64_t)len; }
@@ -183,6 +187,14 @@ struct Batch {
       bases = nullptr;
       bases_cap = bytes + bytes / 8 + 4096;
       if (HOSTIO_ALLOC(bases_cap, (void**)&bases) != 0) throw std::runtime_error(HOSTIO_ALLOC_ERROR());
+    }
+  }
+  void reserve_quals(size_t bytes) {
+    if (quals_cap < bytes + 16) {
+      if (quals) HOSTIO_FREE(quals);
+      quals = nullptr;
+      quals_cap = bytes + bytes / 8 + 4096;
+      if (HOSTIO_ALLOC(quals_cap, (void**)&quals) != 0) throw std::runtime_error(HOSTIO_ALLOC_ERROR());
     }
   }
 };
@@ -244,6 +256,7 @@ inline double now_s() {
 }
 
 struct FastqReader {
+  bool want_quals = false;  // -MQ: every batch gets its packed quality buffer (Batch::quals)
   double t_scan = 0, t_views = 0, t_alloc = 0, t_copy = 0, t_rng = 0;  // -v breakdown
   std::string path;
   const char* data = nullptr;
@@ -417,9 +430,11 @@ struct FastqReader {
     for (int t = 0; t < T; ++t) part[t + 1] += part[t];
     double tm = now_s();
     bt.reserve_bases(part[T]);
+    if (want_quals) bt.reserve_quals(part[T]);
     t_alloc += now_s() - tm;
     tm = now_s();
     std::vector<std::vector<uint64_t>> fix(T);
+    std::vector<uint32_t> bad_qual(T, ~0u);  // -MQ: per thread, its first read whose quality line has another length
 #pragma omp parallel for schedule(static, 1) num_threads(T)
     for (int t = 0; t < T; ++t) {
       uint64_t o = part[t];
@@ -435,9 +450,21 @@ struct FastqReader {
           dst[i] = c;
           if (!is_acgt(c)) fix[t].push_back(o + i);
         }
+        // the qualities stay where they are, also behind a clip point: a clipped base is an 'N' with the quality it had
+        if (want_quals) {
+          if ((uint32_t)(bt.score_v[j] & 0xFFFF) == len) memcpy(bt.quals + o, bt.base + (bt.score_v[j] >> 16), len);
+          else if (bad_qual[t] == ~0u) bad_qual[t] = j;
+        }
         o += len;
       }
     }
+    for (int t = 0; t < T; ++t)
+      if (bad_qual[t] != ~0u) {
+        const View name = bt.name(bad_qual[t]);
+        throw std::runtime_error(path + ": read " + std::string(name.p, name.len) + ": the quality line has " +
+                                 std::to_string(bt.score_v[bad_qual[t]] & 0xFFFF) + " characters, the sequence " +
+                                 std::to_string(bt.seq_v[bad_qual[t]] & 0xFFFF) + " (-MQ reads a quality per base)");
+      }
     bt.offsets[n] = part[T];
     t_copy += now_s() - tm;
     tm = now_s();
@@ -663,6 +690,36 @@ inline bool parse_ignore_value(const std::string& text, uint32_t& out) {
 inline void put_ignore_line(Sink& out, const uint32_t* v, int n) {
   out.lit("ignore");
   for (int k = 0; k < n; ++k) { out.ch('\t'); out.u32(v[k]); }
+  out.ch('\n');
+}
+
+// ---------------------------------------------------------------- minimum base quality (bin/walt -MQ -MQO)
+// The value of -MQ: a Phred quality from 1 to 93 (the printable range above '!'), a decimal integer, nothing in front of
+// or behind its digits.  The value of -MQO: the FASTQ's Phred offset, 33 or 64.  quality_floor: what the library compares
+// the raw bytes with (include/walt_amd.h, "minimum base quality"), or false when it would exceed 127.
+static const uint32_t kMaxMinQual = 93;
+inline bool parse_min_qual(const std::string& text, uint32_t& out) {
+  uint32_t v = 0;
+  if (!parse_ignore_value(text, v) || v < 1 || v > kMaxMinQual) return false;
+  out = v;
+  return true;
+}
+inline bool parse_qual_offset(const std::string& text, uint32_t& out) {
+  uint32_t v = 0;
+  if (!parse_ignore_value(text, v) || (v != 33 && v != 64)) return false;
+  out = v;
+  return true;
+}
+inline bool quality_floor(uint32_t min_qual, uint32_t offset, uint32_t& out) {
+  out = min_qual + offset;
+  return out <= 127;
+}
+// The settings line that ends a read file's part of <out>.methstats under -MQ, behind the overlap and ignore lines:
+//   minqual <TAB> n <TAB> offset
+inline void put_minqual_line(Sink& out, uint32_t min_qual, uint32_t offset) {
+  out.lit("minqual");
+  out.ch('\t'); out.u32(min_qual);
+  out.ch('\t'); out.u32(offset);
   out.ch('\n');
 }
 

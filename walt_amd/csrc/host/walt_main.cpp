@@ -74,6 +74,11 @@ struct Options {
   bool variants = false;
   uint32_t variant_depth = 5, variant_percent = 50;  // -MVD, -MVP: min_depth and max_percent of the rule
   bool variant_depth_given = false, variant_percent_given = false;
+  // -MQ, -MQO: a read base whose Phred quality is below min_qual gets no methylation call and gives no opposite-strand
+  // evidence (walt_meth_pileup_batch_qual, walt_meth_nonconv_batch_qual); qual_offset: the FASTQ's Phred offset.  0: no floor
+  uint32_t min_qual = 0, qual_offset = 33;
+  bool qual_offset_given = false;
+  uint32_t qual_floor() const { return min_qual ? min_qual + qual_offset : 0u; }  // what the raw bytes are compared with
   // -I5 -I3 -I5R2 -I3R2: the first / last bases of a read that get no methylation call (walt_meth_pileup_batch_trim), of
   // the reads of -r or -1 ([0], [1]) and of the reads of -2 ([2], [3]); the user's order, also under -P and -RP
   uint32_t ignore[4] = {0, 0, 0, 0};
@@ -152,6 +157,17 @@ static Options parse(int argc, const char** argv) {
         die(a + " (variant sites) wants a percentage from 0 to 99, not \"" + v + "\"");
       o.variant_percent_given = true;
     }
+    else if (is_opt(a, "MQ", "min-qual") || a == "--min-base-quality") {  // extension: a quality floor under the methylation calls
+      const string v = val();
+      if (!hostio::parse_min_qual(v, o.min_qual))
+        die(a + " (minimum base quality) wants a Phred quality from 1 to 93, not \"" + v + "\"");
+    }
+    else if (is_opt(a, "MQO", "qual-offset") || a == "--quality-offset") {  // extension: the FASTQ's Phred offset
+      const string v = val();
+      if (!hostio::parse_qual_offset(v, o.qual_offset))
+        die(a + " (the FASTQ's Phred offset) wants 33 or 64, not \"" + v + "\"");
+      o.qual_offset_given = true;
+    }
     else if (is_opt(a, "I5", "ignore") || is_opt(a, "I3", "ignore-3prime") || is_opt(a, "I5R2", "ignore-r2") ||
              is_opt(a, "I3R2", "ignore-3prime-r2")) {  // extension: read ends kept out of the methylation calls
       const int k = is_opt(a, "I5", "ignore") ? 0 : is_opt(a, "I3", "ignore-3prime") ? 1 : is_opt(a, "I5R2", "ignore-r2") ? 2 : 3;
@@ -214,6 +230,14 @@ static Options parse(int argc, const char** argv) {
     die("-MEN (the fewest reads of a written window) goes with -ME: without it there is nothing for it to do");
   if ((o.variant_depth_given || o.variant_percent_given) && !o.variants)
     die("-MVD / -MVP (the rule that flags a variant site) go with -MV: without it there is nothing for them to do");
+  if (o.qual_offset_given && !o.min_qual)
+    die("-MQO (the FASTQ's Phred offset) goes with -MQ: without it there is nothing for it to do");
+  if (o.min_qual && !o.consumer())
+    die("-MQ (minimum base quality) changes methylation calls only: without -M, -MC, -MB, -ML, -MR, -MA, -ME or -MV there is nothing for it to do");
+  uint32_t floor = 0;
+  if (o.min_qual && !hostio::quality_floor(o.min_qual, o.qual_offset, floor))
+    die("-MQ " + std::to_string(o.min_qual) + " with -MQO " + std::to_string(o.qual_offset) + ": a quality byte of " +
+        std::to_string(floor) + " does not exist (the sum must not exceed 127)");
   if (o.filter_given[2] && !o.filter_given[3]) o.filter[3] = 5;  // (Bismark's --minimum_count)
   if (o.pbat && !o.se_csv.empty()) o.ag = true;  // single-end PBAT reads are A-rich: same as -A
   return o;
@@ -963,6 +987,8 @@ struct SlotView {
   const uint32_t* excl;  // -NO: the interval words (the user's mate 2 only)
   uint32_t table;        // -MB
   uint32_t ignore5, ignore3;
+  const uint8_t* quals;  // -MQ: the batch's quality bytes, at the offsets of its bases; else null
+  uint32_t min_qual;     // the floor the raw bytes are compared with; 0 without -MQ
 };
 
 struct Consumers {
@@ -1040,6 +1066,8 @@ struct Consumers {
     v.excl = nullptr;
     v.table = (uint32_t)k;
     v.ignore5 = ignore[0]; v.ignore3 = ignore[1];
+    v.quals = o.min_qual ? reinterpret_cast<const uint8_t*>(b.quals) : nullptr;
+    v.min_qual = o.qual_floor();
     return v;
   }
   // The calls of one slot of a share, on the device that mapped it.  With a rule (-F -FC -FP) the verdict pass: the calls
@@ -1049,12 +1077,13 @@ struct Consumers {
   // 0 without theirs, so that a run launches only the kernels its options ask for.
   int call_slot(size_t d, uint32_t n, const SlotView& v, const walt_nonconv_rule* rule) const {
     walt_index* idx = dev->idx[d];
+    // (quals null, without -MQ: each of the two is the older entry point, walt_meth_nonconv_batch and walt_meth_pileup_batch_ev)
     if (rule)
-      return walt_meth_nonconv_batch(idx, v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride, v.conversion, v.clip,
-                                     nullptr, rule, v.filt, v.stride, nullptr);
-    return walt_meth_pileup_batch_ev(idx, pile.of(d), v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride,
-                                     v.conversion, v.clip, v.calls, nullptr, v.stats, v.skip, v.stride, v.excl, mbs.of(d),
-                                     v.table, v.ignore5, v.ignore3, pairs.of(d), epi.of(d), evid.of(d));
+      return walt_meth_nonconv_batch_qual(idx, v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride, v.conversion, v.clip,
+                                          nullptr, rule, v.filt, v.stride, nullptr, v.quals, v.min_qual);
+    return walt_meth_pileup_batch_qual(idx, pile.of(d), v.bases, v.offsets, n, v.rec, v.rec_stride, v.conv, v.stride,
+                                       v.conversion, v.clip, v.calls, nullptr, v.stats, v.skip, v.stride, v.excl, mbs.of(d),
+                                       v.table, v.ignore5, v.ignore3, pairs.of(d), epi.of(d), evid.of(d), v.quals, v.min_qual);
   }
   // The end of a read file: <out>.methstats, the pile-up's files, <out>.mbias, .allelic, .epialleles, .dupstats and
   // .filterstats, each table cleared or closed behind its file.  slot_of_user_mate: null for single-end reads; for pairs
@@ -1073,6 +1102,7 @@ struct Consumers {
       settings.lit(overlap);
     }
     if (o.ignoring()) hostio::put_ignore_line(settings, o.ignore, 2 * n_slots);
+    if (o.min_qual) hostio::put_minqual_line(settings, o.min_qual, o.qual_offset);
     if (o.meth) {
       Sink ms;
       blocks(ms, [&](int slot) { put_meth_block(ms, meth_total[slot]); });
@@ -1146,6 +1176,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
   double t_open_reads = 0;
   first.start([&]() {
     const double t_o0 = now_s();
+    rd.want_quals = o.min_qual != 0;
     rd.open(reads_file, std::max(1, T / 2));
     t_open_reads = now_s() - t_o0;
     rd.load(o.batch_size, o.adaptor, bt[0]);
@@ -1419,6 +1450,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   GenomeInfo g = genome_of(dev.idx[0]);
   if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
   hostio::FastqReader rd[2];
+  rd[0].want_quals = rd[1].want_quals = o.min_qual != 0;
   rd[0].open(f1, T);
   rd[1].open(f2, T);
   const AdaptorPair ap = split_adaptor_option(o.adaptor);
@@ -1626,7 +1658,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -MV -MVD <n> -MVP <p> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -MV -MVD <n> -MVP <p> -MQ <n> -MQO <b> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);

@@ -164,6 +164,8 @@ struct MethArgs {
   uint64_t skip_stride;
   const uint32_t* excl;        // null: none; else excl[r] = ex_lo | ex_hi << 16, read positions of record r that get no call
   uint32_t trim5, trim3;       // the ignored read ends of the batch (include/walt_amd.h, "ignored read ends"); read by the kTrim instances alone
+  const uint8_t* quals;        // one byte per base at the offsets of `bases` (include/walt_amd.h, "minimum base quality"); read by the kQual instances alone
+  uint32_t min_qual;           // 0 .. 127
 };
 
 // Eight lanes per read, one 16-base slice per lane and trip.  Slices are cut at the 16-byte boundaries of the CALLS
@@ -180,7 +182,12 @@ struct MethArgs {
 // bound comes off `limit`, the 5' bound is the lower end of every slice's range; a slice wholly outside them returns
 // inside meth_read_slice before it loads anything (all eight lanes of a group still take every trip: pile_rows).
 // Instances of their own for the same reason as kExcl: a call without bounds runs the code it always ran.
-template <int kPile, bool kExcl, bool kTrim>
+// kQual: the batch comes with base qualities (a.quals, a.min_qual): every slice loads its 16 quality bytes beside its read
+// bytes and the positions below the floor leave its flags (meth_read_slice_q).  Instances of their own once more: a call
+// without qualities launches the kernels it always launched.  There are three of them, not twelve: a quality instance
+// carries the interval word and the bounds unconditionally (kExcl and kTrim both set, a.excl tested for null per record,
+// bounds of 0 without -I): DESIGN.md section 27 has the register figures the choice rests on.
+template <int kPile, bool kExcl, bool kTrim, bool kQual = false>
 __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
   __shared__ uint32_t s_start[kLdsChroms + 1];
   __shared__ unsigned long long s_red[kBlock / 64][kMethTotals];
@@ -211,13 +218,14 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     uint32_t c_lo = 0, c_hi = 0;
     if (mapped) chrom_bounds(s_start, a.start_index, tab, pos, c_lo, c_hi);
     // the other mate of the pair calls these read positions (include/walt_amd.h, "overlap of a pair"); 0: none
-    const uint32_t ex = kExcl ? a.excl[r] : 0u;
+    const uint32_t ex = !kExcl || (kQual && !a.excl) ? 0u : a.excl[r];
     const uint32_t ex_lo = ex & 0xFFFFu, ex_hi = ex >> 16;
     const uint32_t ga = cv == 'A' ? 1u : 0u;
     const uint32_t* __restrict__ ref = a.ref[strand == '-' ? 1 : 0];
     unsigned long long meth = 0, unmeth = 0;
     if (kPile == 2 && end > off && (mapped || a.calls)) {  // as below, every lane of the group taking every trip
       const uint8_t* rb = a.bases + off;
+      const uint8_t* qb = kQual ? a.quals + off : nullptr;
       uint8_t* cb = a.calls ? a.calls + off : nullptr;
       const int head = (int)((a.calls ? (uintptr_t)cb : (uintptr_t)rb) & 15u);
       for (uint64_t done = 0; done < end - off; done += 1u << 30) {
@@ -228,8 +236,9 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
           uint32_t cm = 0, cu = 0;
           if (i0 < total) {
             uint32_t out[4];
-            meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                            batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5);
+            meth_read_slice_q<kQual>(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                                     batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5,
+                                     kQual ? qb + done : nullptr, a.min_qual);
             if (cb) meth_store_slice(cb + done, total, i0, out);
           }
           if (counted) pile_rows(cm, cu, (long long)pos + base, sub, strand == '-', c_lo, c_hi, a.pile);
@@ -238,6 +247,7 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
     } else if (end > off && (mapped || a.calls)) {
       // (bytes of calls to write: the read's own; a read longer than any pattern allows is written in pieces of 2^30)
       const uint8_t* rb = a.bases + off;
+      const uint8_t* qb = kQual ? a.quals + off : nullptr;
       uint8_t* cb = a.calls ? a.calls + off : nullptr;
       // slice grid: by the calls array's address (by the bases' when no calls are wanted)
       const int head = (int)((a.calls ? (uintptr_t)cb : (uintptr_t)rb) & 15u);
@@ -246,8 +256,9 @@ __device__ __forceinline__ void meth_call_body(const MethArgs& a) {
         const int h = done ? 0 : head;
         for (int i0 = -h + 16 * (int)sub; i0 < total; i0 += 16 * (int)kMethGroup) {
           uint32_t out[4], cm, cu;
-          meth_read_slice(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
-                          batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5);
+          meth_read_slice_q<kQual>(rb + done, total, limit, mapped && !done, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off + done,
+                                   batch_bytes - off - done, out, meth, unmeth, cm, cu, ex_lo, ex_hi, trim5,
+                                   kQual ? qb + done : nullptr, a.min_qual);
           if (kPile == 1 && counted)  // (flags are set only where done == 0: slice position k is genome position pos + i0 + k)
             pile_slice(cm, cu, (long long)pos + i0, strand == '-', c_lo, c_hi,
                        [&](uint32_t f, bool m) { pile_add(a.pile[m ? 0 : 1], f); });
@@ -302,6 +313,9 @@ __global__ __launch_bounds__(kBlock) void k_meth_pile_rows_trim(const MethArgs a
 __global__ __launch_bounds__(kBlock) void k_meth_call_excl_trim(const MethArgs a) { meth_call_body<0, true, true>(a); }
 __global__ __launch_bounds__(kBlock) void k_meth_pile_excl_trim(const MethArgs a) { meth_call_body<1, true, true>(a); }
 __global__ __launch_bounds__(kBlock) void k_meth_pile_rows_excl_trim(const MethArgs a) { meth_call_body<2, true, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_call_qual(const MethArgs a) { meth_call_body<0, true, true, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_qual(const MethArgs a) { meth_call_body<1, true, true, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_meth_pile_rows_qual(const MethArgs a) { meth_call_body<2, true, true, true>(a); }
 
 // folds the shards into walt_meth_stats (accumulating) and clears them
 __global__ void k_meth_reduce(unsigned long long* __restrict__ shards, unsigned long long* __restrict__ stats) {
@@ -341,6 +355,8 @@ struct MethCall {
   walt_epialleles* ep = nullptr;   // the window table that takes the calls too (include/walt_amd.h, "four-CpG epialleles")
   walt_pileup* ev = nullptr;       // the object that takes the batch's opposite-strand evidence (include/walt_amd.h, "opposite-strand evidence")
   bool ev_required = false;        // walt_meth_evidence_batch[_device]: it must be given
+  const void* quals = nullptr;     // one byte per base (include/walt_amd.h, "minimum base quality"); null: the call as it was
+  uint32_t min_qual = 0;
   // the rule that judges the calls too (include/walt_amd.h, "non-converted reads"; null: none), and where the verdicts go
   bool rule_form = false;          // walt_meth_nonconv_batch[_device]: a rule must be given
   const walt_nonconv_rule* rule = nullptr;
@@ -363,6 +379,10 @@ static int meth_call_check(const MethCall& c, bool has_calls) {
   if (!c.idx->ref[0])
     return fail(WALT_EINVAL, who + ": the index holds no reference (open it with WALT_WITH_REFERENCE or "
                                    "call walt_index_enable_reference)");
+  if (c.min_qual > 127u)
+    return fail(WALT_EINVAL, who + ": min_qual " + std::to_string(c.min_qual) + " (a quality byte is compared with 0 to 127)");
+  if (!c.quals && c.min_qual)
+    return fail(WALT_EINVAL, who + ": min_qual " + std::to_string(c.min_qual) + " without quals");
   std::string bad = record_stride_refusal(c.record_stride);
   if (bad.empty()) bad = conv_refusal(c.conv, c.conv_stride, c.conversion);
   if (!bad.empty()) return fail(WALT_EINVAL, who + ": " + bad);
@@ -409,7 +429,7 @@ static int meth_launch(const MethCall& c) {
   walt_index* const idx = c.idx;
   if (c.n == 0) return WALT_OK;
   const EvBatch evidence = {c.bases, c.offsets, c.n, c.records, c.record_stride, c.conv, c.conv_stride, c.conversion,
-                            c.call_len, c.skip, c.skip_stride};
+                            c.call_len, c.skip, c.skip_stride, c.quals, c.min_qual};
   if (!c.calls && !c.counts && !c.stats && !c.pile)
     return c.ev ? evidence_launch(c.ev, evidence, reinterpret_cast<hipStream_t>(c.stream)) : WALT_OK;
   WALT_HIP(hipSetDevice(idx->device));
@@ -439,6 +459,8 @@ static int meth_launch(const MethCall& c) {
   a.excl = static_cast<const uint32_t*>(c.excl);
   a.trim5 = c.trim5;
   a.trim3 = c.trim3;
+  a.quals = static_cast<const uint8_t*>(c.quals);
+  a.min_qual = c.min_qual;
   const uint64_t want = ((uint64_t)c.n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
   // [bounds][excl][no pile-up, pile-up, pile_rows]: a call whose bounds are both 0 runs the instances it always ran
@@ -446,7 +468,10 @@ static int meth_launch(const MethCall& c) {
       {{k_meth_call, k_meth_pile, k_meth_pile_rows}, {k_meth_call_excl, k_meth_pile_excl, k_meth_pile_rows_excl}},
       {{k_meth_call_trim, k_meth_pile_trim, k_meth_pile_rows_trim},
        {k_meth_call_excl_trim, k_meth_pile_excl_trim, k_meth_pile_rows_excl_trim}}};
-  const auto kernel = kernels[c.trim5 || c.trim3][a.excl != nullptr][!c.pile ? 0 : idx->opt.pile_rows ? 2 : 1];
+  // with qualities: the three instances that carry the interval word and the bounds whether given or not
+  static void (*const qual_kernels[3])(const MethArgs) = {k_meth_call_qual, k_meth_pile_qual, k_meth_pile_rows_qual};
+  const int by_pile = !c.pile ? 0 : idx->opt.pile_rows ? 2 : 1;
+  const auto kernel = a.quals ? qual_kernels[by_pile] : kernels[c.trim5 || c.trim3][a.excl != nullptr][by_pile];
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   if (c.stats)
     hipLaunchKernelGGL(k_meth_reduce, dim3(1), dim3(kMethTotals), 0, stream, idx->meth_shards,
@@ -503,7 +528,7 @@ static int meth_batch_host(const MethCall& c) {
   std::vector<uint64_t> rel;
   const uint64_t* off = rebase_offsets(offsets, n, rel);
   const char* const what = "methylation calls";
-  DeviceTemp d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl, d_filt, d_tally;
+  DeviceTemp d_bases, d_off, d_rec, d_conv, d_len, d_calls, d_counts, d_stats, d_skip, d_excl, d_filt, d_tally, d_quals;
   if ((rc = d_bases.put(bases + offsets[0], nbytes, what, 16)) || (rc = d_off.put(off, ((size_t)n + 1) * 8, what)) ||
       (rc = d_rec.put(rec.data(), (size_t)n * 16, what)))
     return rc;
@@ -511,6 +536,7 @@ static int meth_batch_host(const MethCall& c) {
   if (c.call_len && (rc = d_len.put(c.call_len, (size_t)n * 4, what))) return rc;
   if (c.skip && (rc = d_skip.put(sk.data(), n, what))) return rc;
   if (c.excl && (rc = d_excl.put(c.excl, (size_t)n * 4, what))) return rc;
+  if (c.quals && (rc = d_quals.put(static_cast<const char*>(c.quals) + offsets[0], nbytes, what))) return rc;
   if ((c.calls || c.mb || c.rule || c.ap || c.ep) && (rc = d_calls.get(nbytes + 16, what))) return rc;  // (the bias, pair and window tables are counted, the verdict made, from the device copy)
   if (c.rule && (rc = d_filt.get(n, what))) return rc;
   if (c.rule && c.tally && (rc = d_tally.get((size_t)n * sizeof(walt_nonconv_tally), what))) return rc;
@@ -523,6 +549,7 @@ static int meth_batch_host(const MethCall& c) {
   d.calls = d_calls.p; d.counts = d_counts.p; d.stats = d_stats.p;
   d.skip = d_skip.p; d.skip_stride = 1; d.excl = d_excl.p; d.stream = nullptr;
   d.filt = d_filt.p; d.filt_stride = 1; d.tally = d_tally.p;
+  d.quals = d_quals.p;
   if ((rc = meth_launch(d))) return rc;
   WALT_HIP(hipStreamSynchronize(nullptr));
   if (c.calls && nbytes) WALT_HIP(hipMemcpy(static_cast<char*>(c.calls) + offsets[0], d_calls.p, nbytes, hipMemcpyDeviceToHost));
@@ -773,6 +800,37 @@ int walt_meth_pileup_batch_ev(walt_index* idx, walt_pileup* p, const char* bases
                           .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .ev = ev});
 }
 
+// the ev forms plus the base qualities and their floor (include/walt_amd.h, "minimum base quality"); quals null: the ev form
+int walt_meth_pileup_batch_qual_device(walt_index* idx, walt_pileup* p, const void* d_bases, const void* d_offsets, uint32_t n,
+                                       const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                       int conversion, const void* d_call_len, void* d_calls, void* d_counts, void* d_stats,
+                                       const void* d_skip, size_t skip_stride, const void* d_excl, walt_mbias* mb,
+                                       uint32_t table, uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep,
+                                       walt_pileup* ev, const void* d_quals, uint32_t min_qual, void* stream) {
+  return meth_batch_device({.who = "walt_meth_pileup_batch_qual_device", .idx = idx, .pile = p,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .counts = d_counts, .stats = d_stats,
+                            .skip = d_skip, .skip_stride = skip_stride, .excl = d_excl, .mb = mb, .table = table,
+                            .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .ev = ev,
+                            .quals = d_quals, .min_qual = min_qual, .stream = stream});
+}
+
+int walt_meth_pileup_batch_qual(walt_index* idx, walt_pileup* p, const char* bases, const uint64_t* offsets, uint32_t n,
+                                const void* records, size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                                const uint32_t* call_len, char* calls, walt_meth_counts* counts, walt_meth_stats* stats,
+                                const uint8_t* skip, size_t skip_stride, const uint32_t* excl, walt_mbias* mb, uint32_t table,
+                                uint32_t trim5, uint32_t trim3, walt_cpgpairs* ap, walt_epialleles* ep, walt_pileup* ev,
+                                const uint8_t* quals, uint32_t min_qual) {
+  return meth_batch_host({.who = "walt_meth_pileup_batch_qual", .idx = idx, .pile = p,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .counts = counts, .stats = stats,
+                          .skip = skip, .skip_stride = skip_stride, .excl = excl, .mb = mb, .table = table,
+                          .trim5 = trim5, .trim3 = trim3, .ap = ap, .ep = ep, .ev = ev,
+                          .quals = quals, .min_qual = min_qual});
+}
+
 // the evidence kernel alone: the batch as the calling call takes it, nothing written but the evidence
 int walt_meth_evidence_batch_device(walt_index* idx, walt_pileup* ev, const void* d_bases, const void* d_offsets, uint32_t n,
                                     const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
@@ -814,6 +872,31 @@ int walt_meth_nonconv_batch(walt_index* idx, const char* bases, const uint64_t* 
                           .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
                           .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
                           .calls = calls,
+                          .rule_form = true, .rule = rule, .filt = filt, .filt_stride = filt_stride, .tally = tally});
+}
+
+// walt_meth_nonconv_batch[_device] plus the base qualities and their floor: the verdict is made from the masked calls
+int walt_meth_nonconv_batch_qual_device(walt_index* idx, const void* d_bases, const void* d_offsets, uint32_t n,
+                                        const void* d_records, size_t record_stride, const void* d_conv, size_t conv_stride,
+                                        int conversion, const void* d_call_len, void* d_calls, const walt_nonconv_rule* rule,
+                                        void* d_filt, size_t filt_stride, void* d_tally, const void* d_quals, uint32_t min_qual,
+                                        void* stream) {
+  return meth_batch_device({.who = "walt_meth_nonconv_batch_qual_device", .idx = idx,
+                            .bases = d_bases, .offsets = d_offsets, .n = n, .records = d_records, .record_stride = record_stride,
+                            .conv = d_conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = d_call_len,
+                            .calls = d_calls, .quals = d_quals, .min_qual = min_qual,
+                            .rule_form = true, .rule = rule, .filt = d_filt, .filt_stride = filt_stride, .tally = d_tally,
+                            .stream = stream});
+}
+
+int walt_meth_nonconv_batch_qual(walt_index* idx, const char* bases, const uint64_t* offsets, uint32_t n, const void* records,
+                                 size_t record_stride, const uint8_t* conv, size_t conv_stride, int conversion,
+                                 const uint32_t* call_len, char* calls, const walt_nonconv_rule* rule, uint8_t* filt,
+                                 size_t filt_stride, walt_nonconv_tally* tally, const uint8_t* quals, uint32_t min_qual) {
+  return meth_batch_host({.who = "walt_meth_nonconv_batch_qual", .idx = idx,
+                          .bases = bases, .offsets = offsets, .n = n, .records = records, .record_stride = record_stride,
+                          .conv = conv, .conv_stride = conv_stride, .conversion = conversion, .call_len = call_len,
+                          .calls = calls, .quals = quals, .min_qual = min_qual,
                           .rule_form = true, .rule = rule, .filt = filt, .filt_stride = filt_stride, .tally = tally});
 }
 

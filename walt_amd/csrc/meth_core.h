@@ -39,6 +39,23 @@ WALT_HD uint32_t meth_spread(uint32_t m) {
   return (m | (m << 6) | (m << 12) | (m << 18)) & 0x01010101u;
 }
 
+// 16 quality bytes (four per word, first base in the low byte) -> the field mask of the positions whose byte is at
+// least min_qual (include/walt_amd.h, "minimum base quality"); min_qual <= 127, the compare unsigned.  Per word: the low
+// seven bits of every byte with bit 7 set on top, minus min_qual in every byte, keeps bit 7 exactly where the seven
+// bits reach min_qual (0x80 + b - t lies in 1 .. 0xFF: no borrow leaves a byte); a byte of 128 or more passes by its own
+// bit 7, which the subtraction alone would get wrong.  The four bit 7s then move to bits 0, 2, 4, 6 of the word's byte.
+WALT_HD uint32_t meth_qual_mask(const uint32_t qd[4], uint32_t min_qual) {
+  const uint32_t t4 = min_qual * 0x01010101u;
+  uint32_t r = 0;
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t w = qd[j];
+    const uint32_t ge = ((((w & 0x7F7F7F7Fu) | 0x80808080u) - t4) | w) & 0x80808080u;
+    const uint32_t x = ge >> 7;
+    r |= ((x | (x >> 6) | (x >> 12) | (x >> 18)) & 0x55u) << (8 * j);
+  }
+  return r;
+}
+
 struct MethSlice {
   uint32_t out[4];             // the 16 call characters
   unsigned long long meth, unmeth;  // four 16-bit counts each: CpG, CHG, CHH, unknown (the layout of walt_meth_counts)
@@ -144,30 +161,49 @@ WALT_HD unsigned long long meth_ref_ext(const uint32_t* ref, long long qs, uint3
 // per-cytosine pile-up adds (pileup_core.h).  [ex_lo, ex_hi): the read positions excluded from calling (meth_slice_flags).
 // trim5: the read positions below it get no call; `limit` comes with the 3' bound taken off (meth_trim_limit).  A slice
 // that lies wholly below trim5 returns like one at or beyond `limit`: before any read byte or reference word is loaded.
-WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
-                             uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
-                             unsigned long long before, unsigned long long after, uint32_t out[4],
-                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
-                             uint32_t ex_lo, uint32_t ex_hi, uint32_t trim5) {
+// kQual: qb = the read's first quality byte, at the offsets of rb in an array as long as the bases (include/walt_amd.h,
+// "minimum base quality"); the slice's quality bytes are loaded beside its read bytes, in the same way and under the
+// same bounds, and the positions below min_qual leave `call`; a slice they leave nothing of returns before the reference
+// words are loaded.  Without kQual neither argument is read and the code is what it was.
+template <bool kQual>
+WALT_HD void meth_read_slice_q(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
+                               uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
+                               unsigned long long before, unsigned long long after, uint32_t out[4],
+                               unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
+                               uint32_t ex_lo, uint32_t ex_hi, uint32_t trim5, const uint8_t* qb, uint32_t min_qual) {
   out[0] = out[1] = out[2] = out[3] = 0x2E2E2E2Eu;
   cm = cu = 0;
   if (!mapped || i0 >= (int)limit || (long long)i0 + 16 <= (long long)trim5) return;
   uint32_t call, v1, v2;
   meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2, ex_lo, ex_hi, trim5);
   if (!call) return;
-  uint32_t rd[4] = {0, 0, 0, 0};
+  uint32_t rd[4] = {0, 0, 0, 0}, qd[4] = {0, 0, 0, 0};
   if ((i0 >= 0 || (unsigned long long)(-i0) <= before) && (unsigned long long)(i0 + 16) <= after) {
     __builtin_memcpy(rd, rb + i0, 16);  // (bases and calls may differ in alignment)
+    if (kQual) __builtin_memcpy(qd, qb + i0, 16);  // (and so may the qualities)
   } else {
     for (int k = 0; k < 16; ++k) {
       const int i = i0 + k;
       if (i >= 0 && i < total) rd[k >> 2] |= (uint32_t)rb[i] << (8 * (k & 3));
+      if (kQual && i >= 0 && i < total) qd[k >> 2] |= (uint32_t)qb[i] << (8 * (k & 3));
     }
+  }
+  if (kQual) {
+    call &= meth_qual_mask(qd, min_qual);
+    if (!call) return;
   }
   const MethSlice s = meth_slice(rd, meth_ref_ext(ref, (long long)pos + i0 - 2, ref_last), ga, call, v1, v2);
   out[0] = s.out[0]; out[1] = s.out[1]; out[2] = s.out[2]; out[3] = s.out[3];
   meth += s.meth; unmeth += s.unmeth;
   cm = s.cm; cu = s.cu;
+}
+WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,
+                             uint32_t hi, uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0,
+                             unsigned long long before, unsigned long long after, uint32_t out[4],
+                             unsigned long long& meth, unsigned long long& unmeth, uint32_t& cm, uint32_t& cu,
+                             uint32_t ex_lo, uint32_t ex_hi, uint32_t trim5) {
+  meth_read_slice_q<false>(rb, total, limit, mapped, pos, lo, hi, ga, ref, ref_last, i0, before, after, out, meth, unmeth, cm, cu,
+                           ex_lo, ex_hi, trim5, nullptr, 0u);
 }
 // the form without ignored ends, and the forms without an excluded interval: what they always gave
 WALT_HD void meth_read_slice(const uint8_t* rb, int total, uint32_t limit, bool mapped, uint32_t pos, uint32_t lo,

@@ -39,12 +39,16 @@ struct EvArgs {
   const uint8_t* skip;         // null: none
   uint64_t skip_stride;
   uint32_t* plane[2];          // match, other
+  const uint8_t* quals;        // one byte per base (include/walt_amd.h, "minimum base quality"); read by the kQual instances alone
+  uint32_t min_qual;
 };
 
 // Eight lanes per read, one 16-base slice per lane and trip, cut at the 16-byte boundaries of the bases array (a whole
 // slice is one aligned 16-byte load); the first and last slice of a read are partial.  Nothing is written but the
 // counters.  kRows: pile_rows instead of pile_slice (option pile_rows); every lane of a group then takes every trip.
-template <bool kRows>
+// kQual: the batch comes with base qualities; a base below a.min_qual adds to neither counter (ev_read_slice_q).
+// Instances of their own, as in meth.hip: a call without qualities launches the kernel it always launched.
+template <bool kRows, bool kQual = false>
 __device__ __forceinline__ void evidence_body(const EvArgs& a) {
   __shared__ uint32_t s_start[kLdsChroms + 1];
   const ChromTab tab = chrom_tab_of(a.n_chrom);
@@ -71,17 +75,19 @@ __device__ __forceinline__ void evidence_body(const EvArgs& a) {
     const bool minus = strand == '-';
     const uint32_t* __restrict__ ref = a.ref[minus ? 1 : 0];
     const uint8_t* rb = a.bases + off;
+    const uint8_t* qb = kQual ? a.quals + off : nullptr;
     const int head = (int)((uintptr_t)rb & 15u);
     if (kRows) {
       for (int base = -head; base < (int)limit; base += 16 * (int)kMethGroup) {
         const int i0 = base + 16 * (int)sub;
         EvSlice s = {0u, 0u};
-        if (i0 < (int)limit) s = ev_read_slice(rb, (int)len, limit, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off, batch_bytes - off);
+        if (i0 < (int)limit)
+          s = ev_read_slice_q<kQual>(rb, (int)len, limit, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off, batch_bytes - off, qb, a.min_qual);
         pile_rows(s.match, s.other, (long long)pos + base, sub, minus, c_lo, c_hi, a.plane);
       }
     } else {
       for (int i0 = -head + 16 * (int)sub; i0 < (int)limit; i0 += 16 * (int)kMethGroup) {
-        const EvSlice s = ev_read_slice(rb, (int)len, limit, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off, batch_bytes - off);
+        const EvSlice s = ev_read_slice_q<kQual>(rb, (int)len, limit, pos, c_lo, c_hi, ga, ref, a.ref_last, i0, off, batch_bytes - off, qb, a.min_qual);
         pile_slice(s.match, s.other, (long long)pos + i0, minus, c_lo, c_hi,
                    [&](uint32_t f, bool m) { pile_add(a.plane[m ? 0 : 1], f); });
       }
@@ -91,6 +97,8 @@ __device__ __forceinline__ void evidence_body(const EvArgs& a) {
 
 __global__ __launch_bounds__(kBlock) void k_evidence(const EvArgs a) { evidence_body<false>(a); }
 __global__ __launch_bounds__(kBlock) void k_evidence_rows(const EvArgs a) { evidence_body<true>(a); }
+__global__ __launch_bounds__(kBlock) void k_evidence_qual(const EvArgs a) { evidence_body<false, true>(a); }
+__global__ __launch_bounds__(kBlock) void k_evidence_rows_qual(const EvArgs a) { evidence_body<true, true>(a); }
 
 int evidence_launch(walt_pileup* ev, const EvBatch& b, hipStream_t stream) {
   if (b.n == 0) return WALT_OK;
@@ -114,9 +122,13 @@ int evidence_launch(walt_pileup* ev, const EvBatch& b, hipStream_t stream) {
   a.skip = static_cast<const uint8_t*>(b.skip);
   a.skip_stride = b.skip_stride;
   a.plane[0] = ev->plane[0]; a.plane[1] = ev->plane[1];
+  a.quals = static_cast<const uint8_t*>(b.quals);
+  a.min_qual = b.min_qual;
   const uint64_t want = ((uint64_t)b.n + kBlock / kMethGroup - 1) / (kBlock / kMethGroup);
   const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)idx->n_cu * 8);
-  hipLaunchKernelGGL(idx->opt.pile_rows ? k_evidence_rows : k_evidence, dim3(grid), dim3(kBlock), 0, stream, a);
+  const auto kernel = a.quals ? (idx->opt.pile_rows ? k_evidence_rows_qual : k_evidence_qual)
+                              : (idx->opt.pile_rows ? k_evidence_rows : k_evidence);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, stream, a);
   WALT_HIP(hipGetLastError());
   return WALT_OK;
 }

@@ -36,23 +36,37 @@ WALT_HD bool ev_record_counts(uint32_t times, uint32_t skip, uint32_t pos, uint3
 // bytes of the batch's bases in front of rb and from rb on; a partial slice is loaded whole where its 16 bytes lie
 // inside the batch and byte by byte at the batch's two ends, exactly as meth_read_slice loads it.  A slice with no
 // position to judge returns before it loads anything.
-WALT_HD EvSlice ev_read_slice(const uint8_t* rb, int total, uint32_t limit, uint32_t pos, uint32_t lo, uint32_t hi,
-                              uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0, unsigned long long before,
-                              unsigned long long after) {
+// kQual: qb = the read's first quality byte, min_qual the floor (include/walt_amd.h, "minimum base quality"): loaded and
+// applied as meth_read_slice_q does, a position below the floor adds to neither counter.
+template <bool kQual>
+WALT_HD EvSlice ev_read_slice_q(const uint8_t* rb, int total, uint32_t limit, uint32_t pos, uint32_t lo, uint32_t hi,
+                                uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0, unsigned long long before,
+                                unsigned long long after, const uint8_t* qb, uint32_t min_qual) {
   if (i0 >= (int)limit) return {0u, 0u};
   uint32_t call, v1, v2;
   meth_slice_flags(i0, pos, lo, hi, limit, ga, call, v1, v2);
   if (!call) return {0u, 0u};
-  uint32_t rd[4] = {0, 0, 0, 0};
+  uint32_t rd[4] = {0, 0, 0, 0}, qd[4] = {0, 0, 0, 0};
   if ((i0 >= 0 || (unsigned long long)(-i0) <= before) && (unsigned long long)(i0 + 16) <= after) {
     __builtin_memcpy(rd, rb + i0, 16);
+    if (kQual) __builtin_memcpy(qd, qb + i0, 16);  // (the qualities' alignment may differ from the bases')
   } else {
     for (int k = 0; k < 16; ++k) {
       const int i = i0 + k;
       if (i >= 0 && i < total) rd[k >> 2] |= (uint32_t)rb[i] << (8 * (k & 3));
+      if (kQual && i >= 0 && i < total) qd[k >> 2] |= (uint32_t)qb[i] << (8 * (k & 3));
     }
   }
+  if (kQual) {
+    call &= meth_qual_mask(qd, min_qual);
+    if (!call) return {0u, 0u};
+  }
   return ev_slice(rd, meth_ref_ext(ref, (long long)pos + i0 - 2, ref_last), ga, call);
+}
+WALT_HD EvSlice ev_read_slice(const uint8_t* rb, int total, uint32_t limit, uint32_t pos, uint32_t lo, uint32_t hi,
+                              uint32_t ga, const uint32_t* ref, uint32_t ref_last, int i0, unsigned long long before,
+                              unsigned long long after) {
+  return ev_read_slice_q<false>(rb, total, limit, pos, lo, hi, ga, ref, ref_last, i0, before, after, nullptr, 0u);
 }
 
 // The rule.  A position is judged when its two counters sum to min_depth or more, and flagged when it is judged and

@@ -1118,6 +1118,50 @@ int walt_meth_nonconv_batch_qual_device(walt_index* idx, const void* d_bases, co
                                         void* d_filt, size_t filt_stride, void* d_tally, const void* d_quals, uint32_t min_qual,
                                         void* stream);
 
+/* ---- called sites: which cytosines are methylated at all ------------------------------------------------------
+ * The reference has no such mode (methylpy's call_methylated_sites and Lister 2009 test every site with a binomial test
+ * against the sample's non-conversion rate and control the false discovery rate per context; MethPipe users take bsrate
+ * and thresholds); the contract is defined here.  The p-value of a site depends on its context and on the pair
+ * (depth, meth) alone, so the device side is exact: a joint histogram of (depth, meth) per context, and an extraction
+ * with a table "smallest significant meth per depth" as its predicate.  The p-values, Benjamini-Hochberg and the table
+ * are the host's (walt_amd/csrc/sitecall_core.h); the device runs no floating point.
+ *
+ * A site is exactly what walt_pileup_extract returns: a covered position f of the range whose R[f] is C or G, with the
+ * context the extraction gives it.  Positions covered on an A or T of R are no sites and appear nowhere here.  For a site,
+ * d = meth + unmeth (in 64 bits: up to 2^33 - 2) and m = meth.
+ *
+ * Histogram.  walt_pileup_depth_hist adds, for every site of [pos_lo, pos_hi) with context c,
+ *   d <= WALT_SITECALL_DEPTH:  hist[c][bin(d, m)] += 1,   bin(d, m) = (d - 1) * (d + 2) / 2 + m   (1 <= d, 0 <= m <= d)
+ *   otherwise:                 deep[c] += 1
+ * into arrays it has zeroed: hist uint64_t[4][WALT_SITECALL_BINS], deep uint64_t[4].  sum(hist[c]) + deep[c] is the number
+ * of records the extraction returns for context c; the result is additive over any partition of a range, all folds are
+ * integer and commutative, and the launch shape (option pile_extract_blocks) cannot change a bit.  Device form: d_hist
+ * (264,160 bytes) and d_deep (32 bytes) are HBM addresses, 8-byte aligned, zeroed by the call itself on `stream`.  The
+ * histogram lives in the caller's memory; the pile-up's table is not used.
+ *
+ * Called sites.  walt_pileup_call_sites writes, ascending by pos, a walt_meth_site for every site of the range with
+ *   d <= WALT_SITECALL_DEPTH and meth >= min_meth[c][d]:  reserved = 0  (a value above d: none at this depth; index 0 of a
+ *                                                         row is never read)
+ *   d >  WALT_SITECALL_DEPTH:                             reserved = 1  (a deep site: the caller judges it)
+ * min_meth: uint32_t[4][128].  With min_meth[c][d] = d + 1 everywhere the call returns exactly the deep sites.  cap, *n_out
+ * and a cap that is too small behave as in walt_pileup_extract[_device]: the host form returns WALT_EINVAL naming both
+ * numbers with *n_out set, the device form leaves *d_n_out > cap, and nothing is written.  Device form: d_min_meth 4-byte,
+ * d_out 16-byte, d_n_out 8-byte aligned.
+ *
+ * Errors and ordering as walt_pileup_extract[_device]: WALT_EINVAL for a null pile-up, a null array, pos_lo > pos_hi,
+ * pos_hi > genome_len or a misaligned device address; the host forms wait for all work on the device first, the device
+ * forms are asynchronous on `stream`.  walt_pileup_call_sites keeps its block offsets in the pile-up's table and counts as
+ * an extraction under "one at a time per pile-up"; walt_pileup_device_bytes is as before. */
+#define WALT_SITECALL_DEPTH 127u          /* depths 1..127 are histogrammed; deeper sites are "deep" */
+#define WALT_SITECALL_BINS  8255u         /* per context: sum over d = 1..127 of (d + 1) = 127 * 130 / 2 */
+int walt_pileup_depth_hist(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, uint64_t* hist /*[4][WALT_SITECALL_BINS]*/,
+                           uint64_t* deep /*[4]*/);
+int walt_pileup_depth_hist_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, void* d_hist, void* d_deep, void* stream);
+int walt_pileup_call_sites(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, const uint32_t* min_meth /*[4][128]*/,
+                           walt_meth_site* out, uint64_t cap, uint64_t* n_out);
+int walt_pileup_call_sites_device(walt_pileup* p, uint32_t pos_lo, uint32_t pos_hi, const void* d_min_meth, void* d_out,
+                                  uint64_t cap, void* d_n_out, void* stream);
+
 /* ---- options ---------------------------------------------------------------------------------
  * Tuning values and test hooks of the mapping calls, per index.  The mapping calls read NO environment
  * variable: an index maps the same way whatever the process environment holds (the library's only

@@ -105,6 +105,18 @@ region_row_dtype = np.dtype([("sites", "<u4"), ("covered", "<u4"), ("meth", "<u8
 region_levels_dtype = np.dtype([("row", region_row_dtype, (5,))])
 REGIONS_MAX = 1 << 22  # regions of one Pileup.regions_device call at most (WALT_REGIONS_MAX)
 assert region_dtype.itemsize == 8 and region_row_dtype.itemsize == 32 and region_levels_dtype.itemsize == 160
+# called sites (include/walt_amd.h, "called sites"): the joint histogram of (depth, meth) per context and its bins
+SITECALL_DEPTH = 127   # WALT_SITECALL_DEPTH: depths 1 .. 127 are histogrammed, deeper sites are "deep"
+SITECALL_BINS = 8255   # WALT_SITECALL_BINS: bins per context
+
+
+def sitecall_bin(d, m):
+    """The bin of a site of depth d (1 .. SITECALL_DEPTH) with m methylated calls (0 .. d)."""
+    if not (1 <= d <= SITECALL_DEPTH and 0 <= m <= d):
+        raise ValueError("sitecall_bin: depth %r is not 1 to %d, or meth %r is not 0 to the depth" % (d, SITECALL_DEPTH, m))
+    return (d - 1) * (d + 2) // 2 + m
+
+
 # walt_nonconv_tally / walt_nonconv_rule (include/walt_amd.h, "non-converted reads")
 nonconv_tally_dtype = np.dtype([("meth", "<u2"), ("total", "<u2"), ("run", "<u2"), ("reserved", "<u2")])
 nonconv_rule_dtype = np.dtype([("min_meth", "<u4"), ("min_run", "<u4"), ("min_percent", "<u4"), ("min_total", "<u4")])
@@ -246,6 +258,10 @@ def lib(pattern=None):
     L.walt_pileup_extract_device.argtypes = [vp, u32, u32, vp, u64, vp, vp, vp]
     L.walt_pileup_levels.argtypes = [vp, u32, u32, vp]
     L.walt_pileup_levels_device.argtypes = [vp, u32, u32, vp, vp]
+    L.walt_pileup_depth_hist.argtypes = [vp, u32, u32, vp, vp]
+    L.walt_pileup_depth_hist_device.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.walt_pileup_call_sites.argtypes = [vp, u32, u32, vp, vp, u64, c.POINTER(u64)]
+    L.walt_pileup_call_sites_device.argtypes = [vp, u32, u32, vp, vp, u64, vp, vp]
     L.walt_pileup_read.argtypes = [vp, u32, u32, vp, vp]
     L.walt_pileup_add.argtypes = [vp, u32, u32, vp, vp]
     L.walt_pileup_regions_workspace_bytes.argtypes = [u32]
@@ -1295,6 +1311,47 @@ class Pileup:
     def levels_device(self, pos_lo, pos_hi, d_out, stream=0):
         """Device-pointer form (walt_pileup_levels_device): 656 bytes at d_out; asynchronous."""
         self._index._ck(self._L.walt_pileup_levels_device(self._h, int(pos_lo), int(pos_hi), d_out, stream))
+
+    def depth_hist(self, pos_lo=0, pos_hi=None):
+        """The joint histogram of the sites of [pos_lo, pos_hi) (walt_pileup_depth_hist): (hist uint64[4][SITECALL_BINS] by
+        context and sitecall_bin(depth, meth), deep uint64[4]: the sites deeper than SITECALL_DEPTH)."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        hist = np.zeros((4, SITECALL_BINS), dtype=np.uint64)
+        deep = np.zeros(4, dtype=np.uint64)
+        self._index._ck(self._L.walt_pileup_depth_hist(self._h, int(pos_lo), int(pos_hi), _ptr(hist), _ptr(deep)))
+        return hist, deep
+
+    def depth_hist_device(self, pos_lo, pos_hi, d_hist, d_deep, stream=0):
+        """Device-pointer form (walt_pileup_depth_hist_device): 8 * 4 * SITECALL_BINS bytes at d_hist, 32 at d_deep, both
+        zeroed by the call; asynchronous."""
+        self._index._ck(self._L.walt_pileup_depth_hist_device(self._h, int(pos_lo), int(pos_hi), d_hist, d_deep, stream))
+
+    @staticmethod
+    def _min_meth_arg(min_meth):
+        table = np.ascontiguousarray(min_meth, dtype=np.uint32)
+        if table.shape != (4, SITECALL_DEPTH + 1):
+            raise ValueError("min_meth must have shape (4, %d): context by depth" % (SITECALL_DEPTH + 1))
+        return table
+
+    def call_sites(self, min_meth, pos_lo=0, pos_hi=None):
+        """The sites of [pos_lo, pos_hi) with meth >= min_meth[context][depth] (reserved 0), and every site deeper than
+        SITECALL_DEPTH (reserved 1), ascending (walt_pileup_call_sites): meth_site_dtype[n]."""
+        pos_hi = self._index.genome_len if pos_hi is None else pos_hi
+        table = self._min_meth_arg(min_meth)
+        args = (self._h, int(pos_lo), int(pos_hi), _ptr(table))
+        n = ctypes.c_uint64(0)
+        rc = self._L.walt_pileup_call_sites(*args, None, 0, ctypes.byref(n))
+        if rc != WALT_OK and n.value == 0:
+            self._index._ck(rc)
+        out = np.zeros(n.value, dtype=meth_site_dtype)
+        if n.value:
+            self._index._ck(self._L.walt_pileup_call_sites(*args, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def call_sites_device(self, pos_lo, pos_hi, d_min_meth, d_out, cap, d_n_out, stream=0):
+        """Device-pointer form (walt_pileup_call_sites_device): d_min_meth uint32[4][128]; asynchronous."""
+        self._index._ck(self._L.walt_pileup_call_sites_device(self._h, int(pos_lo), int(pos_hi), d_min_meth, d_out, int(cap),
+                                                              d_n_out, stream))
 
     def regions(self, regions):
         """The summaries of many ranges in one call (walt_pileup_regions): `regions` is an (n, 2) integer array of

@@ -916,5 +916,67 @@ inline void put_variant_block(Sink& out, const uint64_t tot[5], uint32_t min_dep
   out.lit(num);
 }
 
+// ---------------------------------------------------------------- <out>.methsites, <out>.sitestats (bin/walt -MS)
+// The value of -MSR (0 <= r < 1) or -MSA (0 < a < 1): a decimal fraction in digits, at most one point and an optional
+// exponent, nothing in front of or behind it, at most 24 characters.
+inline bool parse_site_fraction(const std::string& text, bool zero_allowed, double& out) {
+  if (text.empty() || text.size() > 24) return false;
+  bool digit = false;
+  for (size_t i = 0; i < text.size(); ++i) {
+    const char c = text[i];
+    if (c >= '0' && c <= '9') { digit = true; continue; }
+    if (c == '.' || c == 'e' || c == 'E') continue;
+    if ((c == '-' || c == '+') && i > 0 && (text[i - 1] == 'e' || text[i - 1] == 'E')) continue;
+    return false;
+  }
+  if (!digit || text[0] == 'e' || text[0] == 'E') return false;
+  char* end = nullptr;
+  const double v = strtod(text.c_str(), &end);
+  if (!end || *end != '\0' || !(v >= 0.0) || !(v < 1.0) || (v == 0.0 && !zero_allowed)) return false;
+  out = v;
+  return true;
+}
+// The value of -MSD: the minimum depth of a tested site, 1 to 127.
+inline bool parse_site_depth(const std::string& text, uint32_t& out) { return parse_variant_value(text, 1, 127, out); }
+// One called site (include/walt_amd.h, "called sites") as a line, tab-separated:
+//   chrom  pos  strand  context  meth  unmeth  pval
+// pos 0-based within the chromosome; the first six columns are those of <out>.methcounts; pval %.6g.
+inline void put_site_line(Sink& out, const std::string& chrom, uint32_t chrom_start, const walt_meth_site& s, double pval) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  out.put(chrom); out.ch('\t'); out.u32(s.pos - chrom_start); out.ch('\t'); out.ch((char)s.strand); out.ch('\t');
+  out.lit(ctx[s.context & 3]); out.ch('\t'); out.u32(s.meth); out.ch('\t'); out.u32(s.unmeth);
+  char num[48];
+  snprintf(num, sizeof num, "\t%.6g\n", pval);
+  out.lit(num);
+}
+// One read file's block of <out>.sitestats.  control: the sequence's name, or "given" under -MSR, where the control's
+// counts are NA (counts == nullptr); has_rate false: the control has no call, the rate is NA and nothing was called.
+// Then the rule and one line per context: context <TAB> tested <TAB> called <TAB> cutoff (%.6g, NA when no group passed).
+struct SiteStatsRow {
+  uint64_t tested, called;
+  bool has_cutoff;
+  double cutoff;
+};
+inline void put_sitestats_block(Sink& out, const std::string& control, const uint64_t* counts, bool has_rate, double rate,
+                                double alpha, uint32_t min_depth, const SiteStatsRow row[4]) {
+  static const char* ctx[4] = {"CpG", "CHG", "CHH", "unknown"};
+  char num[160];
+  out.lit("control: "); out.put(control); out.ch('\n');
+  if (counts) snprintf(num, sizeof num, "control meth: %llu\ncontrol unmeth: %llu\n", (unsigned long long)counts[0], (unsigned long long)counts[1]);
+  else snprintf(num, sizeof num, "control meth: NA\ncontrol unmeth: NA\n");
+  out.lit(num);
+  if (has_rate) snprintf(num, sizeof num, "non-conversion rate: %.6g\n", rate);
+  else snprintf(num, sizeof num, "non-conversion rate: NA\n");
+  out.lit(num);
+  snprintf(num, sizeof num, "rule\t%.6g\t%u\n", alpha, min_depth);
+  out.lit(num);
+  for (int c = 0; c < 4; ++c) {
+    if (row[c].has_cutoff) snprintf(num, sizeof num, "%s\t%llu\t%llu\t%.6g\n", ctx[c], (unsigned long long)row[c].tested,
+                                    (unsigned long long)row[c].called, row[c].cutoff);
+    else snprintf(num, sizeof num, "%s\t%llu\t%llu\tNA\n", ctx[c], (unsigned long long)row[c].tested, (unsigned long long)row[c].called);
+    out.lit(num);
+  }
+}
+
 }  // namespace hostio
 #endif  // WALT_AMD_HOSTIO_H_

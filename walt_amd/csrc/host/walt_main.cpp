@@ -24,6 +24,7 @@
 #include <exception>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <numeric>
 #include <sstream>
 #include <stdexcept>
@@ -35,6 +36,7 @@
 
 #include "../../../include/walt_amd.h"
 #include "hostio.h"
+#include "../sitecall_core.h"
 
 using std::string;
 using std::vector;
@@ -60,8 +62,8 @@ struct Options {
   bool levels = false;  // -ML: genome-wide methylation levels of the pile-up (walt_pileup_levels): <out>.levels
   string regions_file;  // -MR: methylation levels per region of a BED file (walt_pileup_regions): <out>.regions
   bool regions() const { return !regions_file.empty(); }
-  bool piling() const { return methcounts || levels || regions() || variants; }  // the run keeps pile-ups
-  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic || epialleles || variants; }  // something takes the methylation calls
+  bool piling() const { return methcounts || levels || regions() || variants || sites; }  // the run keeps pile-ups
+  bool consumer() const { return meth || methcounts || mbias || levels || regions() || allelic || epialleles || variants || sites; }  // something takes the methylation calls
   bool dedup = false;  // -D: PCR duplicates marked on the device (walt_dedup_*) and kept out of -M / -MC: <out>.dupstats
   bool no_overlap = false;  // -NO: a base both mates of a unique proper pair cover is called once, for mate 1 (walt_pair_overlap_batch)
   bool mbias = false;  // -MB: methylation bias by read position (walt_meth_pileup_batch_mbias): <out>.mbias
@@ -74,6 +76,15 @@ struct Options {
   bool variants = false;
   uint32_t variant_depth = 5, variant_percent = 50;  // -MVD, -MVP: min_depth and max_percent of the rule
   bool variant_depth_given = false, variant_percent_given = false;
+  // -MS: methylated sites called at the end of a read file (walt_pileup_depth_hist, walt_pileup_call_sites): a binomial test
+  // per site against the non-conversion rate and Benjamini-Hochberg per context: <out>.methsites, <out>.sitestats.
+  // -MSN: the control sequence the rate is taken from (left out of the test); -MSR: the rate itself; -MSA: the FDR;
+  // -MSD: the minimum depth of a tested site
+  bool sites = false;
+  string site_control;
+  double site_rate = 0.0, site_alpha = 0.01;
+  uint32_t site_depth = 1;
+  bool site_control_given = false, site_rate_given = false, site_alpha_given = false, site_depth_given = false;
   // -MQ, -MQO: a read base whose Phred quality is below min_qual gets no methylation call and gives no opposite-strand
   // evidence (walt_meth_pileup_batch_qual, walt_meth_nonconv_batch_qual); qual_offset: the FASTQ's Phred offset.  0: no floor
   uint32_t min_qual = 0, qual_offset = 33;
@@ -157,6 +168,30 @@ static Options parse(int argc, const char** argv) {
         die(a + " (variant sites) wants a percentage from 0 to 99, not \"" + v + "\"");
       o.variant_percent_given = true;
     }
+    else if (is_opt(a, "MS", "sites") || a == "--call-sites") o.sites = true;  // extension: methylated sites by binomial test and FDR
+    else if (is_opt(a, "MSN", "sites-control")) {  // extension: the unmethylated control sequence
+      o.site_control = val();
+      if (o.site_control.empty()) die(a + " (called sites) wants the name of a sequence of the index");
+      o.site_control_given = true;
+    }
+    else if (is_opt(a, "MSR", "sites-rate")) {  // extension: the non-conversion rate, given
+      const string v = val();
+      if (!hostio::parse_site_fraction(v, true, o.site_rate))
+        die(a + " (called sites) wants a non-conversion rate r with 0 <= r < 1, not \"" + v + "\"");
+      o.site_rate_given = true;
+    }
+    else if (is_opt(a, "MSA", "sites-alpha")) {  // extension: the false discovery rate
+      const string v = val();
+      if (!hostio::parse_site_fraction(v, false, o.site_alpha))
+        die(a + " (called sites) wants a false discovery rate a with 0 < a < 1, not \"" + v + "\"");
+      o.site_alpha_given = true;
+    }
+    else if (is_opt(a, "MSD", "sites-min-depth")) {  // extension: the minimum depth of a tested site
+      const string v = val();
+      if (!hostio::parse_site_depth(v, o.site_depth))
+        die(a + " (called sites) wants a depth from 1 to 127, not \"" + v + "\"");
+      o.site_depth_given = true;
+    }
     else if (is_opt(a, "MQ", "min-qual") || a == "--min-base-quality") {  // extension: a quality floor under the methylation calls
       const string v = val();
       if (!hostio::parse_min_qual(v, o.min_qual))
@@ -230,6 +265,11 @@ static Options parse(int argc, const char** argv) {
     die("-MEN (the fewest reads of a written window) goes with -ME: without it there is nothing for it to do");
   if ((o.variant_depth_given || o.variant_percent_given) && !o.variants)
     die("-MVD / -MVP (the rule that flags a variant site) go with -MV: without it there is nothing for them to do");
+  if ((o.site_control_given || o.site_rate_given || o.site_alpha_given || o.site_depth_given) && !o.sites)
+    die("-MSN / -MSR / -MSA / -MSD (the control, the rate, the FDR and the minimum depth of called sites) go with -MS: without it there is nothing for them to do");
+  if (o.sites && o.site_control_given == o.site_rate_given)
+    die(o.site_control_given ? "-MS (called sites) takes its non-conversion rate from -MSN (a control sequence) or from -MSR (the rate itself), not from both"
+                             : "-MS (called sites) wants the non-conversion rate: -MSN <name> (an unmethylated control sequence of the index) or -MSR <r>");
   if (o.qual_offset_given && !o.min_qual)
     die("-MQO (the FASTQ's Phred offset) goes with -MQ: without it there is nothing for it to do");
   if (o.min_qual && !o.consumer())
@@ -339,7 +379,7 @@ struct SideFiles {  // the _ambiguous / _unmapped files of StatSingleReads (mapp
 
 // The files a run writes beside its main output, <out><suffix>: main truncates those whose option is on (walt.cpp:230-233
 // for the first), and the end of every read file appends its block to each.
-enum { kMapstats, kMethstats, kMethcounts, kLevels, kRegions, kMbias, kAllelic, kEpialleles, kDupstats, kFilterstats, kVariants, kVariantstats, kOutputs };
+enum { kMapstats, kMethstats, kMethcounts, kLevels, kRegions, kMbias, kAllelic, kEpialleles, kDupstats, kFilterstats, kVariants, kVariantstats, kMethsites, kSitestats, kOutputs };
 static const struct { bool (*on)(const Options&); const char* suffix; } kOutput[kOutputs] = {
     {[](const Options&) { return true; }, ".mapstats"},
     {[](const Options& o) { return o.meth; }, ".methstats"},
@@ -353,6 +393,8 @@ static const struct { bool (*on)(const Options&); const char* suffix; } kOutput[
     {[](const Options& o) { return o.filtering(); }, ".filterstats"},
     {[](const Options& o) { return o.variants; }, ".variants"},
     {[](const Options& o) { return o.variants; }, ".variantstats"},
+    {[](const Options& o) { return o.sites; }, ".methsites"},
+    {[](const Options& o) { return o.sites; }, ".sitestats"},
 };
 struct Append {  // one of them, open for appending
   OutFile f;
@@ -654,8 +696,116 @@ static void write_variants(const Options& o, const string& out_file, walt_pileup
   if (o.verbose) fwrite(block.p, 1, block.n, stderr);
 }
 
+// ---------------------------------------------------------------- -MS: methylated sites by binomial test and FDR
+// The p-value of a site depends on its context, depth and meth alone: the device gives the joint histogram of the sites
+// outside the control and the deep sites one by one, the host tests every occupied bin once (sitecall_core.h) and turns
+// each context's cutoff into the table the extraction takes as its predicate.  Everything reads the first device's folded
+// counters.
+static uint32_t site_control_of(const Options& o, const GenomeInfo& g) {  // the control's sequence, refused before a read is mapped
+  for (size_t i = 0; i < g.name.size(); ++i)
+    if (g.name[i] == o.site_control) return (uint32_t)i;
+  die("-MSN (called sites): the index has no sequence named \"" + o.site_control + "\"");
+  return 0;
+}
+static void write_sites(const Options& o, const string& out_file, walt_pileup* p, const GenomeInfo& g) {
+  using walt::kSiteBins;
+  const uint32_t genome_len = g.start.back();
+  // the control's range [c_lo, c_hi) (empty under -MSR) and its counts
+  uint32_t c_lo = 0, c_hi = 0;
+  uint64_t counts[2] = {0, 0};
+  double rate = o.site_rate;
+  bool has_rate = true;
+  if (o.site_control_given) {
+    const uint32_t c = site_control_of(o, g);
+    c_lo = g.start[c]; c_hi = g.start[c + 1];
+    walt_levels lv;
+    check(walt_pileup_levels(p, c_lo, c_hi, &lv));
+    for (int r = 0; r < 4; ++r) { counts[0] += lv.row[r].meth; counts[1] += lv.row[r].unmeth; }
+    has_rate = counts[0] + counts[1] != 0;
+    rate = has_rate ? (double)counts[0] / ((double)counts[0] + (double)counts[1]) : 0.0;
+    if (has_rate && counts[1] == 0) {
+      has_rate = false;
+      fprintf(stderr, "[walt_amd sites: every call on the control %s is methylated: no rate below 1, no site is called]\n", o.site_control.c_str());
+    } else if (!has_rate) {
+      fprintf(stderr, "[walt_amd sites: the control %s has no call: no non-conversion rate, no site is called]\n", o.site_control.c_str());
+    }
+  }
+  const uint32_t part[2][2] = {{0, c_lo}, {c_hi, genome_len}};  // in front of and behind the control
+  hostio::SiteStatsRow row[4];
+  memset(row, 0, sizeof row);
+  double cutoff[4] = {0, 0, 0, 0};
+  if (has_rate) {
+    vector<uint64_t> hist(4 * (size_t)kSiteBins, 0), one(4 * (size_t)kSiteBins);
+    uint64_t deep[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 2; ++k) {
+      uint64_t d4[4];
+      check(walt_pileup_depth_hist(p, part[k][0], part[k][1], one.data(), d4));
+      for (size_t i = 0; i < hist.size(); ++i) hist[i] += one[i];
+      for (int c = 0; c < 4; ++c) deep[c] += d4[c];
+    }
+    // the deep sites: the table that is d + 1 everywhere returns exactly them.  Fetched in the windows .methcounts uses and
+    // kept as one entry per (depth, meth) pair with its count, so the host holds a window's records and the distinct pairs
+    const uint64_t window = std::min<uint64_t>(kCountsWindow, genome_len);
+    vector<uint32_t> table(walt::kSiteTable);
+    for (uint32_t i = 0; i < walt::kSiteTable; ++i) table[i] = (i & walt::kSiteDepth) + 1u;
+    vector<walt_meth_site> buf((size_t)window);
+    std::map<std::pair<uint64_t, uint64_t>, uint64_t> pairs_of[4];
+    if (deep[0] + deep[1] + deep[2] + deep[3])
+      for_each_window(genome_len, window, [&](uint32_t w_lo, uint32_t w_hi) {
+        for (int k = 0; k < 2; ++k) {
+          const uint32_t lo = std::max(w_lo, part[k][0]), hi = std::min(w_hi, part[k][1]);
+          if (lo >= hi) continue;
+          uint64_t n = 0;
+          check(walt_pileup_call_sites(p, lo, hi, table.data(), buf.data(), window, &n));
+          for (uint64_t i = 0; i < n; ++i) pairs_of[buf[i].context & 3][{(uint64_t)buf[i].meth + buf[i].unmeth, (uint64_t)buf[i].meth}] += 1;
+        }
+      });
+    vector<walt::SitecallDeep> deep_of[4];
+    for (int c = 0; c < 4; ++c)
+      for (const auto& e : pairs_of[c]) deep_of[c].push_back({e.first.first, e.first.second, e.second});
+    for (int c = 0; c < 4; ++c) {
+      const walt::SitecallContext r = walt::sitecall_context(hist.data() + (size_t)c * kSiteBins, deep_of[c].data(), deep_of[c].size(), rate,
+                                                              o.site_alpha, o.site_depth, table.data() + (size_t)c * (walt::kSiteDepth + 1));
+      row[c] = {r.tested, r.called, r.has_cutoff, r.cutoff};
+      cutoff[c] = r.has_cutoff ? r.cutoff : -1.0;  // (no p-value is at or below it)
+    }
+    // the called sites, in the windows .methcounts uses; a deep record stays when its own p-value meets its context's cutoff
+    vector<double> pv_of(kSiteBins);  // a shallow site's p-value depends on (depth, meth) alone
+    for (uint32_t d = 1; d <= walt::kSiteDepth; ++d)
+      for (uint32_t m = 0; m <= d; ++m) pv_of[walt::sitecall_bin(d, m)] = walt::sitecall_pval(d, m, rate);
+    Append sf(out_file, kMethsites);
+    uint32_t chr = 0;
+    Sink out;
+    for_each_window(genome_len, window, [&](uint32_t w_lo, uint32_t w_hi) {
+      out.clear();
+      for (int k = 0; k < 2; ++k) {
+        const uint32_t lo = std::max(w_lo, part[k][0]), hi = std::min(w_hi, part[k][1]);
+        if (lo >= hi) continue;
+        uint64_t n = 0;
+        check(walt_pileup_call_sites(p, lo, hi, table.data(), buf.data(), window, &n));
+        for (uint64_t i = 0; i < n; ++i) {
+          const walt_meth_site& s = buf[i];
+          const double pv = s.reserved ? walt::sitecall_pval((uint64_t)s.meth + s.unmeth, s.meth, rate)
+                                       : pv_of[walt::sitecall_bin(s.meth + s.unmeth, s.meth)];
+          if (s.reserved && !(pv <= cutoff[s.context & 3])) continue;
+          while (s.pos >= g.start[chr + 1]) ++chr;  // (ascending positions)
+          hostio::put_site_line(out, g.name[chr], g.start[chr], s, pv);
+        }
+      }
+      sf.write(out);
+    });
+  }
+  Sink block;
+  hostio::put_sitestats_block(block, o.site_control_given ? o.site_control : string("given"), o.site_control_given ? counts : nullptr, has_rate,
+                              rate, o.site_alpha, o.site_depth, row);
+  Append(out_file, kSitestats).write(block);
+  if (o.verbose) fwrite(block.p, 1, block.n, stderr);
+}
+
 // the end of a read file: under -MV the variant sites first (ev: the evidence, as many objects as pile-ups); then
-// <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the counters cleared
+// <out>.methcounts (-MC) as ever, then <out>.levels (-ML) and <out>.regions (-MR), then the called sites (-MS:
+// <out>.methsites, <out>.sitestats), which like the two before them read the first device's folded counters; then the
+// counters cleared
 static void end_of_file_pileups(const Options& o, const string& out_file, PileUps& ps, PileUps& ev, const GenomeInfo& g) {
   bool folded = false;
   if (o.variants) {
@@ -673,9 +823,10 @@ static void end_of_file_pileups(const Options& o, const string& out_file, PileUp
       write_window_table(t, ps, out_file, g, o.verbose);
     }
   }
-  if ((o.levels || o.regions()) && !folded) fold_pileups(ps, g.start.back());
+  if ((o.levels || o.regions() || o.sites) && !folded) fold_pileups(ps, g.start.back());
   if (o.levels) write_levels(out_file, ps, g, o.verbose);
   if (o.regions()) write_regions(out_file, ps);
+  if (o.sites) write_sites(o, out_file, ps.p[0], g);
   for (walt_pileup* q : ps.p) check(walt_pileup_clear(q));
   for (walt_pileup* q : ev.p) check(walt_pileup_clear(q));
 }
@@ -1188,6 +1339,7 @@ static void process_se(const Options& o, const string& reads_file, const string&
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0, t_write = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
+  if (o.sites && o.site_control_given) (void)site_control_of(o, g);
   OutFile fout;
   if (!fout.open_append(out_file)) die("cannot open input file " + out_file);
   SideFiles side;
@@ -1449,6 +1601,7 @@ static void process_pe(const Options& o, const string& file1, const string& file
   double t_index = now_s() - t0, t_load = 0, t_map = 0, t_out = 0;
   GenomeInfo g = genome_of(dev.idx[0]);
   if (o.regions()) g_regions.resolve(g, o.verbose);  // (a region beyond its chromosome: refused before a read is mapped)
+  if (o.sites && o.site_control_given) (void)site_control_of(o, g);
   hostio::FastqReader rd[2];
   rd[0].want_quals = rd[1].want_quals = o.min_qual != 0;
   rd[0].open(f1, T);
@@ -1658,7 +1811,7 @@ int main(int argc, const char** argv) {
   g_t_main = now_s();
   try {
     if (argc == 1) {
-      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -MV -MVD <n> -MVP <p> -MQ <n> -MQO <b> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
+      fprintf(stderr, "Usage: walt -i <index> -r <reads> | -1 <reads1> -2 <reads2> -o <out> [-m -N -a -u -C -A -P -R -RP -M -MC -ML -MR <bed> -D -NO -MB -MA -ME -MEN <n> -MV -MVD <n> -MVP <p> -MS -MSN <name> -MSR <r> -MSA <a> -MSD <n> -MQ <n> -MQO <b> -I5 <n> -I3 <n> -I5R2 <n> -I3R2 <n> -F <n> -FC <n> -FP <p> -FM <m> -b -k -L -sam -v -t -g <gpu>[,<gpu>...]]\n");
       return EXIT_SUCCESS;
     }
     Options o = parse(argc, argv);
